@@ -12,6 +12,10 @@ other half's queue chains; every timed step is still one pass of every block thr
 collective; the per-instance closed-form records are gathered to rank 0 (RCCL) inside the timed region.
 
 Prints ONE JSON line (rank 0). See DESIGN.md "Measurement" for the roofline/cpu_baseline definitions.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given and prints the
+line. Everything else it can measure or check (the oracle comparison of the timed region, the inputs-from-host and sensitivity
+legs, the hash-circuit, setup-commitment and full-block legs, the CPU baselines) runs only with --full.
 """
 import argparse
 import json
@@ -19,8 +23,10 @@ import os
 import sys
 import time
 
-import numpy as np
-import torch
+T_START = time.perf_counter()  # (before torch and the library load: the set-up the wall-time breakdown reports)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -40,6 +46,47 @@ def make_inputs(blocks, n, rank, dev):
     masks = torch.randint(-2**31, 2**31 - 1, (blocks, 1, 8), generator=g, dtype=torch.int64).to(torch.int32).to(dev)
     q[:, :, 4:12] ^= masks
     return base, q.contiguous()
+
+
+DUMP_TRACE_CELLS = 1 << 20  # cells of the trace ring in --dump-outputs, all written slots together (16 MB as lo / hi float64 pairs)
+DUMP_RECORD_WORDS = 1 << 21  # closed-form record words in --dump-outputs before they are sampled too (32 MB)
+
+
+def u64_as_f64_pairs(words):
+    """u64 words -> float64 [..., 2] = (low 32 bits, high 32 bits): exact, and comparable with any float tool"""
+    w = np.ascontiguousarray(words).view(np.uint64)
+    return np.stack([(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(out_dir, gathered, rings, slot_instances, dev):
+    """What the timed path's last step handed its caller, as .npy files (u64 words as float64 (lo, hi) pairs, see u64_as_f64_pairs):
+    closed_form_records.npy — the closed-form records gathered to rank 0, [instance, 22 words, 2] (a fixed seeded sample of instances
+    when there are more than DUMP_RECORD_WORDS words); trace_sample.npy — DUMP_TRACE_CELLS cells at fixed seeded positions (column-major
+    cell index) of every ring slot the last step wrote, [slot, cell, 2]; trace_sample_instances.npy — the instance (row of the records)
+    each of those slots holds; trace_sample_cells.npy — the sampled cell indices. Positions depend on the seed only, so two runs with the
+    same arguments compare file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    rec = gathered.cpu().numpy().reshape(gathered.shape[0], -1).view(np.uint64)
+    if rec.size > DUMP_RECORD_WORDS:
+        rows = np.sort(np.random.default_rng(1).choice(rec.shape[0], DUMP_RECORD_WORDS // rec.shape[1], replace=False))
+        rec = rec[rows]
+    np.save(os.path.join(out_dir, "closed_form_records.npy"), u64_as_f64_pairs(rec))
+    slots = [(ring, s) for ring, written in zip(rings, slot_instances) for s in range(len(written))]
+    n_cells = rings[0].n_cols * rings[0].n_rows
+    cells = np.sort(np.random.default_rng(2).integers(0, n_cells, max(1, DUMP_TRACE_CELLS // max(1, len(slots)))))
+    idx = torch.from_numpy(cells.astype(np.int64)).to(dev)
+    stage = torch.empty(n_cells, dtype=torch.int64, device=dev)
+    lib = native.load()
+    sample = np.empty((len(slots), cells.size), np.uint64)
+    for k, (ring, s) in enumerate(slots):
+        assert ring.ctx.pointer_mode == native.PTR_DEVICE and ring.n_cols * ring.n_rows == n_cells
+        native._check(lib.zkw_trace_get(ring.handle, s, 0, ring.n_cols, stage.data_ptr()))  # device to device, on the context's stream
+        ring.ctx.synchronize()
+        sample[k] = stage.index_select(0, idx).cpu().numpy().view(np.uint64)
+    del stage
+    np.save(os.path.join(out_dir, "trace_sample.npy"), u64_as_f64_pairs(sample))
+    np.save(os.path.join(out_dir, "trace_sample_instances.npy"), np.array([i for w in slot_instances for i in w], np.float64))
+    np.save(os.path.join(out_dir, "trace_sample_cells.npy"), cells.astype(np.float64))
 
 
 def cpu_baseline(base, sample_blocks):
@@ -606,7 +653,18 @@ def main():
     ap.add_argument("--launcher-self-test", action="store_true",
                     help="CPU only, no circuit work: the N ranks exchange synthetic closed-form records over gloo and over the C ABI's "
                          "TCP transport and rank 0 prints a line marked as a self-test (tests/test_bench_launcher.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side leg: the oracle comparison of the timed region, inputs from host, "
+                         "sensitivity, hash circuits, setup commitment, full block and the CPU baselines (each --no-* flag still "
+                         "drops its leg). Off: the run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float64; u64 words as (low, high) 32-bit pairs): "
+                         "the gathered closed-form records and a fixed seeded sample of every trace slot it wrote. The inputs "
+                         "depend on the arguments only (with --blocks 0, on the batch that fits the free HBM: pass --blocks to pin it); "
+                         "bench_outputs/ is git-ignored for it")
     args = ap.parse_args()
+    if not args.full:
+        args.no_validate = args.no_h2d = args.no_sensitivity = args.no_hash_circuits = args.no_full_block = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))  # `python bench.py --gpus N` on its own: one process per GPU, this process only waits for them
@@ -811,6 +869,7 @@ def main():
     stagger_s = 0.72 * n * per_item_s * 2 / P if P > 1 else 0.0
     if P > 1 and os.environ.get("ZKW_SYNTH_TURNS", "1") != "0":
         stagger_s = 0.5  # with the synthesis phases taking turns the pipelines order themselves; a short offset starts that
+    t_warm = time.perf_counter()
     for k in range(args.warmup):
         run_steps(1, 0.0)
     if args.stagger_ms >= 0:
@@ -835,6 +894,13 @@ def main():
             a = prof.get(k, (0.0, 0))
             prof[k] = (a[0] + ms, a[1] + cnt)
         c.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        # the ring slots the last pass of each pipeline wrote, and the instance each holds: its last launch wrote instances last_first.. into
+        # slots 0.., the launch before it the remaining slots
+        last_first = (n_inst_p - 1) // ring_p * ring_p
+        slot_instances = [[p * n_inst_p + (last_first + s if last_first + s < n_inst_p else last_first - ring_p + s)
+                           for s in range(min(ring_p, n_inst_p))] for p in range(P)]
+        dump_outputs(args.dump_outputs, gathered, rings, slot_instances, dev)
 
     # ---- inputs arriving from host memory. The throughput leg's queries are resident in HBM; a host hands them over
     # from its own memory (external_calls::run's witness vectors). A true double buffer of the step's inputs needs twice their HBM
@@ -1105,6 +1171,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,  # false: the side legs below (validation, inputs_from_host, sensitivity, full_block, ...) did not run
             "ms_per_step": dt / args.steps * 1e3,
             "per_rank_circuits_per_s": [n_inst_local * args.steps / d_ for d_ in dt_ranks],  # each rank's own clock over the same timed region
             "higher_is_better": True,
@@ -1189,6 +1256,8 @@ def main():
                 out["full_block"]["speedup_vs_cpu_concurrent_builders"] = cpu_fb["wall_concurrent_ms"] / full_block["wall_ms"]
                 out["full_block"]["builders_gpu_over_cpu_concurrent"] = full_block["builders_ms"] / cpu_fb["builders_concurrent_ms"]
         print(json.dumps(out), flush=True)
+        print(f"[bench] wall time: set-up {t_warm - T_START:.1f} s, warm-up {t0 - t_warm:.1f} s, timed {dt:.1f} s, after the timed steps "
+              f"{time.perf_counter() - t0 - dt:.1f} s", file=sys.stderr, flush=True)
     parallel.barrier()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -105,9 +105,9 @@ w = o.append
 w(f"# rocprofv3 summaries, round {ROUND[1:].lstrip('0')} (MI355X, gfx950, ROCm 7.2) — generated by tools/make_profile_readme.py {ROUND}\n")
 w("Commands (`tools/run_round_profiles.sh` runs all of them on the GPU box; `cd /tmp && export TMPDIR=/tmp` first):\n")
 w("```")
-w("python bench.py                                                                                   # bench_default.json")
-w("python bench.py --pipelines 1 --no-cpu-baseline --no-full-block                                   # bench_sequential.json")
-w("rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline         # bench_default_kernel_stats.csv, bench_default_under_rocprofv3.json")
+w("python bench.py --full                                                                            # bench_default.json")
+w("python bench.py --full --pipelines 1 --no-cpu-baseline --no-full-block                            # bench_sequential.json")
+w("rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu-baseline  # bench_default_kernel_stats.csv, bench_default_under_rocprofv3.json")
 w("rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -- python bench.py --pipelines 1 --steps 1 --warmup 0 --no-cpu-baseline --no-full-block   # bench_pmc_WRITE_SIZE.*")
 w("rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -- python bench.py --pipelines 1 --steps 1 --warmup 0 --no-cpu-baseline --no-full-block   # bench_pmc_FETCH_SIZE.*")
 w("ZKW_BLOCK_PROFILE=1 python tools/probe_block.py                                                   # full_block_probe.txt")

@@ -9,15 +9,15 @@ mkdir -p "$OUT"
 OUT=$(cd "$OUT" && pwd)
 export TMPDIR=/tmp
 export ZKW_ROOT="$ROOT"
-# 1. the default bench (throughput leg + full-block leg + CPU legs), without a profiler
+# 1. the bench with every side leg (--full: throughput leg + full-block leg + CPU legs), without a profiler
 S0=$(date +%s)
-timeout -s KILL 1800 python bench.py --steps 20 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-echo "python bench.py --steps 20: $(( $(date +%s) - S0 )) s of wall time" > "$OUT/bench_wall_time.txt"
-timeout -s KILL 900 python bench.py --pipelines 1 --no-cpu-baseline --no-full-block --no-h2d --no-sensitivity > "$OUT/bench_sequential.json" 2> "$OUT/bench_sequential.err"
+timeout -s KILL 1800 python bench.py --full --steps 20 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+echo "python bench.py --full --steps 20: $(( $(date +%s) - S0 )) s of wall time" > "$OUT/bench_wall_time.txt"
+timeout -s KILL 900 python bench.py --full --pipelines 1 --no-cpu-baseline --no-full-block --no-h2d --no-sensitivity > "$OUT/bench_sequential.json" 2> "$OUT/bench_sequential.err"
 # 2. the same command under rocprofv3 --kernel-trace --stats, the batched full-block leg with its 512 blocks in flight included (round 5: that leg
 #    died inside the HIP runtime under the profiler with ~500 host threads; round 6 has one thread per batch)
 cd /tmp && rm -rf /tmp/prof_stats && timeout -s KILL 1800 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- \
-    python "$ROOT/bench.py" --steps 5 --no-cpu-baseline --no-sensitivity > "$OUT/bench_default_under_rocprofv3.json" 2> "$OUT/rocprof_stats.err"
+    python "$ROOT/bench.py" --full --steps 5 --no-cpu-baseline --no-sensitivity > "$OUT/bench_default_under_rocprofv3.json" 2> "$OUT/rocprof_stats.err"
 f=$(ls /tmp/prof_stats/*/*kernel_stats.csv 2>/dev/null | head -1)
 echo "rocprofv3 --kernel-trace --stats over bench.py with 512 blocks in flight in the batched leg: $([ -n "$f" ] && [ -s "$OUT/bench_default_under_rocprofv3.json" ] && echo ok || echo FAILED)" > "$OUT/rocprof_stats_runs.txt"
 [ -n "$f" ] && cp "$f" "$OUT/bench_default_kernel_stats.csv"
@@ -124,7 +124,7 @@ ZKW_BATCH_LOG=2 timeout -s KILL 300 python tools/probe_blocks_builders_trace.py 
 # 8. the order of the legs: the full-block legs BEFORE the timed region against the default order, same box
 for ORD in default first; do
     if [ $ORD = first ]; then export ZKW_FULL_BLOCK_FIRST=1; else unset ZKW_FULL_BLOCK_FIRST; fi
-    timeout -s KILL 900 python bench.py --steps 10 --no-cpu-baseline --no-sensitivity --no-h2d --no-hash-circuits 2>/dev/null | python3 -c "
+    timeout -s KILL 900 python bench.py --full --steps 10 --no-cpu-baseline --no-sensitivity --no-h2d --no-hash-circuits 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('full-block legs $ORD: value %.0f circuits/s, %.0f ms per step, full_block.batched %.1f blocks/s' % (d['value'], d['ms_per_step'], d['full_block']['batched']['blocks_per_s']))"
