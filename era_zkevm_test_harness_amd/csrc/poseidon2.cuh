@@ -427,8 +427,9 @@ __device__ __forceinline__ u64 coop_flattened(const Coop& co, u64 x, u32 g, Put&
 // Lane j of the quad holds elements {j, 4+j, 8+j} (column j of the three 4-element blocks), 16 states per
 // wave. The 4x4 block products cross lanes with quad_perm DPP only; the sum over blocks and most of the
 // internal layer stay inside the lane, and the three elements of a lane give the in-order wave three
-// independent S-box chains to interleave. ~8.1k instructions per permutation step for 16 states, against
-// ~5.9k for 4 states in the row-of-16 form above.
+// independent S-box chains to interleave. Both linear layers work on the 32-bit word planes of the state, as the lane form's do
+// (mad_acc / wp_reduce above), and the partial rounds are unrolled with their constants in the instruction stream: ~5.1k VALU
+// instructions per permutation step for 16 states (319 per permutation, tests/test_chain_q4_isa.py; 383 with the Wide layers).
 #if defined(P2_Q4_PARTIAL_SCHED)
 #define Q4_PARTIAL_MUL gl::mul_sched
 #else
@@ -439,10 +440,21 @@ __device__ __forceinline__ u64 coop_flattened(const Coop& co, u64 x, u32 g, Put&
 #else
 #define Q4_FULL_POW7 gl::pow7_lat
 #endif
+// a quad_perm DPP move whose every lane reads an active lane of its own quad (Coop4 runs on full waves): bound_ctrl set, so the
+// compiler needs no "old" value in the destination (dpp32 above costs a zeroing v_mov per move)
+template <int CTRL>
+__device__ __forceinline__ u32 qdpp32(u32 v) {
+    return (u32)__builtin_amdgcn_update_dpp((int)0, (int)v, CTRL, 0xF, 0xF, true);
+}
+template <int CTRL>
+__device__ __forceinline__ u64 qdpp64(u64 v) {
+    return ((u64)qdpp32<CTRL>((u32)(v >> 32)) << 32) | qdpp32<CTRL>((u32)v);
+}
+
 struct Coop4 {
     u64 rc_full[2 * P2_HALF_FULL_ROUNDS][3];
     u32 ka, kb, kd;
-    u32 shift[3];
+    u32 pw[3];   // 2^shift of elements j, 4 + j, 8 + j (internal diagonal)
     bool first;  // lane 0 of the quad: owns element 0
     bool second; // lane 1: lane 0's helper in the partial rounds' S-box
 
@@ -460,75 +472,128 @@ struct Coop4 {
         kb = even ? 7u : 1u;
         kd = even ? 3u : 4u;
 #pragma unroll
-        for (int c = 0; c < 3; c++) shift[c] = c_shift[4 * c + j];
+        for (int c = 0; c < 3; c++) pw[c] = 1u << c_shift[4 * c + j];
     }
 
-    __device__ __forceinline__ Wide m4_row(u64 x) const {
-        u64 a = x, b = dpp64<QP_ROT1>(x), c = dpp64<QP_ROT2>(x), d = dpp64<QP_ROT3>(x);
-        u64 L = (a & gl::EPS) * ka + (b & gl::EPS) * kb + (c & gl::EPS) + (d & gl::EPS) * kd;
-        u64 H = (a >> 32) * ka + (b >> 32) * kb + (c >> 32) + (d >> 32) * kd;
-        Wide t;
-        t.lo = L + (H << 32);
-        t.hi = (u32)(H >> 32) + (t.lo < L ? 1u : 0u);
-        return t;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // a * k + acc for a per-lane k (a VGPR); no overflow by construction
+    static __device__ __forceinline__ u64 mad_v(u32 a, u32 k, u64 acc) {
+        u64 r, dead;
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(dead) : "v"(a), "v"(k), "v"(acc));
+        return r;
+    }
+    // x + c for a CANONICAL c (a round constant): one wrap at most, and after a wrap the sum is below c < p, so one "+ EPS" that cannot
+    // wrap again. The carries stay in VCC, read only implicitly (VOP2): EPS or 0 is a register minus itself minus the carry, added by
+    // the multiplier. Four instructions, no 64-bit compare and no SGPR carry read by a VOP3 (which needs wait states on gfx950).
+    // c0 may be an SGPR (a partial round's literal): VOP2 takes one scalar operand besides the implicit VCC, in src0 of the first add.
+    template <bool SC = false>  // SC: c0 in an SGPR
+    static __device__ __forceinline__ u64 add_rc(u64 x, u32 c0, u32 c1);
+#endif
+
+    // the M4 row of this lane (ka a + kb b + c + kd d, b / c / d the words of lanes j + 1 / 2 / 3) on one 32-bit word plane: < 16 * 2^32
+    __device__ __forceinline__ u64 m4_plane(u32 a) const {
+        const u32 b = qdpp32<QP_ROT1>(a), c = qdpp32<QP_ROT2>(a), d = qdpp32<QP_ROT3>(a);
+#if defined(__HIP_DEVICE_COMPILE__)
+        return mad_v(d, kd, mad_v(b, kb, mad_v(a, ka, (u64)c)));
+#else
+        return (u64)a * ka + (u64)b * kb + c + (u64)d * kd;
+#endif
     }
 
+    // external layer on word planes (as p2::external): the three blocks' rows per plane, the column sum over the blocks stays in the
+    // lane, row + column < 64 * 2^32 per plane, one wp_reduce per output
     __device__ __forceinline__ void external(u64 x[3]) const {
-        Wide t0 = m4_row(x[0]), t1 = m4_row(x[1]), t2 = m4_row(x[2]);
-        Wide col = wadd(wadd(t0, t1), t2);
-        x[0] = wreduce(wadd(t0, col));
-        x[1] = wreduce(wadd(t1, col));
-        x[2] = wreduce(wadd(t2, col));
+#if defined(__HIP_DEVICE_COMPILE__)
+        u64 L[3], H[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) { L[c] = m4_plane((u32)x[c]); H[c] = m4_plane((u32)(x[c] >> 32)); }
+        const u64 cl = L[0] + L[1] + L[2], ch = H[0] + H[1] + H[2];
+#pragma unroll
+        for (int c = 0; c < 3; c++) x[c] = wp_reduce(L[c] + cl, H[c] + ch);
+#endif
     }
 
+    // internal layer y = x * 2^shift + sum of the state, on word planes: the lane's three words per plane (< 3 * 2^32), summed over the
+    // quad by two DPP butterfly steps whose adds take the DPP operand themselves (carries in VCC, read implicitly), then
+    // word * 2^shift + plane sum (< 2^46 + 2^36) and one wp_reduce per element
     __device__ __forceinline__ void internal(u64 x[3]) const {
-        Wide s;
-        s.lo = x[0]; s.hi = 0;
-        Wide s1; s1.lo = x[1]; s1.hi = 0;
-        Wide s2; s2.lo = x[2]; s2.hi = 0;
-        s = wadd(wadd(s, s1), s2);
-        s = wadd(s, wdpp<QP_ROT2>(s));
-        s = wadd(s, wdpp<QP_SWAP1>(s));
+#if defined(__HIP_DEVICE_COMPILE__)
+        const u64 pl = mad_acc1((u32)x[0], mad_acc1((u32)x[1], (u64)(u32)x[2]));
+        const u64 ph = mad_acc1((u32)(x[0] >> 32), mad_acc1((u32)(x[1] >> 32), x[2] >> 32));
+        u32 l0, l1, h0, h1;
+        // A DPP read needs two wait states after the VALU write of its source: s_nop 1 before the first step (the inputs were just
+        // written); inside, three instructions separate a register's write from its next DPP read.
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_add_co_u32_dpp %0, vcc, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_addc_co_u32_dpp %1, vcc, %5, %5, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_co_u32_dpp %2, vcc, %6, %6 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_addc_co_u32_dpp %3, vcc, %7, %7, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_co_u32_dpp %0, vcc, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_addc_co_u32_dpp %1, vcc, %1, %1, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_co_u32_dpp %2, vcc, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_addc_co_u32_dpp %3, vcc, %3, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+            : "=&v"(l0), "=&v"(l1), "=&v"(h0), "=&v"(h1)
+            : "v"((u32)pl), "v"((u32)(pl >> 32)), "v"((u32)ph), "v"((u32)(ph >> 32))
+            : "vcc");
+        const u64 sl = ((u64)l1 << 32) | l0, sh = ((u64)h1 << 32) | h0;  // < 12 * 2^32
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            Wide m;
-            m.lo = x[c] << shift[c];
-            m.hi = (u32)((x[c] >> 1) >> (63 - shift[c]));
-            x[c] = wreduce(wadd(m, s));
-        }
+        for (int c = 0; c < 3; c++) x[c] = wp_reduce(mad_v((u32)x[c], pw[c], sl), mad_v((u32)(x[c] >> 32), pw[c], sh));
+#endif
     }
 
     // weak in / weak out
     __device__ __forceinline__ void permute(u64 x[3]) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        constexpr u64 RC[P2_TOTAL_ROUNDS * P2_WIDTH] = P2_ROUND_CONSTANTS_INIT;
         external(x);
 #pragma unroll
         for (int k = 0; k < P2_HALF_FULL_ROUNDS; k++) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) x[c] = Q4_FULL_POW7(gl::add_canon(x[c], rc_full[k][c]));
+            for (int c = 0; c < 3; c++) x[c] = Q4_FULL_POW7(add_rc(x[c], (u32)rc_full[k][c], (u32)(rc_full[k][c] >> 32)));
             external(x);
         }
+        // unrolled: the partial rounds' constants are literals of the instruction stream (no scalar load inside the permutation)
+#pragma unroll
         for (int k = 0; k < P2_PARTIAL_ROUNDS; k++) {
-            u64 rc = c_rc[12 * (P2_HALF_FULL_ROUNDS + k)];
-            // (the hand-scheduled multiplication of the row form was tried here, where a lane has ONE dependent S-box: the
-            // chain kernel got 4 % slower, 891 against 932 M permutations/s — with ~2 waves per SIMD the other wave fills
-            // the gaps the compiler's schedule leaves, and the opaque asm blocks only cost)
+            constexpr int R0 = 12 * P2_HALF_FULL_ROUNDS;
+            const u64 rc = RC[R0 + 12 * k];
             // the round's one S-box on two lanes of the quad, as in the row form (Coop::pow7_pair): lane 0 goes on to the cube while
-            // lane 1 squares again — three multiplications per partial round instead of four for the whole wave
-            const u64 t0 = dpp64<QP_BCAST0>(gl::add_canon(x[0], rc));
+            // lane 1 squares again — three multiplications per partial round instead of four for the whole wave. Only lane 0's sum
+            // x[0] + rc is broadcast.
+            const u64 t0 = qdpp64<QP_BCAST0>(add_rc<true>(x[0], (u32)rc, (u32)(rc >> 32)));
             const u64 x2 = Q4_PARTIAL_MUL(t0, t0);
             const u64 y = Q4_PARTIAL_MUL(x2, second ? x2 : t0);
-            const u64 sx = Q4_PARTIAL_MUL(y, dpp64<QP_SWAP1>(y));
+            const u64 sx = Q4_PARTIAL_MUL(y, qdpp64<QP_SWAP1>(y));
             x[0] = first ? sx : x[0];
             internal(x);
         }
 #pragma unroll
         for (int k = 0; k < P2_HALF_FULL_ROUNDS; k++) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) x[c] = Q4_FULL_POW7(gl::add_canon(x[c], rc_full[P2_HALF_FULL_ROUNDS + k][c]));
+            for (int c = 0; c < 3; c++)
+                x[c] = Q4_FULL_POW7(add_rc(x[c], (u32)rc_full[P2_HALF_FULL_ROUNDS + k][c], (u32)(rc_full[P2_HALF_FULL_ROUNDS + k][c] >> 32)));
             external(x);
         }
+#endif
     }
 };
+#if defined(__HIP_DEVICE_COMPILE__)
+#define P2_Q4_ADD_RC(C0)                                                             \
+    asm("v_add_co_u32 %0, vcc, %3, %5\n\t"                                          \
+        "v_addc_co_u32 %1, vcc, %4, %6, vcc\n\t"                                    \
+        "v_subb_co_u32 %2, vcc, %0, %0, vcc" /* -carry: EPS after a wrap */          \
+        : "=&v"(r0), "=&v"(r1), "=&v"(m)                                              \
+        : C0(c0), "v"(c1), "v"((u32)x), "v"((u32)(x >> 32))                           \
+        : "vcc")
+template <bool SC>
+__device__ __forceinline__ u64 Coop4::add_rc(u64 x, u32 c0, u32 c1) {
+    u32 r0, r1, m;
+    if constexpr (SC) P2_Q4_ADD_RC("s"); else P2_Q4_ADD_RC("v");
+    return mad_acc1(m, ((u64)r1 << 32) | r0);
+}
+#undef P2_Q4_ADD_RC
+#endif
 
 // ---------------------------------------------------------------- one state per PAIR of lanes: 32 states per wave
 // Lane j (0 / 1) of a pair holds elements 4c + 2j, 4c + 2j + 1 of the three 4-blocks (x[2c], x[2c + 1]). M4 is symmetric under
