@@ -68,6 +68,17 @@ __device__ inline void sap_leaf_hash(u64 index, const u32 value_limbs[8], u32 ou
     for (int k = 10; k < 16; k++) m[k] = 0;
     blake2s_one_block(m, 40, out);
 }
+// the same with the value as the tree stores it: its 32 bytes as 8 little-endian words (storage_tree_kernels.cuh)
+__device__ inline void sap_leaf_hash_bytes(u64 index, const u32 value_words[8], u32 out[8]) {
+    u32 m[16];
+    m[0] = bswap32((u32)(index >> 32));
+    m[1] = bswap32((u32)index);
+#pragma unroll
+    for (int k = 0; k < 8; k++) m[2 + k] = value_words[k];
+#pragma unroll
+    for (int k = 10; k < 16; k++) m[k] = 0;
+    blake2s_one_block(m, 40, out);
+}
 
 __device__ inline void sap_node_hash(const u32 l[8], const u32 r[8], u32 out[8]) {
     u32 m[16];
@@ -102,17 +113,20 @@ struct SapJob {
 };
 
 // derive_final_address: Blake2s-256(0^12 || address BE (20) || key BE (32))
-static __device__ __forceinline__ void k_sap_keys(const VB& vb, SapJob job) {
-    const u64 i = (u64)vb.x * blockDim.x + threadIdx.x;
-    if (i >= job.n) return;
-    const zkw_log_query* q = job.queries + i;
-    u32 m[16], k[8];
+__device__ inline void sap_derive_key(const zkw_log_query* q, u32 k[8]) {
+    u32 m[16];
     m[0] = m[1] = m[2] = 0;
 #pragma unroll
     for (int j = 0; j < 5; j++) m[3 + j] = bswap32(q->address[4 - j]);
 #pragma unroll
     for (int j = 0; j < 8; j++) m[8 + j] = bswap32(q->key[7 - j]);
     blake2s_one_block(m, 64, k);
+}
+static __device__ __forceinline__ void k_sap_keys(const VB& vb, SapJob job) {
+    const u64 i = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (i >= job.n) return;
+    u32 k[8];
+    sap_derive_key(job.queries + i, k);
 #pragma unroll
     for (int j = 0; j < 8; j++) job.keys[8 * i + j] = k[j];
 }

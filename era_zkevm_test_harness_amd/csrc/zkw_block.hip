@@ -252,11 +252,26 @@ Status storage_branch(zkw_block* B, const zkw_block_inputs* in, const zkw_log_qu
         ST_ZKW(zkw_storage_sorter_build(B->ctx[C_STO], d_q, n, B->cap[T_STO], &B->sto));
         ST_ZKW(zkw_synchronize(B->ctx[C_STO]));
     }
-    if (!in->storage_tree) return Status();
+    if (!in->storage_tree && !in->storage_tree_device) return Status();
     Timed t(B, "storage_application");
     const size_t nr = zkw_storage_witness_num_results(B->sto);
     const zkw_log_query* d_rq = static_cast<const zkw_log_query*>(zkw_storage_witness_device_ptr(B->sto, ZKW_STO_RESULT_QUERIES));
     const uint64_t* d_rt = static_cast<const uint64_t*>(zkw_storage_witness_device_ptr(B->sto, ZKW_STO_RESULT_NEW_TAILS));
+    if (const zkw_storage_tree* tree = in->storage_tree_device) {  // the pre-block answers straight from the tree in HBM, on this branch's stream
+        uint64_t* d_idx = nullptr;
+        uint8_t* d_paths = nullptr;
+        uint8_t root[32];
+        if (nr) {
+            ST_TRY(B->alloc(&d_idx, nr));
+            ST_TRY(B->alloc(&d_paths, nr * 256 * 32));
+            ST_ZKW(zkw_storage_tree_answer_queries(tree, B->ctx[C_STO], d_rq, nr, d_idx, d_paths));
+        }
+        ST_ZKW(zkw_storage_tree_root(tree, root));
+        ST_ZKW(zkw_storage_application_build(B->ctx[C_STO], d_rq, d_rt, nr, d_idx, d_paths, root, zkw_storage_tree_next_enumeration_index(tree),
+                                             B->cap[T_SAP], &B->sap));
+        ST_ZKW(zkw_synchronize(B->ctx[C_STO]));
+        return Status();
+    }
     std::vector<zkw_log_query> hq(nr);
     std::vector<uint64_t> idx(nr);
     std::vector<uint8_t> paths(nr * 256 * 32);
@@ -620,8 +635,24 @@ static bool inputs_valid(const zkw_block_inputs* in) {
     return true;
 }
 
+// the device-resident storage tree of a block's inputs: instead of the callback, and on the block's device
+static bool tree_valid(int device_id, const zkw_block_inputs* in) {
+    if (!in->storage_tree_device) return true;
+    if (in->storage_tree) {
+        g_block_error = "zkw_block_inputs: storage_tree (the host callback) and storage_tree_device are both set; a block takes one of them";
+        return false;
+    }
+    if (zkw_storage_tree_device(in->storage_tree_device) != device_id) {
+        g_block_error = "zkw_block_inputs: storage_tree_device lives on device " + std::to_string(zkw_storage_tree_device(in->storage_tree_device)) +
+                        ", the block runs on device " + std::to_string(device_id);
+        return false;
+    }
+    return true;
+}
+
 extern "C" int zkw_block_run(int device_id, const zkw_block_inputs* in, zkw_block** out) {
     if (!out || !inputs_valid(in)) return ZKW_ERR_INVALID;
+    if (!tree_valid(device_id, in)) return ZKW_ERR_INVALID;
     zkw_block* B = new zkw_block();
     B->device = device_id;
     B->t0 = Clock::now();
@@ -667,7 +698,7 @@ extern "C" int zkw_blocks_run(int device_id, const zkw_block_inputs* const* inpu
     if (!inputs || !out || n_blocks == 0) return ZKW_ERR_INVALID;
     for (size_t k = 0; k < n_blocks; k++) {
         const zkw_block_inputs* in = inputs[k];
-        if (!inputs_valid(in)) return ZKW_ERR_INVALID;
+        if (!inputs_valid(in) || !tree_valid(device_id, in)) return ZKW_ERR_INVALID;
         out[k] = nullptr;
     }
     static const bool threads = [] { const char* e = getenv("ZKW_BLOCKS_THREADS"); return e && e[0] == '1'; }();
@@ -769,7 +800,7 @@ extern "C" int zkw_blocks_run_sharded(int device_id, const zkw_block_inputs* con
     std::vector<size_t> where;
     for (size_t k = 0; k < n_blocks; k++) {
         out[k] = nullptr;
-        if (!inputs_valid(inputs[k])) return ZKW_ERR_INVALID;  // every rank checks every block: all ranks fail or none
+        if (!inputs_valid(inputs[k]) || !tree_valid(device_id, inputs[k])) return ZKW_ERR_INVALID;  // every rank checks every block: all ranks fail or none
         if (zkw_blocks_owner(k, world) == rank) { mine.push_back(inputs[k]); where.push_back(k); }
     }
     if (mine.empty()) return ZKW_OK;
@@ -826,6 +857,19 @@ extern "C" void zkw_blocks_free(zkw_block* const* blocks, size_t n_blocks) {
             }
         });
     for (auto& t : pool) t.join();
+}
+
+extern "C" int zkw_block_apply_storage(const zkw_block* B, zkw_storage_tree* tree) {
+    if (!B || !tree || !B->sto) return ZKW_ERR_INVALID;
+    if (zkw_storage_tree_device(tree) != B->device) {
+        g_block_error = "zkw_block_apply_storage: the tree and the block live on different devices";
+        return ZKW_ERR_INVALID;
+    }
+    if (hipSetDevice(B->device) != hipSuccess) return ZKW_ERR_HIP;
+    const int rc = zkw_storage_tree_apply_queries_device(tree, static_cast<const zkw_log_query*>(zkw_storage_witness_device_ptr(B->sto, ZKW_STO_RESULT_QUERIES)),
+                                                         zkw_storage_witness_num_results(B->sto));
+    if (rc != ZKW_OK) g_block_error = zkw_last_error();
+    return rc;
 }
 
 extern "C" void* zkw_block_witness(const zkw_block* B, uint8_t t) {

@@ -22,3 +22,9 @@ size_t zkw_ctx_scratch_bytes(const zkw_ctx* ctx);
 void zkw_cache_stats(size_t* live_bytes, size_t* idle_bytes);
 void zkw_ctx_scratch_mark(const zkw_ctx* ctx, std::vector<std::string>* names);
 void zkw_ctx_scratch_release_since(zkw_ctx* ctx, const std::vector<std::string>& names);
+// the device-resident storage tree (zkw_storage_tree.hip) as the block sequencer needs it: its device, and zkw_storage_tree_apply_queries over
+// queries that are in DEVICE memory whatever the tree's context says (a block's own deduplicated queue)
+struct zkw_storage_tree;
+struct zkw_log_query;
+int zkw_storage_tree_device(const zkw_storage_tree* t);
+int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_query* d_queries, size_t n);

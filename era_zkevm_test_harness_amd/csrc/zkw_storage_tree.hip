@@ -1,0 +1,244 @@
+// zkw_storage_tree.hip — zkw_storage_tree behind include/zkw.h: the reference's `tree: impl BinarySparseStorageTree`
+// (src/external_calls.rs:81, src/witness/tree/mod.rs:42-99) as a structure of the library, resident in HBM. Kernels and the layout:
+// storage_tree_kernels.cuh. Every call that changes the tree ends with the new root on the host (one small readback), so a call that
+// only reads — zkw_storage_tree_answer_queries from the storage branch of any number of blocks — needs no ordering with the tree's stream.
+#include "zkw_ctx.h"
+#include "storage_tree_kernels.cuh"
+#include "radix_sort.cuh"
+#include "scan_kernels.cuh"
+
+struct zkw_storage_tree {
+    zkw_ctx* ctx = nullptr;
+    size_t cap = 0, n = 0;
+    u64 next_index = 1;
+    // leaves, double buffered: an insert writes the merged leaves to the other side and flips
+    u32* keys[2] = {nullptr, nullptr};
+    u64* index[2] = {nullptr, nullptr};
+    u32* values[2] = {nullptr, nullptr};
+    int cur = 0;
+    u32 *nodes = nullptr, *empty = nullptr, *d = nullptr, *nxt = nullptr, *root_dev = nullptr;
+    uint8_t root[32] = {}, empty_root[32] = {};
+    void release() {
+        void* ptrs[] = {keys[0], keys[1], index[0], index[1], values[0], values[1], nodes, empty, d, nxt, root_dev};
+        for (void* p : ptrs)
+            if (p) dev_free(p);
+    }
+    StView view() const { return StView{keys[cur], index[cur], values[cur], nodes, empty, (u64)n, (u64)cap}; }
+};
+
+// bytes of HBM per leaf of capacity: the nodes (256 x 32), two sides of key / index / value (2 x 72), d and nxt (2 x 4)
+static constexpr size_t ST_BYTES_PER_LEAF = 256 * 32 + 2 * (32 + 8 + 32) + 8;
+
+extern "C" size_t zkw_storage_tree_bytes_per_leaf(void) { return ST_BYTES_PER_LEAF; }
+
+extern "C" int zkw_storage_tree_create(zkw_ctx* ctx, size_t capacity_leaves, zkw_storage_tree** out) {
+    if (!ctx || !out || capacity_leaves == 0) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create: bad argument");
+    if (capacity_leaves >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create: at most 2^31 - 1 leaves");
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create: the context belongs to a batch of blocks");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    zkw_storage_tree* t = new zkw_storage_tree();
+    t->ctx = ctx;
+    t->cap = capacity_leaves;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
+    for (int s = 0; s < 2; s++) {
+        alloc(&t->keys[s], t->cap * 32);
+        alloc(&t->index[s], t->cap * 8);
+        alloc(&t->values[s], t->cap * 32);
+    }
+    alloc(&t->nodes, t->cap * (size_t)ST_DEPTH * 32);
+    alloc(&t->empty, (ST_DEPTH + 1) * 32);
+    alloc(&t->d, t->cap * 4);
+    alloc(&t->nxt, t->cap * 4);
+    alloc(&t->root_dev, 32);
+    auto bail = [&](int rc) { t->release(); delete t; return rc; };
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(ZKW_ERR_OOM, "zkw_storage_tree_create: %zu leaves need %zu bytes of device memory: %s", capacity_leaves,
+                         capacity_leaves * ST_BYTES_PER_LEAF, hipGetErrorString(e)));
+    }
+    int rc = [&]() -> int {
+        { Prof _p(ctx, "k_st_empty"); ZKW_LAUNCH(ctx, k_st_empty, 1, 64, t->empty); }
+        ZKW_TRY(launch_check("k_st_empty"));
+        return ctx->read_small(t->empty_root, t->empty + 8 * ST_DEPTH, 32);
+    }();
+    if (rc != ZKW_OK) return bail(rc);
+    memcpy(t->root, t->empty_root, 32);
+    ctx_retain(ctx);
+    *out = t;
+    return ZKW_OK;
+}
+
+extern "C" void zkw_storage_tree_free(zkw_storage_tree* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->ctx->device);
+    (void)t->ctx->sync_stream();
+    t->release();
+    zkw_ctx* owner = t->ctx;
+    delete t;
+    ctx_release(owner);
+}
+
+extern "C" int zkw_storage_tree_root(const zkw_storage_tree* t, uint8_t out[32]) {
+    if (!t || !out) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_root: null argument");
+    memcpy(out, t->root, 32);
+    return ZKW_OK;
+}
+extern "C" uint64_t zkw_storage_tree_next_enumeration_index(const zkw_storage_tree* t) { return t ? t->next_index : 0; }
+extern "C" int zkw_storage_tree_set_next_enumeration_index(zkw_storage_tree* t, uint64_t next) {
+    if (!t || next == 0) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_set_next_enumeration_index: bad argument (index 0 is the empty leaf's)");
+    t->next_index = next;
+    return ZKW_OK;
+}
+extern "C" size_t zkw_storage_tree_num_leaves(const zkw_storage_tree* t) { return t ? t->n : 0; }
+extern "C" size_t zkw_storage_tree_capacity(const zkw_storage_tree* t) { return t ? t->cap : 0; }
+int zkw_storage_tree_device(const zkw_storage_tree* t) { return t ? t->ctx->device : -1; }
+
+// every height over the leaves of side `cur`, then the root to the host
+static int st_rebuild(zkw_storage_tree* t) {
+    zkw_ctx* ctx = t->ctx;
+    if (t->n == 0) {
+        memcpy(t->root, t->empty_root, 32);
+        return ZKW_OK;
+    }
+    StBuild b{t->keys[t->cur], t->index[t->cur], t->values[t->cur], t->nodes, t->empty, t->d, t->nxt, t->root_dev, (u64)t->n, (u64)t->cap};
+    const unsigned g64 = blocks_for(t->n, 64);
+    { Prof _p(ctx, "k_st_leaves"); ZKW_LAUNCH(ctx, k_st_leaves, g64, 64, b); }
+    ZKW_TRY(launch_check("k_st_leaves"));
+    static_assert(ZKW_STORAGE_TREE_DEPTH == ST_DEPTH, "the tree kernels walk 256 levels");
+    if (t->n <= ST_PERSISTENT_MAX) {
+        Prof _p(ctx, "k_st_levels");
+        ZKW_LAUNCH(ctx, k_st_levels, 1, ST_PERSISTENT_THREADS, b);
+    } else {
+        for (int L = 0; L < ST_DEPTH; L++) {
+            Prof _p(ctx, "k_st_level");
+            ZKW_LAUNCH(ctx, k_st_level, g64, 64, b, L);
+        }
+    }
+    ZKW_TRY(launch_check("k_st_level"));
+    return ctx->read_small(t->root, t->root_dev, 32);
+}
+
+// m pairs in device memory, inserted one after another in array order (insert_many_leafs, tree/mod.rs:65-81)
+static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d_values, size_t m) {
+    zkw_ctx* ctx = t->ctx;
+    if (m == 0) return ZKW_OK;
+    const size_t N = t->n + m;
+    if (N >= (1ull << 32) - 1) return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves and %zu pairs are more than one insert sorts", t->n, m);
+    u32 *perm0 = nullptr, *perm1 = nullptr, *new_first = nullptr, *new_rank = nullptr, *heads = nullptr;
+    u64 *k64a = nullptr, *k64b = nullptr;
+    void* tmp = nullptr;
+    const size_t tmp_bytes = radix_temp_bytes(N);
+    ZKW_TRY(ctx->scratch_t<u32>("st_perm0", N, &perm0));
+    ZKW_TRY(ctx->scratch_t<u32>("st_perm1", N, &perm1));
+    ZKW_TRY(ctx->scratch_t<u64>("st_k64a", N, &k64a));
+    ZKW_TRY(ctx->scratch_t<u64>("st_k64b", N, &k64b));
+    ZKW_TRY(ctx->scratch("st_sort_tmp", tmp_bytes + 256, &tmp));
+    ZKW_TRY(ctx->scratch_t<u32>("st_new_first", m, &new_first));
+    ZKW_TRY(ctx->scratch_t<u32>("st_new_rank", m + 1, &new_rank));
+    ZKW_TRY(ctx->scratch_t<u32>("st_heads", N + 1, &heads));
+    const int cur = t->cur, oth = cur ^ 1;
+    StMerge g{t->keys[cur], t->index[cur], t->values[cur], d_keys, d_values, (u64)t->n, (u64)m, t->next_index};
+    const unsigned grid = blocks_for(N, 256);
+    // the stable sort by key: four passes of 64 bits, least significant first
+    { Prof _p(ctx, "k_st_iota"); ZKW_LAUNCH(ctx, k_st_iota, grid, 256, perm0, (u64)N); }
+    ZKW_TRY(launch_check("k_st_iota"));
+    u32 *pc = perm0, *pn = perm1;
+    for (int w = 0; w < 4; w++) {
+        { Prof _p(ctx, "k_st_gather_word"); ZKW_LAUNCH(ctx, k_st_gather_word, grid, 256, g, (const u32*)pc, w, (u64)N, k64a); }
+        ZKW_TRY(launch_check("k_st_gather_word"));
+        { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, pc, pn, N, 64)); }
+        u32* x = pc; pc = pn; pn = x;
+    }
+    // which batch entries bring a new leaf, and their ranks in array order
+    { Prof _p(ctx, "k_st_mark"); ZKW_LAUNCH(ctx, k_st_mark, grid, 256, g, (const u32*)pc, (u64)N, new_first); }
+    ZKW_TRY(launch_check("k_st_mark"));
+    ZKW_TRY(flag_prefix(ctx, "k_st_new_rank", StArrayFlag{new_first}, m, new_rank));
+    u32 n_new = 0;
+    ZKW_TRY(ctx->read_small(&n_new, new_rank + m, sizeof n_new));
+    if (t->n + n_new > t->cap)  // nothing of the tree has been written yet
+        return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves + %u new ones exceed the capacity of %zu", t->n, n_new, t->cap);
+    ZKW_TRY(flag_prefix(ctx, "k_st_heads", StHeadFlag{g, pc}, N, heads));
+    { Prof _p(ctx, "k_st_emit"); ZKW_LAUNCH(ctx, k_st_emit, grid, 256, g, (const u32*)pc, (u64)N, (const u32*)heads, (const u32*)new_rank, t->keys[oth], t->index[oth], t->values[oth]); }
+    ZKW_TRY(launch_check("k_st_emit"));
+    t->cur = oth;
+    t->n += n_new;
+    t->next_index += n_new;
+    return st_rebuild(t);
+}
+
+extern "C" int zkw_storage_tree_insert(zkw_storage_tree* t, const uint8_t* keys, const uint8_t* values, size_t n) {
+    if (!t || (n && (!keys || !values))) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_insert: null argument");
+    zkw_ctx* ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_k = nullptr, *d_v = nullptr;
+    ZKW_TRY(ctx->in("st_in_keys", keys, n * 32, &d_k));
+    ZKW_TRY(ctx->in("st_in_values", values, n * 32, &d_v));
+    return st_insert_device(t, reinterpret_cast<const u32*>(d_k), reinterpret_cast<const u32*>(d_v), n);
+}
+
+static int st_query(zkw_ctx* ctx, const zkw_storage_tree* t, const StQuery& q, size_t n) {
+    { Prof _p(ctx, "k_st_query"); ZKW_LAUNCH(ctx, k_st_query, n, ST_DEPTH, t->view(), q); }
+    return launch_check("k_st_query");
+}
+
+extern "C" int zkw_storage_tree_get_leaves(const zkw_storage_tree* t, const uint8_t* keys, size_t n, uint64_t* leaf_indexes, uint8_t* values,
+                                           uint8_t* merkle_paths) {
+    if (!t || (n && !keys)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_get_leaves: null argument");
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_get_leaves: too many keys");
+    zkw_ctx* ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return ZKW_OK;
+    const uint8_t* d_k = nullptr;
+    ZKW_TRY(ctx->in("st_q_keys", keys, n * 32, &d_k));
+    u64* d_idx = nullptr;
+    uint8_t *d_val = nullptr, *d_paths = nullptr;
+    if (leaf_indexes) ZKW_TRY(ctx->out("st_q_idx", leaf_indexes, n, &d_idx));
+    if (values) ZKW_TRY(ctx->out("st_q_values", values, n * 32, &d_val));
+    if (merkle_paths) ZKW_TRY(ctx->out("st_q_paths", merkle_paths, n * ST_DEPTH * 32, &d_paths));
+    StQuery q{nullptr, reinterpret_cast<const u32*>(d_k), d_idx, reinterpret_cast<u32*>(d_val), reinterpret_cast<u32*>(d_paths)};
+    ZKW_TRY(st_query(ctx, t, q, n));
+    if (leaf_indexes) ZKW_TRY(ctx->finish_out(leaf_indexes, d_idx, n));
+    if (values) ZKW_TRY(ctx->finish_out(values, d_val, n * 32));
+    if (merkle_paths) ZKW_TRY(ctx->finish_out(merkle_paths, d_paths, n * ST_DEPTH * 32));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_storage_tree_answer_queries(const zkw_storage_tree* t, zkw_ctx* ctx, const zkw_log_query* queries, size_t n,
+                                               uint64_t* leaf_indexes, uint8_t* merkle_paths) {
+    if (!t || !ctx || (n && !queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: null argument");
+    if (ctx->device != t->ctx->device) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: the tree lives on device %d, the context on device %d", t->ctx->device, ctx->device);
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: too many queries");
+    if (n == 0) return ZKW_OK;
+    StQuery q{queries, nullptr, leaf_indexes, nullptr, reinterpret_cast<u32*>(merkle_paths)};
+    return st_query(ctx, t, q, n);
+}
+
+// queries in DEVICE memory (zkw_internal.h: zkw_block_apply_storage hands over the block's own deduplicated queue)
+int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_query* d_queries, size_t n) {
+    if (!t || (n && !d_queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: null argument");
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: too many queries");
+    zkw_ctx* ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return ZKW_OK;
+    u32 *rank = nullptr, *wk = nullptr, *wv = nullptr;
+    ZKW_TRY(ctx->scratch_t<u32>("st_ap_rank", n + 1, &rank));
+    ZKW_TRY(ctx->scratch_t<u32>("st_ap_keys", n * 8, &wk));
+    ZKW_TRY(ctx->scratch_t<u32>("st_ap_values", n * 8, &wv));
+    ZKW_TRY(flag_prefix(ctx, "k_st_write_rank", StWriteFlag{d_queries}, n, rank));
+    { Prof _p(ctx, "k_st_writes"); ZKW_LAUNCH(ctx, k_st_writes, blocks_for(n, 64), 64, d_queries, (u64)n, (const u32*)rank, wk, wv); }
+    ZKW_TRY(launch_check("k_st_writes"));
+    u32 m = 0;
+    ZKW_TRY(ctx->read_small(&m, rank + n, sizeof m));
+    return st_insert_device(t, wk, wv, m);
+}
+
+extern "C" int zkw_storage_tree_apply_queries(zkw_storage_tree* t, const zkw_log_query* queries, size_t n) {
+    if (!t || (n && !queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: null argument");
+    zkw_ctx* ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const zkw_log_query* d_q = nullptr;
+    ZKW_TRY(ctx->in("st_ap_queries", queries, n, &d_q));
+    return zkw_storage_tree_apply_queries_device(t, d_q, n);
+}

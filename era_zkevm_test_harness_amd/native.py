@@ -160,6 +160,19 @@ SYMBOLS = [
     ("zkw_storage_application_witness_device_ptr", _vp, [_vp, _int]),
     ("zkw_storage_application_witness_get", _int, [_vp, _int, _vp, _sz]),
     ("zkw_storage_application_witness_free", None, [_vp]),
+    ("zkw_storage_tree_create", _int, [_vp, _sz, C.POINTER(_vp)]),
+    ("zkw_storage_tree_free", None, [_vp]),
+    ("zkw_storage_tree_bytes_per_leaf", _sz, []),
+    ("zkw_storage_tree_root", _int, [_vp, _vp]),
+    ("zkw_storage_tree_next_enumeration_index", C.c_uint64, [_vp]),
+    ("zkw_storage_tree_set_next_enumeration_index", _int, [_vp, C.c_uint64]),
+    ("zkw_storage_tree_num_leaves", _sz, [_vp]),
+    ("zkw_storage_tree_capacity", _sz, [_vp]),
+    ("zkw_storage_tree_insert", _int, [_vp, _vp, _vp, _sz]),
+    ("zkw_storage_tree_get_leaves", _int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("zkw_storage_tree_answer_queries", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_storage_tree_apply_queries", _int, [_vp, _vp, _sz]),
+    ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
     ("zkw_precompile_build", _int, [_vp, _int, _vp, _vp, _sz, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -558,6 +571,115 @@ class StorageApplicationWitness:
         except Exception:
             pass
 
+
+
+class StorageTreeDevice:
+    """zkw_storage_tree: the reference's `tree: impl BinarySparseStorageTree` (src/witness/tree/mod.rs:42-99) resident in the HBM of
+    `ctx`'s device — depth 256, Blake2s-256, the conventions of synthetic.StorageTree. Keys and values are 32 bytes each: numpy
+    arrays [n, 32] of uint8 (or anything np.asarray makes one of, a list of `bytes` included) on a context in host pointer mode; torch
+    uint8 tensors on the context's device when it is in device pointer mode (Context.set_pointer_mode(PTR_DEVICE)) — results then
+    come back as tensors too. `capacity_leaves` bounds the tree: bytes_per_leaf() bytes of device memory each, allocated here."""
+
+    def __init__(self, ctx, capacity_leaves):
+        self.ctx = ctx
+        self.handle = C.c_void_p(None)
+        _check(load().zkw_storage_tree_create(ctx.handle, capacity_leaves, C.byref(self.handle)))
+
+    @staticmethod
+    def bytes_per_leaf():
+        return load().zkw_storage_tree_bytes_per_leaf()
+
+    @property
+    def root(self) -> bytes:
+        out = np.zeros(32, np.uint8)
+        _check(load().zkw_storage_tree_root(self.handle, _np_ptr(out)))
+        return out.tobytes()
+
+    @property
+    def next_enumeration_index(self) -> int:
+        return load().zkw_storage_tree_next_enumeration_index(self.handle)
+
+    @next_enumeration_index.setter
+    def next_enumeration_index(self, value):
+        _check(load().zkw_storage_tree_set_next_enumeration_index(self.handle, int(value)))
+
+    @property
+    def num_leaves(self) -> int:
+        return load().zkw_storage_tree_num_leaves(self.handle)
+
+    @property
+    def capacity(self) -> int:
+        return load().zkw_storage_tree_capacity(self.handle)
+
+    def _device_mode(self):
+        return self.ctx.pointer_mode == PTR_DEVICE
+
+    def _rows32(self, a):
+        """([n, 32] bytes as the library takes them, a pointer to them, n, what must stay alive)"""
+        if self._device_mode():
+            import torch
+
+            assert isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.uint8, "device pointer mode: a torch uint8 tensor on the device"
+            a = a.contiguous().reshape(-1, 32)
+            return C.c_void_p(a.data_ptr() if a.shape[0] else None), a.shape[0], a
+        if isinstance(a, (list, tuple)):
+            a = np.frombuffer(b"".join(bytes(x) for x in a), np.uint8)
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 32)
+        return (_np_ptr(a) if a.shape[0] else None), a.shape[0], a
+
+    def insert(self, keys, values):
+        """insert_many_leafs: the pairs one after another, in order"""
+        kp, n, _k = self._rows32(keys)
+        vp, nv, _v = self._rows32(values)
+        assert n == nv
+        _check(load().zkw_storage_tree_insert(self.handle, kp, vp, n))
+
+    def get_leaves(self, keys, paths=True):
+        """get_leaf of every key: (leaf_indexes [n] uint64, values [n, 32], merkle_paths [n, 256, 32] or None)"""
+        kp, n, _k = self._rows32(keys)
+        if self._device_mode():
+            import torch
+
+            dev = _k.device
+            idx = torch.zeros(n, dtype=torch.int64, device=dev)
+            val = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+            pth = torch.zeros((n, 256, 32), dtype=torch.uint8, device=dev) if paths else None
+            torch.cuda.synchronize(dev)  # the outputs are zeroed on torch's stream, filled on the context's
+            _check(load().zkw_storage_tree_get_leaves(self.handle, kp, n, C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()),
+                                                      C.c_void_p(pth.data_ptr()) if paths else None))
+            self.ctx.synchronize()
+            return idx, val, pth
+        idx = np.zeros(n, np.uint64)
+        val = np.zeros((n, 32), np.uint8)
+        pth = np.zeros((n, 256, 32), np.uint8) if paths else None
+        _check(load().zkw_storage_tree_get_leaves(self.handle, kp, n, _np_ptr(idx), _np_ptr(val), _np_ptr(pth) if paths else None))
+        return idx, val, pth
+
+    def answer_queries(self, ctx, queries_ptr, n, leaf_indexes_ptr, merkle_paths_ptr):
+        """zkw_storage_tree_answer_queries on `ctx`'s stream: DEVICE pointers (ints), nothing synchronised"""
+        _check(load().zkw_storage_tree_answer_queries(self.handle, ctx.handle, C.c_void_p(queries_ptr), n, C.c_void_p(leaf_indexes_ptr),
+                                                      C.c_void_p(merkle_paths_ptr)))
+
+    def apply_queries(self, queries):
+        """the writes of a block's deduplicated storage queue (LOG_QUERY records; a torch uint8 tensor of them in device pointer mode)"""
+        if self._device_mode():
+            q = queries.contiguous()
+            n = q.numel() // LOG_QUERY.itemsize
+            _check(load().zkw_storage_tree_apply_queries(self.handle, C.c_void_p(q.data_ptr() if n else None), n))
+            return
+        q = np.ascontiguousarray(queries, dtype=LOG_QUERY)
+        _check(load().zkw_storage_tree_apply_queries(self.handle, _np_ptr(q) if q.size else None, q.size))
+
+    def free(self):
+        if self.handle:
+            load().zkw_storage_tree_free(self.handle)
+            self.handle = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class PrecompileWitness:
@@ -1562,14 +1684,17 @@ class BlockInputs(C.Structure):
                 ("num_non_deterministic_heap_queries", C.c_uint32),
                 ("storage_tree", STORAGE_TREE_FN), ("storage_tree_user", C.c_void_p),
                 ("storage_initial_root", C.c_uint8 * 32), ("storage_initial_next_enumeration_index", C.c_uint64),
-                ("capacities", C.c_uint32 * 14), ("vm_tracer", C.c_void_p), ("queues_on_device", C.c_uint32)]
+                ("capacities", C.c_uint32 * 14), ("vm_tracer", C.c_void_p), ("queues_on_device", C.c_uint32),
+                ("storage_tree_device", C.c_void_p)]
 
 
 class Block:
     """zkw_block: every witness builder of one block scheduled as a dependency graph inside libzkw (csrc/zkw_block.hip).
     `block`: the dict of synthetic.block_after_vm (or the same arrays from a real VM run); `capacities`: circuit type ->
     capacity (default geometry_config.rs); `storage_tree`: callable(dedup_queries) -> (leaf_indexes, merkle_paths,
-    initial_root, next_enumeration_index is given separately) or None."""
+    initial_root, next_enumeration_index is given separately) or None; `storage_tree_device`: a StorageTreeDevice the block's
+    storage queries are answered from on the device instead (root and next enumeration index are the tree's) — the form
+    run_many / prepare_many / run_sharded take too, as one tree for all blocks or a list with a tree or None per block."""
 
     WITNESS_GETTERS = {2: "zkw_decommit_witness", 3: "zkw_decommitter_witness", 4: "zkw_demux_witness", 5: "zkw_precompile_witness",
                        6: "zkw_precompile_witness", 7: "zkw_precompile_witness", 8: "zkw_ram_witness", 9: "zkw_storage_witness",
@@ -1596,7 +1721,8 @@ class Block:
         return d
 
     def __init__(self, device_id, block, capacities=None, storage_tree=None, storage_initial_root=None,
-                 storage_next_enumeration_index=0, num_non_deterministic_heap_queries=0, vm_tracer=None, _run=True):
+                 storage_next_enumeration_index=0, num_non_deterministic_heap_queries=0, vm_tracer=None, _run=True,
+                 storage_tree_device=None):
         lib = load()
         inp = BlockInputs()
         keep = []
@@ -1653,6 +1779,9 @@ class Block:
             for i in range(32):
                 inp.storage_initial_root[i] = int(root[i])
             inp.storage_initial_next_enumeration_index = storage_next_enumeration_index
+        if storage_tree_device is not None:
+            keep.append(storage_tree_device)
+            inp.storage_tree_device = storage_tree_device.handle
         if vm_tracer is not None:  # the tracer's cycle-stamped vectors: MainVM instance records come back with the block
             t = dict(vm_tracer)
             t.setdefault("vm_memory_queries", np.ascontiguousarray(block["vm_memory_queries"], dtype=MEM_QUERY))  # ignored by the block (it uses its own memory queue / states)
@@ -1675,11 +1804,20 @@ class Block:
             raise ZkwError(rc, (lib.zkw_block_last_error() or b"").decode() or lib.zkw_last_error().decode())
 
     @staticmethod
-    def run_many(device_id, blocks, capacities=None):
+    def _trees_for(blocks, storage_tree_device):
+        """one tree for all blocks, or a list with a tree (or None) per block"""
+        if isinstance(storage_tree_device, (list, tuple)):
+            assert len(storage_tree_device) == len(blocks)
+            return list(storage_tree_device)
+        return [storage_tree_device] * len(blocks)
+
+    @staticmethod
+    def run_many(device_id, blocks, capacities=None, storage_tree_device=None):
         """zkw_blocks_run: the given blocks (dicts as for Block) in flight together, their queue chains merged into shared
         launches by the chain service. Returns the list of Block objects."""
         lib = load()
-        objs = [Block(device_id, b, capacities, _run=False) for b in blocks]
+        trees = Block._trees_for(blocks, storage_tree_device)
+        objs = [Block(device_id, b, capacities, _run=False, storage_tree_device=t) for b, t in zip(blocks, trees)]
         ptrs = (C.c_void_p * len(objs))(*[C.addressof(o._inp) for o in objs])
         outs = (C.c_void_p * len(objs))()
         rc = lib.zkw_blocks_run(device_id, ptrs, len(objs), outs)
@@ -1690,10 +1828,11 @@ class Block:
         return objs
 
     @staticmethod
-    def prepare_many(device_id, blocks, capacities=None):
+    def prepare_many(device_id, blocks, capacities=None, storage_tree_device=None):
         """The input structs of `blocks` built once (a service that receives its blocks as arrays does this as they arrive): the list
         run_prepared takes, any number of times."""
-        return [Block(device_id, b, capacities, _run=False) for b in blocks]
+        trees = Block._trees_for(blocks, storage_tree_device)
+        return [Block(device_id, b, capacities, _run=False, storage_tree_device=t) for b, t in zip(blocks, trees)]
 
     @staticmethod
     def run_prepared(device_id, templates):
@@ -1736,11 +1875,12 @@ class Block:
         return res
 
     @staticmethod
-    def run_sharded(device_id, blocks, rank, world, capacities=None):
+    def run_sharded(device_id, blocks, rank, world, capacities=None, storage_tree_device=None):
         """zkw_blocks_run_sharded: every rank passes the same list of blocks; rank r builds the blocks k with k % world == r.
         Returns a list with a Block for every owned index and None elsewhere."""
         lib = load()
-        objs = [Block(device_id, b, capacities, _run=False) for b in blocks]
+        trees = Block._trees_for(blocks, storage_tree_device)
+        objs = [Block(device_id, b, capacities, _run=False, storage_tree_device=t) for b, t in zip(blocks, trees)]
         ptrs = (C.c_void_p * len(objs))(*[C.addressof(o._inp) for o in objs])
         outs = (C.c_void_p * len(objs))()
         rc = lib.zkw_blocks_run_sharded(device_id, ptrs, len(objs), rank, world, outs)
@@ -1770,6 +1910,13 @@ class Block:
         if rank != root:
             return None
         return [out[k, 1:1 + 24 * int(out[k, 0])].reshape(-1, 24).copy() for k in range(n)]
+
+    def apply_storage(self, tree):
+        """zkw_block_apply_storage: the writes of this block's deduplicated storage queue into `tree` (a StorageTreeDevice), device to
+        device — the tree a following block starts from"""
+        rc = load().zkw_block_apply_storage(self.handle, tree.handle)
+        if rc != OK:
+            raise ZkwError(rc, (load().zkw_block_last_error() or b"").decode() or load().zkw_last_error().decode())
 
     def num_instances(self, circuit_type):
         return load().zkw_block_num_instances(self.handle, circuit_type)

@@ -570,6 +570,51 @@ const void *zkw_storage_application_witness_device_ptr(const zkw_storage_applica
 int zkw_storage_application_witness_get(const zkw_storage_application_witness *w, int what, void *dst, size_t dst_bytes);
 void zkw_storage_application_witness_free(zkw_storage_application_witness *w);
 
+/* ---- the storage tree, resident on the device ------------------------------------------------------------ */
+/* The reference's `tree: impl BinarySparseStorageTree` (src/external_calls.rs:81; trait src/witness/tree/mod.rs:42-99,
+   ZKSyncTestingTree = InMemoryStorageTree<256, 32, 8, Blake2s256, ZkSyncStorageLeaf> at :101-384) as a structure of this
+   library: depth 256, Blake2s-256; leaf hash = H(enumeration index as 8 big-endian bytes || 32-byte value), the empty leaf =
+   index 0 and a zero value, node = H(left || right); bit `level` of the key read as a little-endian 256-bit number picks the
+   side at `level`; a Merkle path's level 0 is the leaf's sibling; enumeration indices start at 1 and a key keeps the index
+   of its first insertion. Keys and values are 32 bytes each.
+   The tree lives in the HBM of ctx's device and works on ctx's stream: the leaves sorted by key, every non-empty node of
+   every height stored (csrc/storage_tree_kernels.cuh). capacity_leaves bounds it: zkw_storage_tree_bytes_per_leaf() =
+   8 344 bytes of device memory per leaf of CAPACITY, allocated by zkw_storage_tree_create (8 192 of them the nodes: what one
+   Merkle path of the leaf weighs), plus ~60 bytes of context scratch per leaf during an insert.
+   Array arguments follow ctx's pointer mode (host pointers, or device pointers after zkw_set_pointer_mode) except where
+   DEVICE is said; a root, an index and a count are always host values. Errors are return codes and leave the tree as it
+   was: more leaves than capacity_leaves -> ZKW_ERR_OOM; NULL / zero-capacity arguments -> ZKW_ERR_INVALID. A tree is used
+   by one caller at a time, but any number of readers — zkw_storage_tree_get_leaves, zkw_storage_tree_answer_queries, the
+   blocks of one zkw_blocks_run — may read it together. A call that changes the tree returns when the change is complete
+   (the new root is on the host). The tree keeps a reference to ctx (see "lifetimes" above). */
+typedef struct zkw_storage_tree zkw_storage_tree;
+int zkw_storage_tree_create(zkw_ctx *ctx, size_t capacity_leaves, zkw_storage_tree **out); /* empty(), tree/mod.rs:43 */
+void zkw_storage_tree_free(zkw_storage_tree *tree);
+size_t zkw_storage_tree_bytes_per_leaf(void);
+int zkw_storage_tree_root(const zkw_storage_tree *tree, uint8_t out[32]);                  /* root(); out: HOST */
+uint64_t zkw_storage_tree_next_enumeration_index(const zkw_storage_tree *tree);
+int zkw_storage_tree_set_next_enumeration_index(zkw_storage_tree *tree, uint64_t next_enumeration_index);
+size_t zkw_storage_tree_num_leaves(const zkw_storage_tree *tree);
+size_t zkw_storage_tree_capacity(const zkw_storage_tree *tree);
+/* insert_many_leafs (tree/mod.rs:65-81): the result of inserting the n pairs ONE AFTER ANOTHER in array order — a key that
+   repeats inside one call takes the last value and the enumeration index of its first occurrence; a key the tree holds
+   keeps its index. keys, values: [n][32]. Every height is rebuilt: the cost is that of the whole tree, whatever n. */
+int zkw_storage_tree_insert(zkw_storage_tree *tree, const uint8_t *keys, const uint8_t *values, size_t n);
+/* get_leaf (tree/mod.rs:219-240) of n keys in the CURRENT state, present or absent (absent: index 0, a zero value, the path
+   of the empty leaf at that key). leaf_indexes[n], values[n][32], merkle_paths[n][256][32]; any of the three may be NULL. */
+int zkw_storage_tree_get_leaves(const zkw_storage_tree *tree, const uint8_t *keys, size_t n, uint64_t *leaf_indexes,
+                                uint8_t *values, uint8_t *merkle_paths);
+/* The whole zkw_storage_tree_fn contract on the device: LogQuery::derive_final_address of each query, then get_leaf.
+   queries, leaf_indexes[n], merkle_paths[n][256][32] are DEVICE pointers (either output may be NULL). Enqueued on ctx's
+   stream — any context of the tree's device, in particular a block's storage context, also inside zkw_blocks_run — and
+   not synchronised. The tree is only read. */
+int zkw_storage_tree_answer_queries(const zkw_storage_tree *tree, zkw_ctx *ctx, const zkw_log_query *queries, size_t n,
+                                    uint64_t *leaf_indexes, uint8_t *merkle_paths);
+/* What the reference's walk leaves in the tree after a block (storage_application.rs:221-283): insert(derive_final_address(q),
+   q.written_value) for every query with rw_flag set, in order. queries = the deduplicated queue the builder saw
+   (ZKW_STO_RESULT_QUERIES). See zkw_block_apply_storage for a block's own queue. */
+int zkw_storage_tree_apply_queries(zkw_storage_tree *tree, const zkw_log_query *queries, size_t n);
+
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
 /* kind = ZKW_PRECOMPILE_KECCAK256: keccak256_decompose_into_per_circuit_witness,
@@ -1006,10 +1051,12 @@ int zkw_gather_records(zkw_comm *c, const uint32_t *owner, size_t n, const void 
    hashed ONCE, inside the RAM-permutation builder, and the decommitter / precompile builders take their slices of it.
    Results are identical to calling the builders one by one (tests/test_gpu_block.py). */
 typedef struct zkw_block zkw_block;
-/* the reference's `tree: impl BinarySparseStorageTree` (src/external_calls.rs:81): asked once, for the deduplicated
-   rollup storage queries of the block in their final order: leaf_indexes[n] (0 = empty leaf) and merkle_paths[n][256][32]
-   of the state BEFORE the block (see zkw_storage_application_build). Return 0 on success. Called on the thread that runs
-   the storage branch. */
+/* the reference's `tree: impl BinarySparseStorageTree` (src/external_calls.rs:81) as a host callback: asked once, for the
+   deduplicated rollup storage queries of the block in their final order: leaf_indexes[n] (0 = empty leaf) and
+   merkle_paths[n][256][32] of the state BEFORE the block (see zkw_storage_application_build). Return 0 on success. Called
+   on the thread that runs the storage branch; the queries travel to the host and 8 KB of path per query back. Supported
+   by zkw_block_run only. The alternative that never leaves the device, and the one zkw_blocks_run is tested with:
+   zkw_block_inputs.storage_tree_device, a zkw_storage_tree. */
 typedef int (*zkw_storage_tree_fn)(void *user, const zkw_log_query *dedup_queries, size_t n, uint64_t *leaf_indexes,
                                    uint8_t *merkle_paths);
 typedef struct zkw_block_inputs {
@@ -1042,6 +1089,12 @@ typedef struct zkw_block_inputs {
        (a VM that runs next to the library leaves them in HBM); they are read, never written, and must stay valid until the block is
        freed. The bytecodes and vm_tracer stay HOST pointers. 0 (the default): everything is host memory. */
     uint32_t queues_on_device;
+    /* optional (NULL = the callback above, or no StorageApplication instances): the tree the block's storage queries are answered from, on
+       the device — zkw_storage_tree_answer_queries on the storage branch's stream, no host code, no copies. It must live on the block's
+       device and storage_tree must be NULL (else ZKW_ERR_INVALID, zkw_block_last_error). storage_initial_root and
+       storage_initial_next_enumeration_index above are IGNORED: both are the tree's. The tree is only read — by any number of blocks of
+       one zkw_blocks_run / zkw_blocks_run_sharded — and must not change while a run is under way; zkw_block_apply_storage advances it. */
+    const zkw_storage_tree *storage_tree_device;
 } zkw_block_inputs;
 /* All pointers in `in` are HOST pointers (but see queues_on_device). Blocks until every builder has finished. */
 int zkw_block_run(int device_id, const zkw_block_inputs *in, zkw_block **out);
@@ -1068,6 +1121,9 @@ const char *zkw_block_last_error(void);
 void zkw_block_free(zkw_block *b);
 /* n_blocks blocks released on a few threads of the library (NULL entries are skipped); what zkw_block_free does for each. */
 void zkw_blocks_free(zkw_block *const *blocks, size_t n_blocks);
+/* For the host that chains blocks: zkw_storage_tree_apply_queries over the block's own deduplicated storage queue (device to
+   device) — after it `tree` is what the reference's tree is after the block: its root the last root of ZKW_SAP_ROOTS. */
+int zkw_block_apply_storage(const zkw_block *b, zkw_storage_tree *tree);
 /* witness of one circuit type, to be cast to its zkw_*_witness type (2 zkw_decommit_witness, 3 zkw_decommitter_witness,
    4 zkw_demux_witness, 5/6/7 zkw_precompile_witness, 8 zkw_ram_witness, 9 zkw_storage_witness, 10
    zkw_storage_application_witness, 11/12 zkw_events_witness); NULL for the others. The handles belong to the block and
@@ -1075,8 +1131,8 @@ void zkw_blocks_free(zkw_block *const *blocks, size_t n_blocks);
 void *zkw_block_witness(const zkw_block *b, uint8_t circuit_type);
 zkw_ctx *zkw_block_context(const zkw_block *b, uint8_t circuit_type);
 size_t zkw_block_num_instances(const zkw_block *b, uint8_t circuit_type);
-/* public inputs [n_instances][4] of every type but MainVM (1; its closed form needs the VM's local state; 10 only when the
-   storage tree answers were given), the RecursionRequest encodings
+/* public inputs [n_instances][4] of every type but MainVM (1; its closed form needs the VM's local state; 10 only when a
+   storage tree — callback or device tree — was given), the RecursionRequest encodings
    [n_instances][8] and the RecursionQueueSimulator states [n_instances][12] after each push (postprocessing/mod.rs:393-400).
    Host pointers valid until zkw_block_free; NULL when the type has none. */
 const uint64_t *zkw_block_public_inputs(const zkw_block *b, uint8_t circuit_type);
