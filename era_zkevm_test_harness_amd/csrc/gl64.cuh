@@ -187,8 +187,53 @@ __device__ __forceinline__ u64 mul_cyc(u64 a, u64 b) {
 }
 #endif
 
+#if defined(__HIPCC__)
+// a * b mod p for a LONE wave (the serial queue chains, one wave per SIMD: its instruction count is its time): mul_cyc's algebra with
+// mul_sched's carry discipline, 15 instructions. Every carry is consumed by the NEXT instruction as the implicit VCC of a VOP2
+// add / subtract-with-carry (no wait state; an SGPR pair read by a VOP3 costs a lone wave two) and is a VGPR value from there on:
+//   p = a0 b0, q = a0 b1, h = a1 b1, q += a1 b0 (carry cm, worth 2^96) and cm goes straight into h's high word (h1 <= 2^32 - 2);
+//   w1 = p1 + q0, w2 = h0 + q1 + c, w3 = h1 + c' are the exact product words (w3 cannot carry out: the product is below 2^128);
+//   x = w2 * (2^32 - 1) + (w1:w0) in one more v_mad_u64_u32: the product is (w1:w0) + w2 * 2^64 + w3 * 2^96 = (w1:w0) + w2 EPS - w3,
+//   and the carry c1 out of x is worth 2^64 = EPS; y = x - w3 with borrow b1, worth -EPS; result = y + (c1 - b1) EPS.
+// c1 - b1 is in {-1, 0, 1} and the last step cannot wrap: with c1 alone x = lo + w2 EPS - 2^64 <= 2^64 - 2^33, so y + EPS < 2^64; with
+// b1 alone x < w3 < 2^32, so y = x - w3 + 2^64 >= 2^64 - EPS and y - EPS > 0; both set cancel. The flags never meet as flags: -c1 is a
+// register minus itself minus VCC, n = b1 - c1 is that plus VCC after the borrow chain, and y - n EPS = y - n 2^32 + sext64(n) is a
+// 32-bit subtract from the high word and one v_mad_i64_i32 (n * 1 + y).
+// ONE asm statement: gfx950's compiler puts an s_nop between an asm statement and the next instruction that reads what it wrote (it
+// must assume a destination-forwarding hazard), so a product cut into five statements costs a lone wave five more issue slots. The
+// words of the 64-bit products are addressed as registers, which operands do not allow: the six temporaries are v[2:7] by name.
+// Weak in, weak out.
+__device__ __forceinline__ u64 mul_vcc(u64 a, u64 b) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    return 0;  // device-only
+#else
+    u64 r;
+    asm("v_mad_u64_u32 v[2:3], vcc, %1, %3, 0\n\t"         // p = a0 * b0 (the carries of the first three are dead)
+        "v_mad_u64_u32 v[4:5], vcc, %1, %4, 0\n\t"         // q = a0 * b1
+        "v_mad_u64_u32 v[6:7], vcc, %2, %4, 0\n\t"         // h = a1 * b1
+        "v_mad_u64_u32 v[4:5], vcc, %2, %3, v[4:5]\n\t"    // q += a1 * b0, carry out of 64 bits: cm
+        "v_addc_co_u32 v7, vcc, 0, v7, vcc\n\t"            // h1 += cm
+        "v_add_co_u32 v3, vcc, v3, v4\n\t"                 // w1 = p1 + q0
+        "v_addc_co_u32 v6, vcc, v6, v5, vcc\n\t"           // w2 = h0 + q1 + c
+        "v_addc_co_u32 v7, vcc, 0, v7, vcc\n\t"            // w3 = h1 + cm + c'
+        "v_mad_u64_u32 v[2:3], vcc, v6, -1, v[2:3]\n\t"    // x = w2 * EPS + (w1:w0), carry c1
+        "v_subb_co_u32 v4, vcc, v6, v6, vcc\n\t"           // -c1
+        "v_sub_co_u32 v2, vcc, v2, v7\n\t"                 // y = x - w3, borrow b1
+        "v_subbrev_co_u32 v3, vcc, 0, v3, vcc\n\t"
+        "v_addc_co_u32 v4, vcc, 0, v4, vcc\n\t"            // n = b1 - c1
+        "v_sub_u32 v3, v3, v4\n\t"                         // y - n * 2^32
+        "v_mad_i64_i32 %0, vcc, v4, 1, v[2:3]"             //   + sext64(n)
+        : "=v"(r)
+        : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32))
+        : "vcc", "v2", "v3", "v4", "v5", "v6", "v7");
+    return r;
+#endif
+}
+#endif
+
 // a * b mod p, the compiler-scheduled form: four chained v_mad_u64_u32 + reduce128, 21 instructions that the compiler interleaves with
-// whatever else the lane has to do. For LATENCY-bound code — the serial queue chains, one wave per SIMD (p2::Coop4 / Coop2): with the
+// whatever else the lane has to do. For LATENCY-bound code — the pair-form chains (p2::Coop2), the one-lane sponges, and the quad form
+// (p2::Coop4) before mul_vcc above, which GL_CHAIN_MUL_COMPILER_FORM brings back: with the
 // 14-instruction form below k_chain_full_q4 was 11 % slower (4.91 -> 5.45 s per step, profiles/r05/README.md), its carry chains through
 // SGPR pairs stall a lone wave. Weak in, weak out.
 GL_HD u64 mul_lat(u64 a, u64 b) {

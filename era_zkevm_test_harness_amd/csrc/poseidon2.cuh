@@ -248,9 +248,17 @@ __device__ __forceinline__ u64 add_rc_sched(u64 x, u64 c) {
         : "vcc");
     return ((u64)r1 << 32) | r0;
 }
+// The multiplication of the chain forms (Coop, Coop4), whose wave runs alone on its SIMD: gl::mul_vcc, the 15-instruction product with
+// its carries in VCC. GL_CHAIN_MUL_COMPILER_FORM restores the earlier products for A/B builds (row form: the 20-instruction mul_sched;
+// quad form: the compiler-scheduled mul_lat).
+#if defined(GL_CHAIN_MUL_COMPILER_FORM)
+#define P2_ROW_MUL gl::mul_sched
+#else
+#define P2_ROW_MUL gl::mul_vcc
+#endif
 __device__ __forceinline__ u64 pow7_sched(u64 x) {  // one dependent chain per wave: the hand-scheduled multiplication (gl64.cuh)
-    const u64 x2 = gl::mul_sched(x, x), x3 = gl::mul_sched(x2, x), x4 = gl::mul_sched(x2, x2);
-    return gl::mul_sched(x3, x4);
+    const u64 x2 = P2_ROW_MUL(x, x), x3 = P2_ROW_MUL(x2, x), x4 = P2_ROW_MUL(x2, x2);
+    return P2_ROW_MUL(x3, x4);
 }
 
 struct Coop {
@@ -389,10 +397,10 @@ struct Coop {
     // wave's time is its instruction count). Only lane 0's result means anything; the other lanes' is discarded by the caller.
     __device__ __forceinline__ u64 pow7_pair(u64 t) const {
         const u64 t0 = dpp64<QP_BCAST0>(t);            // lanes 0..3 of a quad: lane 0's element
-        const u64 x2 = gl::mul_sched(t0, t0);
+        const u64 x2 = P2_ROW_MUL(t0, t0);
         const u64 b = second ? x2 : t0;
-        const u64 y = gl::mul_sched(x2, b);            // lane 0: x^3, lane 1: x^4
-        return gl::mul_sched(y, dpp64<QP_SWAP1>(y));   // lane 0: x^3 * x^4
+        const u64 y = P2_ROW_MUL(x2, b);               // lane 0: x^3, lane 1: x^4
+        return P2_ROW_MUL(y, dpp64<QP_SWAP1>(y));      // lane 0: x^3 * x^4
     }
 };
 
@@ -428,17 +436,26 @@ __device__ __forceinline__ u64 coop_flattened(const Coop& co, u64 x, u32 g, Put&
 // wave. The 4x4 block products cross lanes with quad_perm DPP only; the sum over blocks and most of the
 // internal layer stay inside the lane, and the three elements of a lane give the in-order wave three
 // independent S-box chains to interleave. Both linear layers work on the 32-bit word planes of the state, as the lane form's do
-// (mad_acc / wp_reduce above), and the partial rounds are unrolled with their constants in the instruction stream: ~5.1k VALU
-// instructions per permutation step for 16 states (319 per permutation, tests/test_chain_q4_isa.py; 383 with the Wide layers).
+// (mad_acc / wp_reduce above), and the partial rounds are unrolled with their constants in the instruction stream: ~4.1k VALU
+// instructions per permutation step for 16 states (258 per permutation, tests/test_chain_sbox_isa.py; 319 with the S-boxes through
+// gl::mul_lat, 383 with the Wide layers as well).
+__device__ __forceinline__ u64 pow7_vcc(u64 x) {
+    const u64 x2 = gl::mul_vcc(x, x), x3 = gl::mul_vcc(x2, x), x4 = gl::mul_vcc(x2, x2);
+    return gl::mul_vcc(x3, x4);
+}
 #if defined(P2_Q4_PARTIAL_SCHED)
 #define Q4_PARTIAL_MUL gl::mul_sched
-#else
+#elif defined(GL_CHAIN_MUL_COMPILER_FORM)
 #define Q4_PARTIAL_MUL gl::mul_lat
+#else
+#define Q4_PARTIAL_MUL gl::mul_vcc
 #endif
 #if defined(P2_Q4_FULL_CYC)
 #define Q4_FULL_POW7 gl::pow7
-#else
+#elif defined(GL_CHAIN_MUL_COMPILER_FORM)
 #define Q4_FULL_POW7 gl::pow7_lat
+#else
+#define Q4_FULL_POW7 pow7_vcc
 #endif
 // a quad_perm DPP move whose every lane reads an active lane of its own quad (Coop4 runs on full waves): bound_ctrl set, so the
 // compiler needs no "old" value in the destination (dpp32 above costs a zeroing v_mov per move)
