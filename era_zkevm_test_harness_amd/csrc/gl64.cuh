@@ -233,17 +233,13 @@ __device__ __forceinline__ u64 mul_vcc(u64 a, u64 b) {
 
 // a * b mod p, the compiler-scheduled form: four chained v_mad_u64_u32 + reduce128, 21 instructions that the compiler interleaves with
 // whatever else the lane has to do. For LATENCY-bound code — the pair-form chains (p2::Coop2), the one-lane sponges, and the quad form
-// (p2::Coop4) before mul_vcc above, which GL_CHAIN_MUL_COMPILER_FORM brings back: with the
-// 14-instruction form below k_chain_full_q4 was 11 % slower (4.91 -> 5.45 s per step, profiles/r05/README.md), its carry chains through
-// SGPR pairs stall a lone wave. Weak in, weak out.
+// (p2::Coop4) before mul_vcc above, which GL_CHAIN_MUL_COMPILER_FORM brings back. The earlier hand-written forms did not replace it
+// there: with the 14-instruction mul_cyc above k_chain_full_q4 was 11 % slower (4.91 -> 5.45 s per step, profiles/r05/README.md), its
+// carry chains through SGPR pairs stall a lone wave; the 20-instruction mul_sched paid only where a wave runs ONE dependent S-box chain
+// (the row form: 9.99 -> 7.44 us per permutation) and lost 3-4 % where a lane has several independent multiplications (quad-form
+// chains, the trace fills' per-lane permutation): the compiler interleaves those instruction by instruction, opaque asm blocks it
+// cannot. Weak in, weak out.
 GL_HD u64 mul_lat(u64 a, u64 b) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MUL_SCHEDULED_EVERYWHERE)
-    // measured (bench.py): the hand-scheduled form only pays where a wave runs ONE dependent S-box chain (the row-form
-    // queue chains, p2::Coop: 9.99 -> 7.44 us per permutation with the other hand-scheduled pieces). Kernels with several
-    // independent multiplications per lane (quad-form chains, the per-lane permutation of the trace fills) lose 3-4 %:
-    // the compiler interleaves independent multiplications instruction by instruction, opaque asm blocks it cannot.
-    return mul_sched(a, b);
-#else
 #if defined(__HIP_DEVICE_COMPILE__)
     // four chained v_mad_u64_u32 give both halves of the 128-bit product; computing `a * b` and
     // `__umul64hi(a, b)` separately costs 5 mads + 2 v_mul_lo_u32 (+16 % instructions per S-box, measured)
@@ -258,7 +254,6 @@ GL_HD u64 mul_lat(u64 a, u64 b) {
     u64 lo = (u64)w, hi = (u64)(w >> 64);
 #endif
     return reduce128(lo, hi);
-#endif
 }
 
 // a * b mod p. On the device: the 14-instruction form (mul_cyc) — every kernel that keeps its SIMDs full is bound by VALU issue cycles,

@@ -439,24 +439,20 @@ __device__ __forceinline__ u64 coop_flattened(const Coop& co, u64 x, u32 g, Put&
 // (mad_acc / wp_reduce above), and the partial rounds are unrolled with their constants in the instruction stream: ~4.1k VALU
 // instructions per permutation step for 16 states (258 per permutation, tests/test_chain_sbox_isa.py; 319 with the S-boxes through
 // gl::mul_lat, 383 with the Wide layers as well).
-__device__ __forceinline__ u64 pow7_vcc(u64 x) {
-    const u64 x2 = gl::mul_vcc(x, x), x3 = gl::mul_vcc(x2, x), x4 = gl::mul_vcc(x2, x2);
-    return gl::mul_vcc(x3, x4);
+// The S-box product of the quad form: gl::mul_vcc; GL_CHAIN_MUL_COMPILER_FORM restores the compiler-scheduled gl::mul_lat (A/B builds,
+// tests/test_chain_sbox_isa.py). Two alternatives were measured and retired (docs/KERNELS.md 3.2, rounds 4 and 5): gl::mul_sched in the
+// partial rounds and gl::pow7 (mul_cyc) in the full rounds.
+__device__ __forceinline__ u64 q4_mul(u64 a, u64 b) {
+#if defined(GL_CHAIN_MUL_COMPILER_FORM)
+    return gl::mul_lat(a, b);
+#else
+    return gl::mul_vcc(a, b);
+#endif
 }
-#if defined(P2_Q4_PARTIAL_SCHED)
-#define Q4_PARTIAL_MUL gl::mul_sched
-#elif defined(GL_CHAIN_MUL_COMPILER_FORM)
-#define Q4_PARTIAL_MUL gl::mul_lat
-#else
-#define Q4_PARTIAL_MUL gl::mul_vcc
-#endif
-#if defined(P2_Q4_FULL_CYC)
-#define Q4_FULL_POW7 gl::pow7
-#elif defined(GL_CHAIN_MUL_COMPILER_FORM)
-#define Q4_FULL_POW7 gl::pow7_lat
-#else
-#define Q4_FULL_POW7 pow7_vcc
-#endif
+__device__ __forceinline__ u64 q4_pow7(u64 x) {
+    const u64 x2 = q4_mul(x, x), x3 = q4_mul(x2, x), x4 = q4_mul(x2, x2);
+    return q4_mul(x3, x4);
+}
 // a quad_perm DPP move whose every lane reads an active lane of its own quad (Coop4 runs on full waves): bound_ctrl set, so the
 // compiler needs no "old" value in the destination (dpp32 above costs a zeroing v_mov per move)
 template <int CTRL>
@@ -567,7 +563,7 @@ struct Coop4 {
 #pragma unroll
         for (int k = 0; k < P2_HALF_FULL_ROUNDS; k++) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) x[c] = Q4_FULL_POW7(add_rc(x[c], (u32)rc_full[k][c], (u32)(rc_full[k][c] >> 32)));
+            for (int c = 0; c < 3; c++) x[c] = q4_pow7(add_rc(x[c], (u32)rc_full[k][c], (u32)(rc_full[k][c] >> 32)));
             external(x);
         }
         // unrolled: the partial rounds' constants are literals of the instruction stream (no scalar load inside the permutation)
@@ -579,9 +575,9 @@ struct Coop4 {
             // lane 1 squares again — three multiplications per partial round instead of four for the whole wave. Only lane 0's sum
             // x[0] + rc is broadcast.
             const u64 t0 = qdpp64<QP_BCAST0>(add_rc<true>(x[0], (u32)rc, (u32)(rc >> 32)));
-            const u64 x2 = Q4_PARTIAL_MUL(t0, t0);
-            const u64 y = Q4_PARTIAL_MUL(x2, second ? x2 : t0);
-            const u64 sx = Q4_PARTIAL_MUL(y, qdpp64<QP_SWAP1>(y));
+            const u64 x2 = q4_mul(t0, t0);
+            const u64 y = q4_mul(x2, second ? x2 : t0);
+            const u64 sx = q4_mul(y, qdpp64<QP_SWAP1>(y));
             x[0] = first ? sx : x[0];
             internal(x);
         }
@@ -589,7 +585,7 @@ struct Coop4 {
         for (int k = 0; k < P2_HALF_FULL_ROUNDS; k++) {
 #pragma unroll
             for (int c = 0; c < 3; c++)
-                x[c] = Q4_FULL_POW7(add_rc(x[c], (u32)rc_full[P2_HALF_FULL_ROUNDS + k][c], (u32)(rc_full[P2_HALF_FULL_ROUNDS + k][c] >> 32)));
+                x[c] = q4_pow7(add_rc(x[c], (u32)rc_full[P2_HALF_FULL_ROUNDS + k][c], (u32)(rc_full[P2_HALF_FULL_ROUNDS + k][c] >> 32)));
             external(x);
         }
 #endif

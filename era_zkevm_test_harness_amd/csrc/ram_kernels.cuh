@@ -52,9 +52,12 @@ static __device__ __forceinline__ void k_encode_mem(const VB& vb, const zkw_mem_
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2: full-width queue chains. One chain per 16-lane DPP row (4 chains per wave, 1 wave per block so
-// that every chain gets its own SIMD issue slot when chains are few). tails[i] = permute(enc[i] ||
-// capacity(tails[i-1])). The absorb loads are prefetched one item ahead; stores are fire-and-forget.
+// K2: full-width queue chains, tails[i] = permute(enc[i] || capacity(tails[i-1])): the critical path of the step (docs/KERNELS.md 3.2).
+// ONE loop, `chain_body`, owns the protocol — the job fetch, the two item sources (encodings, or memory queries encoded on the fly,
+// optionally through a permutation), the prefetch, the deferred stores and the three outputs — and a FORM supplies the permutation and
+// how a state is laid over lanes: RowForm (16 lanes per state, 4 chains per wave), QuadForm (4 / 16), PairForm (2 / 32), LaneForm (1 / 64).
+// The log-queue chain (log_kernels.cuh, k_chain_log) is not a form of this loop: its tails are four words that move between lanes of
+// the row, each item brings a prehashed capacity besides its rate words, and it has one output whose store is not deferred.
 struct ChainJob {
     const u64* enc;      // [n][8], or nullptr: the items are memory queries, encoded on the fly from `q`
     u64* tails;          // [n][12], or nullptr when only the compact outputs below are wanted
@@ -91,334 +94,212 @@ __device__ __forceinline__ u64 pick8(const u64 e[8], int g) {
     return v;
 }
 
-// The stores of item i are issued at the top of iteration i + 1, before the prefetch of item i + 2: gfx9 counts
-// loads and stores in one in-order vmcnt, so consuming the prefetched encoding waits for every earlier store too.
-// Stored late, those stores are a whole permutation (>= 10 us) old by then; stored right after the permutation their
-// write latency was exposed once per step (15 -> 22.5 us per step beyond ~8.5 k concurrent chains).
-struct ChainOut {
-    u64* tails;
-    u64* caps;
-    u64* marks;
+// What a form provides (everything else is chain_body's):
+//   LANES          lanes per state (64 / LANES chains per wave); N, R: state words and rate words held by one lane
+//   init(j)        j = the lane's index inside its state
+//   reads_items()  whether this lane fetches items at all
+//   load_tail      the lane's share of tail_in[12]
+//   load_rate      its share of an item's eight rate words, as loads from enc + 8 i;  pick_rate: the same share of an encoded query
+//   absorb_permute AbsorptionModeOverwrite (rate part replaced, capacity kept) and the permutation; weak in, weak out
+//   store_tail / store_caps   its share of a canonical tail at a [..][12] address, of the capacity (elements 8..11) at a [..][4] address
+// Each form keeps its own access widths. Everything is forced inline and every per-lane array is indexed by unrolled constants: a
+// method left as a call, or an index known only at run time, would put the state in scratch memory.
+
+// Row form (p2::Coop): lane g of a 16-lane DPP row holds element g, lanes 12..15 idle. The lowest latency per item. 8-byte accesses:
+// loads in lanes g < 8, stores in the active lanes, caps from lanes 8..11.
+struct RowForm {
+    static constexpr int LANES = 16, N = 1, R = 1;
+    p2::Coop co;
+    int g;
+    __device__ __forceinline__ void init(int j) { g = j; co.init(j); }
+    __device__ __forceinline__ bool reads_items() const { return g < 8; }
+    __device__ __forceinline__ void load_tail(const u64* t, u64 x[N]) const { x[0] = (co.active && t) ? t[g] : 0; }
+    __device__ __forceinline__ void load_rate(const u64* enc, u64 e[R]) const { e[0] = enc[g]; }
+    __device__ __forceinline__ void pick_rate(const u64 ew[8], u64 e[R]) const { e[0] = pick8(ew, g); }
+    __device__ __forceinline__ void absorb_permute(u64 x[N], const u64 e[R]) const { x[0] = co.permute(g < 8 ? e[0] : x[0]); }
+    __device__ __forceinline__ void store_tail(u64* t, const u64 p[N]) const { if (co.active) t[g] = p[0]; }
+    __device__ __forceinline__ void store_caps(u64* c, const u64 p[N]) const { if (g >= 8 && g < 12) c[g - 8] = p[0]; }
 };
 
-// WAVES = 1: one wave per workgroup. WAVES = 4 (`k_chain_full_x4`, the chain service's launches): the four waves of a workgroup go to
-// the four SIMDs of ONE CU and the launch asks for more than half of a CU's LDS (unused), so that no two chain waves — of this launch or
-// of another chain launch that runs next to it — share a SIMD (as `k_chain_full_q4x4` below; measured with 96 blocks in flight: three
-// concurrent one-wave launches ran 1.4 - 1.5 x as long as alone).
-template <int WAVES>
-static __device__ __forceinline__ void chain_full_body(const ChainJob* __restrict__ jobs, int n_jobs) {
-    __builtin_amdgcn_s_setprio(3);  // a serial chain is latency-bound: its wave issues before the fill waves sharing the SIMD
-    const int lane = threadIdx.x & 63, g = lane & 15;
-    const int chain = (blockIdx.x * WAVES + (int)(threadIdx.x >> 6)) * 4 + (lane >> 4);
-    p2::Coop co;
-    co.init(g);
-    ChainJob job;
-    memset(&job, 0, sizeof job);
-    if (chain < n_jobs) job = jobs[chain];
-    u64 x = (co.active && job.tail_in) ? job.tail_in[g] : 0;
-    const bool absorbs = g < 8;
-    const bool from_q = job.enc == nullptr;
-    RawQuery rq_next;
-    rq_next.a = rq_next.b = rq_next.c = make_uint4(0, 0, 0, 0);
-    u64 e_next = 0;
-    u64 at_next = 0;  // index (into q) of item i + 2, fetched one iteration before its query
-    if (absorbs && job.n > 0) {
-        if (from_q) rq_next = load_raw_query(job.q + (job.perm ? job.perm[0] : 0)); else e_next = job.enc[g];
-    }
-    if (absorbs && from_q && job.n > 1) at_next = job.perm ? job.perm[1] : 1;
-    u64 next_mark = job.marks ? job.period : ~0ull, mark_idx = 0;  // item count at which the next full tail is kept
-    u64 pend = 0, pend_i = 0;  // canonical tail of the previous item, not stored yet
-    bool have_pend = false, pend_mark = false;
-    auto flush = [&]() {
-        if (!have_pend) return;
-        if (co.active && job.tails) job.tails[12 * pend_i + g] = pend;
-        if (g >= 8 && g < 12 && job.caps) job.caps[4 * pend_i + (g - 8)] = pend;
-        if (pend_mark) {
-            if (co.active) job.marks[12 * mark_idx + g] = pend;
-            mark_idx++;
-        }
-        have_pend = false;
-    };
-    for (u64 i = 0; __any(i < job.n); i++) {
-        const bool live = i < job.n;
-        u64 e = e_next;
-        if (from_q) {
-            u64 ew[8];
-            encode_raw_query(rq_next, ew);
-            e = pick8(ew, g);
-        }
-        flush();
-        if (absorbs && i + 1 < job.n) {
-            if (from_q) {
-                rq_next = load_raw_query(job.q + at_next);
-                if (i + 2 < job.n) at_next = job.perm ? job.perm[i + 2] : i + 2;
-            } else {
-                e_next = job.enc[8 * (i + 1) + g];
-            }
-        }
-        u64 y = co.permute(absorbs ? e : x);  // AbsorptionModeOverwrite
-        if (live) {
-            x = y;
-            pend = gl::canon(y);
-            pend_i = i;
-            have_pend = true;
-            pend_mark = job.marks && (i + 1 == next_mark || i + 1 == job.n);
-            if (pend_mark) next_mark += job.period;
-        }
-    }
-    flush();
-}
-static __global__ __launch_bounds__(64) void k_chain_full(const ChainJob* __restrict__ jobs, int n_jobs) { chain_full_body<1>(jobs, n_jobs); }
-static __global__ __launch_bounds__(256) void k_chain_full_x4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_full_body<4>(jobs, n_jobs); }
-
-// Quad form: 16 chains per wave (p2::Coop4). Lane j of a quad loads enc[j], enc[4+j] and stores tails[j],
-// tails[4+j], tails[8+j]: 32 contiguous bytes per quad per access.
-// WAVES = 1: one wave per workgroup (placed wherever a wave slot is free). WAVES = 4 (`k_chain_full_q4x4`): the four waves of a
-// workgroup go to the four SIMDs of ONE CU, and the launch asks for more than half of a CU's LDS (unused) so that a CU takes one such
-// workgroup: every chain wave of a launch of <= 16 384 chains has a SIMD without another chain wave on it, whatever else (the
-// other pipeline's fills) occupies the chip when the launch arrives — see dev_chains.
-template <int WAVES>
-static __device__ __forceinline__ void chain_full_q4_body(const ChainJob* __restrict__ jobs, int n_jobs) {
-    __builtin_amdgcn_s_setprio(3);  // a serial chain is latency-bound: its wave issues before the fill waves sharing the SIMD
-    const int lane = threadIdx.x & 63, j = lane & 3;
-    const int chain = blockIdx.x * (16 * WAVES) + (threadIdx.x >> 2);
+// Quad form (p2::Coop4): lane j of a quad holds elements j, 4 + j, 8 + j. 8-byte accesses, 32 contiguous bytes per quad and access.
+struct QuadForm {
+    static constexpr int LANES = 4, N = 3, R = 2;
     p2::Coop4 co;
-    co.init(j);
+    int j;
+    __device__ __forceinline__ void init(int j_) { j = j_; co.init(j_); }
+    __device__ __forceinline__ bool reads_items() const { return true; }
+    __device__ __forceinline__ void load_tail(const u64* t, u64 x[N]) const {
+#pragma unroll
+        for (int c = 0; c < 3; c++) x[c] = t ? t[4 * c + j] : 0;
+    }
+    __device__ __forceinline__ void load_rate(const u64* enc, u64 e[R]) const { e[0] = enc[j]; e[1] = enc[4 + j]; }
+    __device__ __forceinline__ void pick_rate(const u64 ew[8], u64 e[R]) const { e[0] = pick8(ew, j); e[1] = pick8(ew, 4 + j); }
+    __device__ __forceinline__ void absorb_permute(u64 x[N], const u64 e[R]) const { x[0] = e[0]; x[1] = e[1]; co.permute(x); }
+    __device__ __forceinline__ void store_tail(u64* t, const u64 p[N]) const {
+#pragma unroll
+        for (int c = 0; c < 3; c++) t[4 * c + j] = p[c];
+    }
+    __device__ __forceinline__ void store_caps(u64* c, const u64 p[N]) const { c[j] = p[2]; }
+};
+
+// Pair form (p2::Coop2): lane j of a pair holds elements 4c + 2j, 4c + 2j + 1 (x[2c], x[2c + 1]): 16-byte accesses, one per block of
+// four. Half the waves of the quad form for the same queues and ~half its wave-instructions per permutation: what a launch of tens of
+// thousands of queues takes away from the trace fills it overlaps.
+struct PairForm {
+    static constexpr int LANES = 2, N = 6, R = 4;
+    p2::Coop2 co;
+    int j;
+    __device__ __forceinline__ void init(int j_) { j = j_; co.init(j_); }
+    __device__ __forceinline__ bool reads_items() const { return true; }
+    __device__ __forceinline__ void load_tail(const u64* t, u64 x[N]) const {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            x[2 * c] = t ? t[4 * c + 2 * j] : 0;
+            x[2 * c + 1] = t ? t[4 * c + 2 * j + 1] : 0;
+        }
+    }
+    __device__ __forceinline__ void load_rate(const u64* enc, u64 e[R]) const {
+        const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(enc + 2 * j), hi = *reinterpret_cast<const ulonglong2*>(enc + 4 + 2 * j);
+        e[0] = lo.x; e[1] = lo.y; e[2] = hi.x; e[3] = hi.y;
+    }
+    __device__ __forceinline__ void pick_rate(const u64 ew[8], u64 e[R]) const {
+        e[0] = j ? ew[2] : ew[0];
+        e[1] = j ? ew[3] : ew[1];
+        e[2] = j ? ew[6] : ew[4];
+        e[3] = j ? ew[7] : ew[5];
+    }
+    __device__ __forceinline__ void absorb_permute(u64 x[N], const u64 e[R]) const {
+#pragma unroll
+        for (int k = 0; k < 4; k++) x[k] = e[k];
+        co.permute(x);
+    }
+    __device__ __forceinline__ void store_tail(u64* t, const u64 p[N]) const {
+#pragma unroll
+        for (int c = 0; c < 3; c++) *reinterpret_cast<ulonglong2*>(t + 4 * c + 2 * j) = make_ulonglong2(p[2 * c], p[2 * c + 1]);
+    }
+    __device__ __forceinline__ void store_caps(u64* c, const u64 p[N]) const { *reinterpret_cast<ulonglong2*>(c + 2 * j) = make_ulonglong2(p[4], p[5]); }
+};
+
+// Lane form (p2::permute): ONE CHAIN PER LANE, the whole state in the lane's registers. The cooperative forms buy latency with idle
+// lanes (during the 22 partial rounds only one S-box per state is live: 506 wave-instructions per permutation in the quad form); per
+// lane a permutation costs ~210. With tens of thousands of queues in one launch (bench.py: 2 x 14 440) latency per step is irrelevant
+// and VALU issue slots are what the chains take away from the trace fills they overlap: 29 k chains are 451 waves, fewer than half the
+// SIMDs, instead of 1 805 waves on every SIMD twice. 16-byte accesses, each lane on its own stream (48 B in, 32 B out per step): a
+// few hundred bytes per wave every ~25 us.
+struct LaneForm {
+    static constexpr int LANES = 1, N = 12, R = 8;
+    __device__ __forceinline__ void init(int) {}
+    __device__ __forceinline__ bool reads_items() const { return true; }
+    __device__ __forceinline__ void load_tail(const u64* t, u64 x[N]) const {
+#pragma unroll
+        for (int k = 0; k < 12; k++) x[k] = t ? t[k] : 0;
+    }
+    __device__ __forceinline__ void load_rate(const u64* enc, u64 e[R]) const {
+        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(enc);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const ulonglong2 v = src[k]; e[2 * k] = v.x; e[2 * k + 1] = v.y; }
+    }
+    __device__ __forceinline__ void pick_rate(const u64 ew[8], u64 e[R]) const {
+#pragma unroll
+        for (int k = 0; k < 8; k++) e[k] = ew[k];
+    }
+    __device__ __forceinline__ void absorb_permute(u64 x[N], const u64 e[R]) const {
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = e[k];
+        p2::permute(x);
+    }
+    __device__ __forceinline__ void store_tail(u64* t, const u64 p[N]) const {
+        ulonglong2* d = reinterpret_cast<ulonglong2*>(t);
+#pragma unroll
+        for (int k = 0; k < 6; k++) d[k] = make_ulonglong2(p[2 * k], p[2 * k + 1]);
+    }
+    __device__ __forceinline__ void store_caps(u64* c, const u64 p[N]) const {
+        ulonglong2* d = reinterpret_cast<ulonglong2*>(c);
+        d[0] = make_ulonglong2(p[8], p[9]);
+        d[1] = make_ulonglong2(p[10], p[11]);
+    }
+};
+
+// WAVES = 1: one wave per workgroup (placed wherever a wave slot is free). WAVES = 4 (`k_chain_full_x4`, `k_chain_full_q4x4`): the four
+// waves of a workgroup go to the four SIMDs of ONE CU and the launch asks for more than half of a CU's LDS (unused), so that a CU takes
+// one such workgroup and no two chain waves — of this launch or of another chain launch that runs next to it — share a SIMD, whatever
+// else (the other pipeline's fills) occupies the chip when the launch arrives: see launch_chain (measured with 96 blocks in flight:
+// three concurrent one-wave launches ran 1.4 - 1.5 x as long as alone).
+template <class Form, int WAVES>
+static __device__ __forceinline__ void chain_body(const ChainJob* __restrict__ jobs, int n_jobs) {
+    __builtin_amdgcn_s_setprio(3);  // a serial chain is latency-bound: its wave issues before the fill waves sharing the SIMD
+    const int chain = blockIdx.x * (64 * WAVES / Form::LANES) + threadIdx.x / Form::LANES;
+    Form form;
+    form.init(threadIdx.x % Form::LANES);
     ChainJob job;
     memset(&job, 0, sizeof job);
     if (chain < n_jobs) job = jobs[chain];
-    u64 x[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) x[c] = job.tail_in ? job.tail_in[4 * c + j] : 0;
-    u64 e0 = 0, e1 = 0;
+    u64 x[Form::N];  // the lane's share of the running state (weak)
+    form.load_tail(job.tail_in, x);
+    const bool reads = form.reads_items();
     const bool from_q = job.enc == nullptr;
+    // item i + 1 is fetched during the permutation of item i: its rate words (e_next), or its query (rq_next), whose index — when the
+    // items go through `perm` — was fetched one iteration earlier still (at_next: the index into q of item i + 2)
+    u64 e_next[Form::R] = {};
     RawQuery rq_next;
     rq_next.a = rq_next.b = rq_next.c = make_uint4(0, 0, 0, 0);
-    u64 at_next = 0;  // index (into q) of item i + 2, fetched one iteration before its query
-    if (job.n > 0) {
-        if (from_q) rq_next = load_raw_query(job.q + (job.perm ? job.perm[0] : 0)); else { e0 = job.enc[j]; e1 = job.enc[4 + j]; }
+    u64 at_next = 0;
+    if (reads && job.n > 0) {
+        if (from_q) rq_next = load_raw_query(job.q + (job.perm ? job.perm[0] : 0)); else form.load_rate(job.enc, e_next);
     }
-    if (from_q && job.n > 1) at_next = job.perm ? job.perm[1] : 1;
-    u64 next_mark = job.marks ? job.period : ~0ull, mark_idx = 0;
-    u64 pend[3] = {0, 0, 0}, pend_i = 0;
+    if (reads && from_q && job.n > 1) at_next = job.perm ? job.perm[1] : 1;
+    u64 next_mark = job.marks ? job.period : ~0ull, mark_idx = 0;  // item count at which the next full tail is kept
+    // The stores of item i are issued at the top of iteration i + 1, before the prefetch of item i + 2: gfx9 counts loads and stores in
+    // one in-order vmcnt, so consuming the prefetched item waits for every earlier store too. Stored late, those stores are a whole
+    // permutation (>= 10 us) old by then; stored right after the permutation their write latency was exposed once per step (15 -> 22.5 us
+    // per step beyond ~8.5 k concurrent chains).
+    u64 pend[Form::N] = {}, pend_i = 0;  // canonical tail of the previous item, not stored yet
     bool have_pend = false, pend_mark = false;
     auto flush = [&]() {
         if (!have_pend) return;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            if (job.tails) job.tails[12 * pend_i + 4 * c + j] = pend[c];
-            if (c == 2 && job.caps) job.caps[4 * pend_i + j] = pend[c];
-            if (pend_mark) job.marks[12 * mark_idx + 4 * c + j] = pend[c];
-        }
-        if (pend_mark) mark_idx++;
+        if (job.tails) form.store_tail(job.tails + 12 * pend_i, pend);
+        if (job.caps) form.store_caps(job.caps + 4 * pend_i, pend);
+        if (pend_mark) form.store_tail(job.marks + 12 * mark_idx++, pend);
         have_pend = false;
     };
-    for (u64 i = 0; __any(i < job.n); i++) {
+    for (u64 i = 0; __any(i < job.n); i++) {  // (a lane past its chain's end permutes on, to no effect: the wave runs while any lane is live)
         const bool live = i < job.n;
+        u64 e[Form::R];
         if (from_q) {
             u64 ew[8];
             encode_raw_query(rq_next, ew);
-            e0 = pick8(ew, j);
-            e1 = pick8(ew, 4 + j);
+            form.pick_rate(ew, e);
+        } else {
+#pragma unroll
+            for (int k = 0; k < Form::R; k++) e[k] = e_next[k];
         }
-        u64 y[3] = {e0, e1, x[2]};  // AbsorptionModeOverwrite: rate part replaced, capacity kept
         flush();
-        if (i + 1 < job.n) {
+        if (reads && i + 1 < job.n) {
             if (from_q) {
                 rq_next = load_raw_query(job.q + at_next);
                 if (i + 2 < job.n) at_next = job.perm ? job.perm[i + 2] : i + 2;
             } else {
-                e0 = job.enc[8 * (i + 1) + j]; e1 = job.enc[8 * (i + 1) + 4 + j];
+                form.load_rate(job.enc + 8 * (i + 1), e_next);
             }
         }
-        co.permute(y);
+        form.absorb_permute(x, e);
         if (live) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
-                x[c] = y[c];
-                pend[c] = gl::canon(y[c]);
-            }
+            for (int k = 0; k < Form::N; k++) pend[k] = gl::canon(x[k]);
             pend_i = i;
             have_pend = true;
-            pend_mark = job.marks && (i + 1 == next_mark || i + 1 == job.n);
+            pend_mark = job.marks && (i + 1 == next_mark || i + 1 == job.n);  // a periodic mark that is also the last one is ONE mark
             if (pend_mark) next_mark += job.period;
         }
     }
     flush();
 }
-static __global__ __launch_bounds__(64) void k_chain_full_q4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_full_q4_body<1>(jobs, n_jobs); }
-static __global__ __launch_bounds__(256) void k_chain_full_q4x4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_full_q4_body<4>(jobs, n_jobs); }
-
-// Pair form: 32 chains per wave (p2::Coop2). Lane j of a pair holds elements 4c + 2j, 4c + 2j + 1: it loads / stores 16
-// contiguous bytes per block of four. Half the waves of the quad form for the same queues and ~half its wave-instructions per
-// permutation: what a launch of tens of thousands of queues takes away from the trace fills it overlaps.
-static __global__ __launch_bounds__(64) void k_chain_full_p2(const ChainJob* __restrict__ jobs, int n_jobs) {
-    __builtin_amdgcn_s_setprio(3);  // a serial chain is latency-bound: its wave issues before the fill waves sharing the SIMD
-    const int lane = threadIdx.x & 63, j = lane & 1;
-    const int chain = blockIdx.x * 32 + (lane >> 1);
-    p2::Coop2 co;
-    co.init(j);
-    ChainJob job;
-    memset(&job, 0, sizeof job);
-    if (chain < n_jobs) job = jobs[chain];
-    u64 x[6];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        x[2 * c] = job.tail_in ? job.tail_in[4 * c + 2 * j] : 0;
-        x[2 * c + 1] = job.tail_in ? job.tail_in[4 * c + 2 * j + 1] : 0;
-    }
-    u64 e[4] = {0, 0, 0, 0};  // rate elements 2j, 2j + 1, 4 + 2j, 5 + 2j of the next item
-    const bool from_q = job.enc == nullptr;
-    RawQuery rq_next;
-    rq_next.a = rq_next.b = rq_next.c = make_uint4(0, 0, 0, 0);
-    u64 at_next = 0;  // index (into q) of item i + 2, fetched one iteration before its query
-    auto load_enc = [&](u64 i) {
-        const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(job.enc + 8 * i + 2 * j), hi = *reinterpret_cast<const ulonglong2*>(job.enc + 8 * i + 4 + 2 * j);
-        e[0] = lo.x; e[1] = lo.y; e[2] = hi.x; e[3] = hi.y;
-    };
-    if (job.n > 0) {
-        if (from_q) rq_next = load_raw_query(job.q + (job.perm ? job.perm[0] : 0)); else load_enc(0);
-    }
-    if (from_q && job.n > 1) at_next = job.perm ? job.perm[1] : 1;
-    u64 next_mark = job.marks ? job.period : ~0ull, mark_idx = 0;
-    u64 pend[6] = {0, 0, 0, 0, 0, 0}, pend_i = 0;
-    bool have_pend = false, pend_mark = false;
-    auto flush = [&]() {  // the stores of item i go out at the top of iteration i + 1 (see k_chain_full)
-        if (!have_pend) return;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const ulonglong2 v = make_ulonglong2(pend[2 * c], pend[2 * c + 1]);
-            if (job.tails) *reinterpret_cast<ulonglong2*>(job.tails + 12 * pend_i + 4 * c + 2 * j) = v;
-            if (c == 2 && job.caps) *reinterpret_cast<ulonglong2*>(job.caps + 4 * pend_i + 2 * j) = v;
-            if (pend_mark) *reinterpret_cast<ulonglong2*>(job.marks + 12 * mark_idx + 4 * c + 2 * j) = v;
-        }
-        if (pend_mark) mark_idx++;
-        have_pend = false;
-    };
-    for (u64 i = 0; __any(i < job.n); i++) {
-        const bool live = i < job.n;
-        if (from_q) {
-            u64 ew[8];
-            encode_raw_query(rq_next, ew);
-            e[0] = j ? ew[2] : ew[0];
-            e[1] = j ? ew[3] : ew[1];
-            e[2] = j ? ew[6] : ew[4];
-            e[3] = j ? ew[7] : ew[5];
-        }
-        u64 y[6] = {e[0], e[1], e[2], e[3], x[4], x[5]};  // AbsorptionModeOverwrite: rate part replaced, capacity kept
-        flush();
-        if (i + 1 < job.n) {
-            if (from_q) {
-                rq_next = load_raw_query(job.q + at_next);
-                if (i + 2 < job.n) at_next = job.perm ? job.perm[i + 2] : i + 2;
-            } else {
-                load_enc(i + 1);
-            }
-        }
-        co.permute(y);
-        if (live) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                x[c] = y[c];
-                pend[c] = gl::canon(y[c]);
-            }
-            pend_i = i;
-            have_pend = true;
-            pend_mark = job.marks && (i + 1 == next_mark || i + 1 == job.n);
-            if (pend_mark) next_mark += job.period;
-        }
-    }
-    flush();
-}
-
-// Lane form: ONE CHAIN PER LANE, 64 chains per wave (p2::permute, the whole state in the lane's registers). The
-// cooperative forms above buy latency with idle lanes (during the 22 partial rounds only one S-box per state is live:
-// 506 wave-instructions per permutation in the quad form); per lane a permutation costs ~210. With tens of thousands
-// of queues in one launch (bench.py: 2 x 14 440) latency per step is irrelevant and VALU issue slots are what the
-// chains take away from the trace fills they overlap: 29 k chains are 451 waves, fewer than half the SIMDs, instead of
-// 1 805 waves on every SIMD twice. Accesses are per-lane (48 B in, 32 B out per step, each lane on its own stream): a few
-// hundred bytes per wave every ~25 us.
-static __global__ __launch_bounds__(64) void k_chain_full_lane(const ChainJob* __restrict__ jobs, int n_jobs) {
-    __builtin_amdgcn_s_setprio(3);  // a serial chain is latency-bound: its wave issues before the fill waves sharing the SIMD
-    const int chain = blockIdx.x * 64 + (threadIdx.x & 63);
-    ChainJob job;
-    memset(&job, 0, sizeof job);
-    if (chain < n_jobs) job = jobs[chain];
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = job.tail_in ? job.tail_in[k] : 0;
-    const bool from_q = job.enc == nullptr;
-    RawQuery rq_next;
-    rq_next.a = rq_next.b = rq_next.c = make_uint4(0, 0, 0, 0);
-    u64 e_next[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    u64 at_next = 0;
-    if (job.n > 0) {
-        if (from_q) rq_next = load_raw_query(job.q + (job.perm ? job.perm[0] : 0));
-        else {
-            const ulonglong2* src = reinterpret_cast<const ulonglong2*>(job.enc);
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const ulonglong2 v = src[k]; e_next[2 * k] = v.x; e_next[2 * k + 1] = v.y; }
-        }
-    }
-    if (from_q && job.n > 1) at_next = job.perm ? job.perm[1] : 1;
-    u64 next_mark = job.marks ? job.period : ~0ull, mark_idx = 0;
-    u64 pend[12], pend_i = 0;
-#pragma unroll
-    for (int k = 0; k < 12; k++) pend[k] = 0;
-    bool have_pend = false, pend_mark = false;
-    auto flush = [&]() {  // the stores of item i go out at the top of iteration i + 1 (see k_chain_full)
-        if (!have_pend) return;
-        if (job.tails) {
-            ulonglong2* d = reinterpret_cast<ulonglong2*>(job.tails + 12 * pend_i);
-#pragma unroll
-            for (int k = 0; k < 6; k++) d[k] = make_ulonglong2(pend[2 * k], pend[2 * k + 1]);
-        }
-        if (job.caps) {
-            ulonglong2* d = reinterpret_cast<ulonglong2*>(job.caps + 4 * pend_i);
-            d[0] = make_ulonglong2(pend[8], pend[9]);
-            d[1] = make_ulonglong2(pend[10], pend[11]);
-        }
-        if (pend_mark) {
-            ulonglong2* d = reinterpret_cast<ulonglong2*>(job.marks + 12 * mark_idx);
-#pragma unroll
-            for (int k = 0; k < 6; k++) d[k] = make_ulonglong2(pend[2 * k], pend[2 * k + 1]);
-            mark_idx++;
-        }
-        have_pend = false;
-    };
-    for (u64 i = 0; __any(i < job.n); i++) {
-        const bool live = i < job.n;
-        u64 e[8];
-        if (from_q) encode_raw_query(rq_next, e);
-        else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) e[k] = e_next[k];
-        }
-        flush();
-        if (i + 1 < job.n) {
-            if (from_q) {
-                rq_next = load_raw_query(job.q + at_next);
-                if (i + 2 < job.n) at_next = job.perm ? job.perm[i + 2] : i + 2;
-            } else {
-                const ulonglong2* src = reinterpret_cast<const ulonglong2*>(job.enc + 8 * (i + 1));
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const ulonglong2 v = src[k]; e_next[2 * k] = v.x; e_next[2 * k + 1] = v.y; }
-            }
-        }
-        if (live) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) s[k] = e[k];  // AbsorptionModeOverwrite
-            p2::permute(s);
-#pragma unroll
-            for (int k = 0; k < 12; k++) pend[k] = gl::canon(s[k]);
-            pend_i = i;
-            have_pend = true;
-            pend_mark = job.marks && (i + 1 == next_mark || i + 1 == job.n);
-            if (pend_mark) next_mark += job.period;
-        }
-    }
-    flush();
-}
+static __global__ __launch_bounds__(64) void k_chain_full(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<RowForm, 1>(jobs, n_jobs); }
+static __global__ __launch_bounds__(256) void k_chain_full_x4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<RowForm, 4>(jobs, n_jobs); }
+static __global__ __launch_bounds__(64) void k_chain_full_q4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<QuadForm, 1>(jobs, n_jobs); }
+static __global__ __launch_bounds__(256) void k_chain_full_q4x4(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<QuadForm, 4>(jobs, n_jobs); }
+static __global__ __launch_bounds__(64) void k_chain_full_p2(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<PairForm, 1>(jobs, n_jobs); }
+static __global__ __launch_bounds__(64) void k_chain_full_lane(const ChainJob* __restrict__ jobs, int n_jobs) { chain_body<LaneForm, 1>(jobs, n_jobs); }
 
 // ------------------------------------------------------------------------------------------------
 // K5: Fiat-Shamir challenges, one job per lane (a handful of permutations; latency-irrelevant).

@@ -456,12 +456,6 @@ extern "C" int zkw_profile_names(zkw_ctx* ctx, char* buf, size_t buf_bytes) {
     return ZKW_OK;
 }
 
-// The quad chain kernel's launch. Up to 16 384 chains (= 256 CUs x 4 SIMDs x 16 chains per wave) go out as 4-wave workgroups with an
-// LDS request of more than half a CU's 160 KB: one workgroup per CU, its waves on the CU's four SIMDs — no two chain waves of the launch
-// share a SIMD even when the launch arrives on a chip that another stream's fill kernels keep full (one-wave workgroups then land
-// wherever a slot is free, some SIMDs get two or three chain waves, and the pass takes 1.5x or 2x as long: the slowest chain sets it).
-// A second such launch cannot start on a CU that still holds the first one's workgroup, so overlapping chain passes queue up instead of
-// doubling up. ZKW_CHAIN_WG4=0 restores one-wave workgroups.
 // the LDS request that lets a CU take ONE 4-wave workgroup of `func` (more than half of the CU's LDS, from the device's own figure); -1 when
 // the device refuses it: a device or partition mode without that much LDS per workgroup runs the one-wave form, which is correct everywhere
 static int one_workgroup_per_cu_lds(const void* func, int slot /* 0 .. 3: which kernel */) {
@@ -479,25 +473,33 @@ static int one_workgroup_per_cu_lds(const void* func, int slot /* 0 .. 3: which 
     }
     return lds;
 }
-static int launch_chain_q4(hipStream_t st, const ChainJob* d_jobs, int n_jobs) {
-    static const bool wg4 = [] { const char* e = getenv("ZKW_CHAIN_WG4"); return !(e && e[0] == '0'); }();
-    if (wg4 && n_jobs > 64 && n_jobs <= 256 * 64) {
-        const int lds = one_workgroup_per_cu_lds(reinterpret_cast<const void*>(&k_chain_full_q4x4), 0);
-        if (lds > 0) {
-            hipLaunchKernelGGL(k_chain_full_q4x4, dim3((n_jobs + 63) / 64), dim3(256), (size_t)lds, st, d_jobs, n_jobs);
-            return ZKW_OK;
-        }
+// The ONE place that picks a queue-chain kernel and its geometry. `form` = lanes per Poseidon2 state: 16 row, 4 quad, 2 pair, 1 lane.
+// The row and quad forms have a 4-wave variant: up to 4 096 / 16 384 chains (= 256 CUs x 4 SIMDs x 4 / 16 chains per wave) go out as
+// 4-wave workgroups with an LDS request of more than half a CU's 160 KB: one workgroup per CU, its waves on the CU's four SIMDs — no two
+// chain waves share a SIMD, of this launch or of launches that run side by side (a memory-queue stage next to a decommit stage next to a
+// log-queue stage), even when the launch arrives on a chip that another stream's fill kernels keep full (one-wave workgroups then land
+// wherever a slot is free, some SIMDs get two or three chain waves, and the pass takes 1.5x or 2x as long: the slowest chain sets it).
+// A second such launch cannot start on a CU that still holds the first one's workgroup, so overlapping chain passes queue up instead of
+// doubling up. `allow_wg4` = false or ZKW_CHAIN_WG4=0: one-wave workgroups. Returns the name of the kernel it launched.
+static const char* launch_chain(int form, bool allow_wg4, hipStream_t st, const ChainJob* d_jobs, int n_jobs) {
+    static const bool wg4_env = [] { const char* e = getenv("ZKW_CHAIN_WG4"); return !(e && e[0] == '0'); }();
+    const bool wg4 = allow_wg4 && wg4_env;
+    const unsigned per_wave = 64 / form, waves = (n_jobs + per_wave - 1) / per_wave;
+    if (form == 4) {
+        const int lds = wg4 && n_jobs > 64 && n_jobs <= 256 * 64 ? one_workgroup_per_cu_lds(reinterpret_cast<const void*>(&k_chain_full_q4x4), 0) : -1;
+        if (lds > 0) { hipLaunchKernelGGL(k_chain_full_q4x4, dim3((waves + 3) / 4), dim3(256), (size_t)lds, st, d_jobs, n_jobs); return "k_chain_full_q4x4"; }
+        hipLaunchKernelGGL(k_chain_full_q4, dim3(waves), dim3(64), 0, st, d_jobs, n_jobs);
+        return "k_chain_full_q4";
     }
-    hipLaunchKernelGGL(k_chain_full_q4, dim3((n_jobs + 15) / 16), dim3(64), 0, st, d_jobs, n_jobs);
-    return ZKW_OK;
-}
-// the row forms as the chain service launches them: 16 chains per 4-wave workgroup, one workgroup per CU (up to 4 096 chains), so that the
-// waves of launches that run side by side — a memory-queue stage next to a decommit stage next to a log-queue stage — never share a SIMD
-static void launch_chain_full_rows(hipStream_t st, const ChainJob* d_jobs, int n_jobs) {
-    static const bool wg4 = [] { const char* e = getenv("ZKW_CHAIN_WG4"); return !(e && e[0] == '0'); }();
-    const int lds = wg4 && n_jobs > 4 && n_jobs <= 256 * 16 ? one_workgroup_per_cu_lds(reinterpret_cast<const void*>(&k_chain_full_x4), 1) : -1;
-    if (lds > 0) hipLaunchKernelGGL(k_chain_full_x4, dim3((n_jobs + 15) / 16), dim3(256), (size_t)lds, st, d_jobs, n_jobs);
-    else hipLaunchKernelGGL(k_chain_full, dim3((n_jobs + 3) / 4), dim3(64), 0, st, d_jobs, n_jobs);
+    if (form == 16) {
+        const int lds = wg4 && n_jobs > 4 && n_jobs <= 256 * 16 ? one_workgroup_per_cu_lds(reinterpret_cast<const void*>(&k_chain_full_x4), 1) : -1;
+        if (lds > 0) { hipLaunchKernelGGL(k_chain_full_x4, dim3((waves + 3) / 4), dim3(256), (size_t)lds, st, d_jobs, n_jobs); return "k_chain_full_x4"; }
+        hipLaunchKernelGGL(k_chain_full, dim3(waves), dim3(64), 0, st, d_jobs, n_jobs);
+        return "k_chain_full";
+    }
+    if (form == 2) { hipLaunchKernelGGL(k_chain_full_p2, dim3(waves), dim3(64), 0, st, d_jobs, n_jobs); return "k_chain_full_p2"; }
+    hipLaunchKernelGGL(k_chain_full_lane, dim3(waves), dim3(64), 0, st, d_jobs, n_jobs);
+    return "k_chain_full_lane";
 }
 static void launch_chain_log_rows(hipStream_t st, const LogChainJob* d_jobs, int n_jobs) {
     static const bool wg4 = [] { const char* e = getenv("ZKW_CHAIN_WG4"); const char* l = getenv("ZKW_CHAIN_LOG_WG4"); return !(e && e[0] == '0') && !(l && l[0] == '0'); }();
@@ -507,8 +509,7 @@ static void launch_chain_log_rows(hipStream_t st, const LogChainJob* d_jobs, int
 }
 
 int zkw_launch_chain_full(hipStream_t st, const ChainJob* d_jobs, int n_jobs) {
-    if (n_jobs >= 4096) return launch_chain_q4(st, d_jobs, n_jobs);
-    launch_chain_full_rows(st, d_jobs, n_jobs);
+    launch_chain(n_jobs >= 4096 ? 4 : 16, true, st, d_jobs, n_jobs);  // row form while every wave can have a SIMD to itself
     return ZKW_OK;
 }
 int zkw_launch_chain_log(hipStream_t st, const LogChainJob* d_jobs, int n_jobs) {
@@ -683,10 +684,7 @@ struct ChainService {
                 fail_hip(hipStreamSynchronize(st), "job upload");
                 const int nf = (int)b->full.size(), nl = (int)b->log.size();
                 if (rc == ZKW_OK && nl) launch_chain_log_rows(sl, reinterpret_cast<const LogChainJob*>(dp + off_log), nl);
-                if (rc == ZKW_OK && nf) {
-                    if (nf >= 4096) { const int lrc = launch_chain_q4(st, reinterpret_cast<const ChainJob*>(dp), nf); if (lrc != ZKW_OK && rc == ZKW_OK) { rc = lrc; err = "chain launch (quad form)"; } }
-                    else launch_chain_full_rows(st, reinterpret_cast<const ChainJob*>(dp), nf);
-                }
+                if (rc == ZKW_OK && nf) launch_chain(nf >= 4096 ? 4 : 16, true, st, reinterpret_cast<const ChainJob*>(dp), nf);
                 fail_hip(hipGetLastError(), "chain launch");
                 fail_hip(hipStreamSynchronize(sl), "chain batch (log queues)");
                 {
@@ -811,19 +809,18 @@ int dev_chains(zkw_ctx* ctx, const std::vector<ChainJob>& jobs) {
         HIP_TRY(hipStreamWaitEvent(ctx->chain_stream, ctx->chain_ev_a, 0));
         st = ctx->chain_stream;
     }
+    // (the profiling key is the form's, whichever of its kernels runs; form 16 here is not one of several launches side by side: one-wave workgroups)
     const char* name = form == 16 ? "k_chain_full" : form == 4 ? "k_chain_full_q4" : form == 2 ? "k_chain_full_p2" : "k_chain_full_lane";
+    const char* launched;
     {
         Prof _p(ctx, name);
-        if (form == 16) hipLaunchKernelGGL(k_chain_full, dim3((n_jobs + 3) / 4), dim3(64), 0, st, d_jobs, n_jobs);
-        else if (form == 4) ZKW_TRY(launch_chain_q4(st, d_jobs, n_jobs));
-        else if (form == 2) hipLaunchKernelGGL(k_chain_full_p2, dim3((n_jobs + 31) / 32), dim3(64), 0, st, d_jobs, n_jobs);
-        else hipLaunchKernelGGL(k_chain_full_lane, dim3((n_jobs + 63) / 64), dim3(64), 0, st, d_jobs, n_jobs);
+        launched = launch_chain(form, form != 16, st, d_jobs, n_jobs);
         if (ctx->chain_stream) {  // the profiling events live on the context's stream: bring the kernel's end onto it first
             HIP_TRY(hipEventRecord(ctx->chain_ev_b, ctx->chain_stream));
             HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->chain_ev_b, 0));
         }
     }
-    return launch_check(name);
+    return launch_check(launched);
 }
 
 int dev_fs(zkw_ctx* ctx, const std::vector<FsJob>& jobs, int state_w, int n_chal) {

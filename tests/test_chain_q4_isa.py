@@ -50,13 +50,25 @@ def test_permutation_is_straight_line(probe):
     assert not [ln for ln in one if ln.startswith("s_cbranch")]
 
 
+# VGPRs of the six queue-chain kernels before they became instantiations of one loop (ram_kernels.cuh, chain_body): the shared loop may
+# not cost a form registers (docs/KERNELS.md 3.2, round 9)
+CHAIN_VGPRS = {"k_chain_full": 93, "k_chain_full_x4": 93, "k_chain_full_q4": 162, "k_chain_full_q4x4": 162, "k_chain_full_p2": 242,
+               "k_chain_full_lane": 140}
+
+
 def test_quad_chain_kernels_use_no_scratch(tmp_path):
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, "zkw_api.hip"), "-o",
                         str(tmp_path / "x.o"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     names = re.findall(r"Function Name: (\S+)", r.stderr)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    assert len(names) == len(scratch)
+    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", r.stderr)]
+    assert len(names) == len(scratch) == len(vgprs)
     q4 = {n: s for n, s in zip(names, scratch) if "k_chain_full_q4" in n}
     assert len(q4) == 2, q4
     assert not any(q4.values()), q4
+    # every form of the chain loop: no scratch, and no more VGPRs than its hand-written kernel had
+    chain = {m.group(1): (s, v) for n, s, v in zip(names, scratch, vgprs) if (m := re.search(r"\d+(k_chain_full\w*?)EPKNS", n))}
+    assert sorted(chain) == sorted(CHAIN_VGPRS), chain
+    for k, (s, v) in chain.items():
+        assert s == 0 and v <= CHAIN_VGPRS[k], (k, s, v)

@@ -59,7 +59,7 @@ def test_queue_chain_forms_agree(ctx, oracle, form):
 
 def test_queue_chain_thousands_of_queues_take_the_quad_form(ctx, oracle):
     """4 100 short queues in one call: dev_chains picks the quad form by itself (>= 4 096 chains) and launches it as 4-wave workgroups,
-    one per CU (launch_chain_q4: the path of the throughput benchmark); the last workgroup is partly empty. Every queue against the oracle."""
+    one per CU (launch_chain: the path of the throughput benchmark); the last workgroup is partly empty. Every queue against the oracle."""
     rng = np.random.default_rng(5)
     lens = rng.integers(0, 4, 4100).tolist()
     lens[17], lens[4099] = 9, 3
@@ -73,13 +73,15 @@ def test_queue_chain_thousands_of_queues_take_the_quad_form(ctx, oracle):
             assert np.array_equal(got[lo:lo + ln], oracle.queue_push_chain_full(enc[lo:lo + ln], tins[k])), k
 
 
-@pytest.mark.parametrize("form", [1, 2, 4])
+@pytest.mark.parametrize("form", [1, 2, 4, 16])
 def test_ram_builder_chain_forms(ctx, oracle, form):
     """the RAM builder's chain path (queries encoded on the fly, the sorted side through the permutation, capacity words +
-    instance-end tails as outputs) in the lane and quad forms: a ragged batch of blocks against the oracle"""
+    instance-end tails as outputs) in every form of the one chain loop: a ragged batch of blocks against the oracle. With 512 queries
+    per instance the blocks of 1, 512, 513 and 1024 queries are where the marks can go wrong: a one-item chain, a length that is a
+    multiple of the period (the periodic mark and the final one coincide and are ONE mark), one item past such a boundary."""
     from era_zkevm_test_harness_amd import native
 
-    sizes = [2500, 700, 1301, 64, 999]
+    sizes = [2500, 700, 1301, 64, 999, 1, 512, 513, 1024]
     qs = [synthetic.ram_trace(n, seed=300 + k) for k, n in enumerate(sizes)]
     offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
     ctx.set_chain_form(form)
