@@ -125,68 +125,12 @@ __device__ __forceinline__ void fill_flattened_poseidon(u64* trace, size_t n_row
 }
 
 // ------------------------------------------------------------------------------------------------
-// Poseidon2 rows (regions PU and PS): one lane per cycle runs the permutation and stores all 130
-// flattened-gate variables as it goes. SIDE 0 = unsorted queue, 1 = sorted queue.
-template <int SIDE>
-static __device__ __forceinline__ void k_ram_fill_poseidon(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity,
-                                                          size_t n_rows) {
-    __shared__ u32 sh_hist[256];
-    for (int t = threadIdx.x; t < 256; t += blockDim.x) sh_hist[t] = 0;
-    __syncthreads();
-    const SynthJob job = jobs[vb.y];
-    const u32 i = vb.x * blockDim.x + threadIdx.x;
-    if (i < capacity) {
-        u64* trace = job.trace;
-        const zkw_ram_instance* in = job.inst;
-        const size_t first = in->first_item, m = in->num_items;
-        const bool can_pop = i < m;
-        const size_t row = (size_t)(SIDE == 0 ? RC_ROW_PU : RC_ROW_PS) * RC_REGION_STRIDE(capacity) + i;
-        const zkw_mem_query* qs = SIDE == 0 ? job.unsorted_q : job.sorted_q;
-        const u64* caps = SIDE == 0 ? job.unsorted_caps : job.sorted_caps;
-        u64 s[12];
-        if (can_pop) {
-            encode_raw_query(load_raw_query(qs + first + i), s);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) s[k] = 0;
-        }
-        const RegsIn ri = regs_in(in);
-        // capacity part of the queue head entering this cycle
-        const u64* prev_cap = i == 0 ? (SIDE == 0 ? ri.uh : ri.sh) + 8 : caps + 4 * (first + (i - 1 < m ? i - 1 : m - 1));
-#pragma unroll
-        for (int k = 0; k < 4; k++) s[8 + k] = prev_cap[k];
-        fill_flattened_poseidon(trace, n_rows, row, s);
-        // spare general slots + lookup cells of this row type
-        zkw_mem_query q;
-        memset(&q, 0, sizeof q);
-        if (can_pop) q = job.sorted_q[first + i];
-        if (SIDE == 0) {
-            TR(RC_PU_idx, row) = q.index; TR(RC_PU_v0, row) = q.value[0]; TR(RC_PU_v1, row) = q.value[1];
-            put_bytes(trace, n_rows, row, RC_PU_idx_b0, q.index);
-            put_bytes(trace, n_rows, row, RC_PU_v0_b0, q.value[0]);
-            put_bytes(trace, n_rows, row, RC_PU_v1_b0, q.value[1]);
-            hist_bytes(sh_hist, q.index); hist_bytes(sh_hist, q.value[0]); hist_bytes(sh_hist, q.value[1]);
-        } else {
-            if (!job.tail_clean) for (int c = 130; c < RC_G; c++) TR(c, row) = 0;
-            put_bytes(trace, n_rows, row, RC_PS_ts_b0, q.timestamp);
-            put_bytes(trace, n_rows, row, RC_PS_page_b0, q.page);
-            put_bytes(trace, n_rows, row, RC_PS_v4_b0, q.value[4]);
-            hist_bytes(sh_hist, q.timestamp); hist_bytes(sh_hist, q.page); hist_bytes(sh_hist, q.value[4]);
-        }
-        if (!job.tail_clean) for (int c = RC_G + 12; c < RC_G + RC_L; c++) TR(c, row) = 0;
-    } else if (i < RC_REGION_STRIDE(capacity)) {
-        if (!job.tail_clean) zero_gap_row(job.trace, n_rows, (size_t)(SIDE == 0 ? RC_ROW_PU : RC_ROW_PS) * RC_REGION_STRIDE(capacity) + i);
-    }
-    hist_flush(sh_hist, job.hist);
-}
-
-// ------------------------------------------------------------------------------------------------
 // General rows A..D: one lane per cycle; every value is a function of item i, item i-1 and the
 // instance record (no carried state), so all cycles are independent.
 struct CycleCtx {
     bool can_pop;
     zkw_mem_query q, pq;   // this item, previous item (zeros when padding / FSM-in for cycle 0)
-    u64 eu[8], es[8];
+    u64 es[8];
     u64 p_val[5];          // es3..es6, v4 of the previous item
     u32 p_ptr;
 };
@@ -197,18 +141,17 @@ __device__ __forceinline__ void load_query(const zkw_mem_query* src, zkw_mem_que
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
-__device__ __forceinline__ void cycle_ctx(const SynthJob& job, u32 i, CycleCtx& c, bool want_eu) {
+__device__ __forceinline__ void cycle_ctx(const SynthJob& job, u32 i, CycleCtx& c) {
     const zkw_ram_instance* in = job.inst;
     const size_t first = in->first_item, m = in->num_items;
     c.can_pop = i < m;
     memset(&c.q, 0, sizeof c.q);
     memset(&c.pq, 0, sizeof c.pq);
 #pragma unroll
-    for (int k = 0; k < 8; k++) { c.eu[k] = 0; c.es[k] = 0; }
+    for (int k = 0; k < 8; k++) c.es[k] = 0;
     if (c.can_pop) {
         load_query(job.sorted_q + first + i, c.q);
         encode_mem_query(c.q, c.es);
-        if (want_eu) encode_raw_query(load_raw_query(job.unsorted_q + first + i), c.eu);
     }
     if (i == 0) {
         const zkw_ram_fsm& f = in->hidden_fsm_input;
@@ -230,89 +173,150 @@ __device__ __forceinline__ u64 acc_before(const u64* z, size_t first, size_t m, 
     return i == 0 ? fsm_in : z[first + (i - 1 < m ? i - 1 : m - 1)];
 }
 
-static __device__ __forceinline__ void k_ram_fill_A(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity, size_t n_rows) {
-    __shared__ u32 sh_hist[256];
-    sh_hist[threadIdx.x] = 0;
-    __syncthreads();
-    const SynthJob job = jobs[vb.y];
-    const u32 i = vb.x * blockDim.x + threadIdx.x;
-    const u64* lhs_z_all = job.lhs_z;
-    const u64* rhs_z_all = job.rhs_z;
-    const size_t n_total = job.n_block;
+// Rows A and B have no kernel of their own: the lane of k_ram_fill_poseidon that runs cycle i's permutation writes them too (A with
+// the unsorted side, B with the sorted side), from the query and the encodings it holds anyway. q = the sorted item of cycle i,
+// eu / es = the encodings of the unsorted / sorted item; all zeros in a cycle that pops nothing.
+__device__ __forceinline__ void fill_row_A(const SynthJob& job, u32 i, u32 capacity, size_t n_rows, const zkw_mem_query& q,
+                                           const u64 eu[8], const u64 es[8], u32* sh_hist) {
+    u64* trace = job.trace;
+    const size_t row = (size_t)RC_ROW_A * RC_REGION_STRIDE(capacity) + i;
     if (i < capacity) {
-        u64* trace = job.trace;
         const zkw_ram_instance* in = job.inst;
-        const size_t first = in->first_item, m = in->num_items, row = (size_t)RC_ROW_A * RC_REGION_STRIDE(capacity) + i;
-        CycleCtx c;
-        cycle_ctx(job, i, c, true);
-        const u64 rw = c.q.rw_flag ? 1 : 0, ptr = c.q.value_is_pointer ? 1 : 0;
+        const size_t first = in->first_item, m = in->num_items, n_total = job.n_block;
+        const bool can_pop = i < m;
+        const u64 rw = q.rw_flag ? 1 : 0, ptr = q.value_is_pointer ? 1 : 0;
 #pragma unroll
-        for (int k = 0; k < 8; k++) { TR(RC_A_eu0 + k, row) = c.eu[k]; TR(RC_A_ts + k, row) = c.es[k]; }
+        for (int k = 0; k < 8; k++) { TR(RC_A_eu0 + k, row) = eu[k]; TR(RC_A_ts + k, row) = es[k]; }
         for (int r = 0; r < 2; r++) {
             const u64* ch = job.challenges + 9 * r;
             u64 lc = ch[8], rc = ch[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                lc = gl::add(lc, gl::mul(c.eu[k], ch[k]));
-                rc = gl::add(rc, gl::mul(c.es[k], ch[k]));
+                lc = gl::add(lc, gl::mul(eu[k], ch[k]));
+                rc = gl::add(rc, gl::mul(es[k], ch[k]));
+                __builtin_amdgcn_sched_barrier(0);  // two products in flight, not 32: their carries live in SGPR pairs (as P2_SBOX_GROUP)
             }
-            const u64 pl = acc_before(lhs_z_all + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.lhs_accumulator[r]);
-            const u64 pr = acc_before(rhs_z_all + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.rhs_accumulator[r]);
+            const u64 pl = acc_before(job.lhs_z + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.lhs_accumulator[r]);
+            const u64 pr = acc_before(job.rhs_z + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.rhs_accumulator[r]);
             const u64 nl = gl::canon(gl::mul(pl, lc)), nr = gl::canon(gl::mul(pr, rc));
             const int o = r * (RC_A_lc1 - RC_A_lc0);
 #pragma unroll
             for (int k = 1; k < 9; k++) TR(RC_A_G_c0_1 + (k - 1) + r * (RC_A_G_c1_1 - RC_A_G_c0_1), row) = ch[k];
+            __builtin_amdgcn_sched_barrier(0);
             TR(RC_A_lc0 + o, row) = gl::canon(lc); TR(RC_A_P_lhs0 + o, row) = pl; TR(RC_A_nl0 + o, row) = nl;
-            TR(RC_A_lhs0 + o, row) = c.can_pop ? nl : pl;
+            TR(RC_A_lhs0 + o, row) = can_pop ? nl : pl;
             TR(RC_A_rc0 + o, row) = gl::canon(rc); TR(RC_A_P_rhs0 + o, row) = pr; TR(RC_A_nr0 + o, row) = nr;
-            TR(RC_A_rhs0 + o, row) = c.can_pop ? nr : pr;
+            TR(RC_A_rhs0 + o, row) = can_pop ? nr : pr;
+            __builtin_amdgcn_sched_barrier(0);
         }
-        TR(RC_A_rw, row) = rw; TR(RC_A_ptr, row) = ptr; TR(RC_A_idx, row) = c.q.index;
-        TR(RC_A_v2, row) = c.q.value[2]; TR(RC_A_v3, row) = c.q.value[3]; TR(RC_A_v0, row) = c.q.value[0];
-        TR(RC_A_v5_b3c, row) = c.q.value[5] >> 24; TR(RC_A_can_pop, row) = c.can_pop ? 1 : 0;
-        put_bytes(trace, n_rows, row, RC_A_v2_b0, c.q.value[2]);
-        put_bytes(trace, n_rows, row, RC_A_v3_b0, c.q.value[3]);
-        put_bytes(trace, n_rows, row, RC_A_v5_b0, c.q.value[5]);
-        hist_bytes(sh_hist, c.q.value[2]); hist_bytes(sh_hist, c.q.value[3]); hist_bytes(sh_hist, c.q.value[5]);
+        TR(RC_A_rw, row) = rw; TR(RC_A_ptr, row) = ptr; TR(RC_A_idx, row) = q.index;
+        TR(RC_A_v2, row) = q.value[2]; TR(RC_A_v3, row) = q.value[3]; TR(RC_A_v0, row) = q.value[0];
+        TR(RC_A_v5_b3c, row) = q.value[5] >> 24; TR(RC_A_can_pop, row) = can_pop ? 1 : 0;
+        put_bytes(trace, n_rows, row, RC_A_v2_b0, q.value[2]);
+        put_bytes(trace, n_rows, row, RC_A_v3_b0, q.value[3]);
+        put_bytes(trace, n_rows, row, RC_A_v5_b0, q.value[5]);
+        hist_bytes(sh_hist, q.value[2]); hist_bytes(sh_hist, q.value[3]); hist_bytes(sh_hist, q.value[5]);
         constexpr int NA = ROW_SLOTS[RC_ROW_A];  // general slots used by row type A
         if (!job.tail_clean) {
             for (int col = NA; col < RC_G; col++) TR(col, row) = 0;
             for (int col = RC_G + 12; col < RC_G + RC_L; col++) TR(col, row) = 0;
         }
     } else if (i < RC_REGION_STRIDE(capacity)) {
-        if (!job.tail_clean) zero_gap_row(job.trace, n_rows, (size_t)RC_ROW_A * RC_REGION_STRIDE(capacity) + i);
+        if (!job.tail_clean) zero_gap_row(trace, n_rows, row);
     }
-    hist_flush(sh_hist, job.hist);
 }
 
-static __device__ __forceinline__ void k_ram_fill_B(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity, size_t n_rows) {
-    __shared__ u32 sh_hist[256];
-    sh_hist[threadIdx.x] = 0;
-    __syncthreads();
-    const SynthJob job = jobs[vb.y];
-    const u32 i = vb.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void fill_row_B(const SynthJob& job, u32 i, u32 capacity, size_t n_rows, const zkw_mem_query& q,
+                                           const u64 es[8], u32* sh_hist) {
+    u64* trace = job.trace;
+    const size_t row = (size_t)RC_ROW_B * RC_REGION_STRIDE(capacity) + i;
     if (i < capacity) {
-        u64* trace = job.trace;
-        const size_t row = (size_t)RC_ROW_B * RC_REGION_STRIDE(capacity) + i;
-        CycleCtx c;
-        cycle_ctx(job, i, c, false);
-        put_bytes(trace, n_rows, row, RC_B_v6_b0, c.q.value[6]);
-        put_bytes(trace, n_rows, row, RC_B_v7_b0, c.q.value[7]);
-        TR(RC_B_es4, row) = c.es[4]; TR(RC_B_v1, row) = c.q.value[1]; TR(RC_B_v5_b3c, row) = c.q.value[5] >> 24;
-        TR(RC_B_es5, row) = c.es[5]; TR(RC_B_v2, row) = c.q.value[2];
-        TR(RC_B_es6, row) = c.es[6]; TR(RC_B_v3, row) = c.q.value[3];
-        const u32 d0 = c.q.timestamp - c.pq.timestamp;
+        const zkw_ram_instance* in = job.inst;
+        // timestamp of the previous sorted item: the FSM input at cycle 0, zero once the previous cycle popped nothing
+        u32 p_ts = 0;
+        if (i == 0) p_ts = in->hidden_fsm_input.previous_sorting_key[0];
+        else if (i - 1 < in->num_items) p_ts = job.sorted_q[in->first_item + i - 1].timestamp;
+        put_bytes(trace, n_rows, row, RC_B_v6_b0, q.value[6]);
+        put_bytes(trace, n_rows, row, RC_B_v7_b0, q.value[7]);
+        TR(RC_B_es4, row) = es[4]; TR(RC_B_v1, row) = q.value[1]; TR(RC_B_v5_b3c, row) = q.value[5] >> 24;
+        TR(RC_B_es5, row) = es[5]; TR(RC_B_v2, row) = q.value[2];
+        TR(RC_B_es6, row) = es[6]; TR(RC_B_v3, row) = q.value[3];
+        const u32 d0 = q.timestamp - p_ts;
         TR(RC_B_d0, row) = d0; put_bytes(trace, n_rows, row, RC_B_d0_b0, d0);
-        TR(RC_B_bw0, row) = c.q.timestamp < c.pq.timestamp ? 1 : 0;
-        TR(RC_B_ts, row) = c.q.timestamp; TR(RC_B_P_ts, row) = c.pq.timestamp;
-        hist_bytes(sh_hist, c.q.value[6]); hist_bytes(sh_hist, c.q.value[7]); hist_bytes(sh_hist, d0);
+        TR(RC_B_bw0, row) = q.timestamp < p_ts ? 1 : 0;
+        TR(RC_B_ts, row) = q.timestamp; TR(RC_B_P_ts, row) = p_ts;
+        hist_bytes(sh_hist, q.value[6]); hist_bytes(sh_hist, q.value[7]); hist_bytes(sh_hist, d0);
         constexpr int NB = ROW_SLOTS[RC_ROW_B];
         if (!job.tail_clean) {
             for (int col = NB; col < RC_G; col++) TR(col, row) = 0;
             for (int col = RC_G + 12; col < RC_G + RC_L; col++) TR(col, row) = 0;
         }
     } else if (i < RC_REGION_STRIDE(capacity)) {
-        if (!job.tail_clean) zero_gap_row(job.trace, n_rows, (size_t)RC_ROW_B * RC_REGION_STRIDE(capacity) + i);
+        if (!job.tail_clean) zero_gap_row(trace, n_rows, row);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Poseidon2 rows (regions PU and PS) and the general row that shares their inputs (A with PU, B with PS): one lane per cycle
+// stores the fused row and the Poseidon2 row's spare and lookup cells, then runs the permutation and stores all 130
+// flattened-gate variables as it goes. SIDE 0 = unsorted queue, 1 = sorted queue. The general row goes FIRST: the query and
+// its encodings are dead when the permutation starts (its 92 registers are the kernel's peak, 5 waves per SIMD), and the
+// row's stores drain under the permutation's arithmetic.
+template <int SIDE>
+static __device__ __forceinline__ void k_ram_fill_poseidon(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity,
+                                                          size_t n_rows) {
+    __shared__ u32 sh_hist[256];
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) sh_hist[t] = 0;
+    __syncthreads();
+    const SynthJob job = jobs[vb.y];
+    const u32 i = vb.x * blockDim.x + threadIdx.x;
+    u64* trace = job.trace;
+    const zkw_ram_instance* in = job.inst;
+    const size_t first = in->first_item, m = in->num_items;
+    const bool can_pop = i < capacity && i < m;
+    const size_t row = (size_t)(SIDE == 0 ? RC_ROW_PU : RC_ROW_PS) * RC_REGION_STRIDE(capacity) + i;
+    zkw_mem_query q;  // the sorted item of this cycle
+    memset(&q, 0, sizeof q);
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 8; k++) s[k] = 0;
+    if (can_pop) {
+        load_query(job.sorted_q + first + i, q);
+        if (SIDE == 0) encode_raw_query(load_raw_query(job.unsorted_q + first + i), s); else encode_mem_query(q, s);
+    }
+    if (SIDE == 0) {
+        u64 es[8];
+        encode_mem_query(q, es);
+        fill_row_A(job, i, capacity, n_rows, q, s, es, sh_hist);
+    } else {
+        fill_row_B(job, i, capacity, n_rows, q, s, sh_hist);
+    }
+    if (i < capacity) {
+        // spare general slots + lookup cells of this row type
+        if (SIDE == 0) {
+            TR(RC_PU_idx, row) = q.index; TR(RC_PU_v0, row) = q.value[0]; TR(RC_PU_v1, row) = q.value[1];
+            put_bytes(trace, n_rows, row, RC_PU_idx_b0, q.index);
+            put_bytes(trace, n_rows, row, RC_PU_v0_b0, q.value[0]);
+            put_bytes(trace, n_rows, row, RC_PU_v1_b0, q.value[1]);
+            hist_bytes(sh_hist, q.index); hist_bytes(sh_hist, q.value[0]); hist_bytes(sh_hist, q.value[1]);
+        } else {
+            if (!job.tail_clean) for (int c = 130; c < RC_G; c++) TR(c, row) = 0;
+            put_bytes(trace, n_rows, row, RC_PS_ts_b0, q.timestamp);
+            put_bytes(trace, n_rows, row, RC_PS_page_b0, q.page);
+            put_bytes(trace, n_rows, row, RC_PS_v4_b0, q.value[4]);
+            hist_bytes(sh_hist, q.timestamp); hist_bytes(sh_hist, q.page); hist_bytes(sh_hist, q.value[4]);
+        }
+        if (!job.tail_clean) for (int c = RC_G + 12; c < RC_G + RC_L; c++) TR(c, row) = 0;
+        __builtin_amdgcn_sched_barrier(0);  // nothing of the rows above moves into the permutation, where every register counts
+        const RegsIn ri = regs_in(in);
+        // capacity part of the queue head entering this cycle
+        const u64* caps = SIDE == 0 ? job.unsorted_caps : job.sorted_caps;
+        const u64* prev_cap = i == 0 ? (SIDE == 0 ? ri.uh : ri.sh) + 8 : caps + 4 * (first + (i - 1 < m ? i - 1 : m - 1));
+#pragma unroll
+        for (int k = 0; k < 4; k++) s[8 + k] = prev_cap[k];
+        fill_flattened_poseidon(trace, n_rows, row, s);
+    } else if (i < RC_REGION_STRIDE(capacity)) {
+        if (!job.tail_clean) zero_gap_row(trace, n_rows, row);
     }
     hist_flush(sh_hist, job.hist);
 }
@@ -369,7 +373,7 @@ static __device__ __forceinline__ void k_ram_fill_C(const VB& vb, const SynthJob
     c.can_pop = false;
     bool nd = false;
     if (live) {
-        cycle_ctx(job, i, c, false);
+        cycle_ctx(job, i, c);
         nd = nd_flag(c.can_pop, c.q);
     }
     // exclusive count of nd flags before this lane inside the block (tile)

@@ -1704,14 +1704,11 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     ZKW_TRY(launch_check("k_ram_nd_tiles"));
     { Prof _p(ctx, "k_ram_nd_scan"); ZKW_LAUNCH(ctx, k_ram_nd_scan, nj, 64, d_jobs, (int)nj, n_tiles); }
     ZKW_TRY(launch_check("k_ram_nd_scan"));
+    // <0> fills the PU rows and row A, <1> the PS rows and row B (one lane per cycle writes both)
     { Prof _p(ctx, "k_ram_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ram_fill_poseidon<0>), "k_ram_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
     ZKW_TRY(launch_check("k_ram_fill_poseidon<0>"));
     { Prof _p(ctx, "k_ram_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ram_fill_poseidon<1>), "k_ram_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
     ZKW_TRY(launch_check("k_ram_fill_poseidon<1>"));
-    { Prof _p(ctx, "k_ram_fill_A"); ZKW_LAUNCH_D(ctx, (k_ram_fill_A), "k_ram_fill_A", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_A"));
-    { Prof _p(ctx, "k_ram_fill_B"); ZKW_LAUNCH_D(ctx, (k_ram_fill_B), "k_ram_fill_B", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_B"));
     { Prof _p(ctx, "k_ram_fill_C"); ZKW_LAUNCH_D(ctx, (k_ram_fill_C), "k_ram_fill_C", g256, 256, 0, d_jobs, capacity, n_rows); }
     ZKW_TRY(launch_check("k_ram_fill_C"));
     { Prof _p(ctx, "k_ram_fill_D"); const unsigned d_tiles = (unsigned)((rstride + RC_D_TILES * 256 - 1) / (RC_D_TILES * 256));  // row D: RC_D_TILES tiles per block (they share one inversion per lane)
