@@ -5,7 +5,9 @@ src/witness/postprocessing/mod.rs:353-405). Everything heavy is a libzkw call on
 
 Not covered: the MainVM instances themselves (they need the VM) and the storage application (it needs the
 pre-block Merkle paths of the storage tree from a `BlockchainDataSource`; call
-`Context.decompose_into_storage_application_witnesses` on `artifacts["storage_sorter"]` results with them).
+`Context.decompose_into_storage_application_witnesses` on `artifacts["storage_sorter"]` results with them). Inside the
+library the paths come from a tree in HBM instead: `native.Block(storage_tree_device=...)` takes a full `StorageTreeDevice` or
+a witness tree (`StorageTreeDevice.from_proofs` for paths a node supplied, `.extract_witness` for consecutive blocks).
 """
 import numpy as np
 

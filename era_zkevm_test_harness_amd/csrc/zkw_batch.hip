@@ -150,7 +150,9 @@ struct zkw_batch {
     std::string flush_err;
     // statistics (ZKW_BATCH_LOG=1)
     size_t n_flushes = 0, n_launches = 0, n_jobs = 0, n_chain_launches = 0, n_switches = 0;
+    std::map<std::string, std::pair<size_t, size_t>> per_kernel;  // kernel name -> (merged launches, jobs they carried)
     double flush_host_ms = 0, wait_ms = 0;
+    const bool log_kernels = getenv("ZKW_BATCH_LOG") != nullptr;
 
     hipEvent_t event() {
         hipEvent_t e = nullptr;
@@ -340,6 +342,11 @@ bool zkw_batch::flush() {
             fail_flush(hipLaunchKernel(m.k->multi_fn, dim3(m.total), dim3(m.k->bs), args, m.lds, main), m.k->name);
             n_launches++;
             n_jobs += m.jobs.size();
+            if (log_kernels) {
+                auto& pk = per_kernel[m.k->name];
+                pk.first++;
+                pk.second += m.jobs.size();
+            }
         }
         ChainGroup& c = R.chain;
         if (c.owners.empty()) continue;
@@ -394,6 +401,7 @@ int zkw_batch::run(const std::vector<std::function<int()>>& roots) {
     zkw_batch* outer = tl_batch;
     tl_batch = this;
     n_flushes = n_launches = n_jobs = n_chain_launches = n_switches = 0;
+    per_kernel.clear();
     flush_host_ms = wait_ms = 0;
     for (auto& r : roots)
         if (make_fiber(this, r) < 0) {
@@ -496,6 +504,8 @@ int zkw_batch::run(const std::vector<std::function<int()>>& roots) {
     if (getenv("ZKW_BATCH_LOG"))
         fprintf(stderr, "[zkw batch] %zu fibers, %zu flushes, %zu merged launches carrying %zu jobs, %zu chain launches, %zu switches; host %.1f ms in flushes, %.1f ms waiting\n",
                 fibers.size(), n_flushes, n_launches, n_jobs, n_chain_launches, n_switches, flush_host_ms, wait_ms);
+    if (log_kernels)  // K blocks of one shape: a kernel whose launches merge shows jobs = K x launches
+        for (const auto& pk : per_kernel) fprintf(stderr, "[zkw batch]   %s: %zu merged launches carrying %zu jobs\n", pk.first.c_str(), pk.second.first, pk.second.second);
     fibers.clear();
     if (first_rc != ZKW_OK) return fail(first_rc, "%s", first_err.c_str());
     return ZKW_OK;

@@ -244,6 +244,24 @@ Branch start_branch(zkw_block* B, F f) {
     return b;
 }
 
+// the storage branch's failure when the block's witness tree has no entry for deduplicated query `pos`
+Status missing_in_witness_tree(zkw_block* B, const zkw_log_query* d_rq, size_t pos) {
+    zkw_log_query q;
+    ST_TRY(B->xf[X_STO].d2h(&q, d_rq + pos, sizeof q));
+    auto hex = [](const uint32_t* words, int n) {  // a big number of n little-endian words
+        std::string h = "0x";
+        char w[9];
+        for (int k = n - 1; k >= 0; k--) { snprintf(w, sizeof w, "%08x", words[k]); h += w; }
+        return h;
+    };
+    const std::string text = "storage_tree_device is a witness tree without an entry for deduplicated storage query " + std::to_string(pos) +
+                             " (address " + hex(q.address, 5) + ", key " + hex(q.key, 8) + ")";
+    Status s;
+    s.rc = ZKW_ERR_INVALID;
+    s.msg = text;
+    return s;
+}
+
 // ---- branch: log demuxer, then the three sorters (each on its own thread) --------------------------------------
 Status storage_branch(zkw_block* B, const zkw_block_inputs* in, const zkw_log_query* d_q, size_t n) {
     ST_HIP(hipSetDevice(B->device));
@@ -261,16 +279,29 @@ Status storage_branch(zkw_block* B, const zkw_block_inputs* in, const zkw_log_qu
         uint64_t* d_idx = nullptr;
         uint8_t* d_paths = nullptr;
         uint8_t root[32];
+        uint32_t* d_missing = nullptr;  // a witness tree only: the word its lookup raises for a query it has no entry for
         if (nr) {
             ST_TRY(B->alloc(&d_idx, nr));
             ST_TRY(B->alloc(&d_paths, nr * 256 * 32));
-            ST_ZKW(zkw_storage_tree_answer_queries(tree, B->ctx[C_STO], d_rq, nr, d_idx, d_paths));
+            if (zkw_storage_tree_is_witness(tree)) {
+                ST_TRY(B->alloc(&d_missing, 1));
+                ST_ZKW(zkw_storage_tree_answer_queries_flagged(tree, B->ctx[C_STO], d_rq, nr, d_idx, d_paths, d_missing));
+            } else {
+                ST_ZKW(zkw_storage_tree_answer_queries(tree, B->ctx[C_STO], d_rq, nr, d_idx, d_paths));
+            }
         }
         ST_ZKW(zkw_storage_tree_root(tree, root));
-        ST_ZKW(zkw_storage_application_build(B->ctx[C_STO], d_rq, d_rt, nr, d_idx, d_paths, root, zkw_storage_tree_next_enumeration_index(tree),
-                                             B->cap[T_SAP], &B->sap));
-        ST_ZKW(zkw_synchronize(B->ctx[C_STO]));
-        return Status();
+        // (the builder checks every pre-state proof against the root: with a witness tree, a proof it refuses may be the sentinel of a slot the
+        // table does not hold, and the block's error then says so)
+        const Status built = from_rc(zkw_storage_application_build(B->ctx[C_STO], d_rq, d_rt, nr, d_idx, d_paths, root,
+                                                                   zkw_storage_tree_next_enumeration_index(tree), B->cap[T_SAP], &B->sap));
+        if (built.ok() || d_missing) ST_ZKW(zkw_synchronize(B->ctx[C_STO]));
+        if (d_missing) {
+            uint32_t missing = 0;
+            ST_TRY(B->xf[X_STO].d2h(&missing, d_missing, sizeof missing));
+            if (missing) return missing_in_witness_tree(B, d_rq, nr - missing);
+        }
+        return built;
     }
     std::vector<zkw_log_query> hq(nr);
     std::vector<uint64_t> idx(nr);

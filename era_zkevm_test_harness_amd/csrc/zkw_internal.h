@@ -28,3 +28,8 @@ struct zkw_storage_tree;
 struct zkw_log_query;
 int zkw_storage_tree_device(const zkw_storage_tree* t);
 int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_query* d_queries, size_t n);
+// zkw_storage_tree_answer_queries with the flag word a WITNESS tree's lookup raises (storage_witness_kernels.cuh, k_sw_lookup): d_missing is
+// one word of device memory the caller owns; it is zeroed ahead of the lookup, and afterwards 0 = every key was in the table, else the
+// first query without an entry is at position n - *d_missing. A full tree answers every key: the word stays 0.
+int zkw_storage_tree_answer_queries_flagged(const zkw_storage_tree* t, zkw_ctx* ctx, const zkw_log_query* queries, size_t n, uint64_t* leaf_indexes,
+                                            uint8_t* merkle_paths, uint32_t* d_missing);

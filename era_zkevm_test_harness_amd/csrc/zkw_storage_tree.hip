@@ -2,8 +2,10 @@
 // (src/external_calls.rs:81, src/witness/tree/mod.rs:42-99) as a structure of the library, resident in HBM. Kernels and the layout:
 // storage_tree_kernels.cuh. Every call that changes the tree ends with the new root on the host (one small readback), so a call that
 // only reads — zkw_storage_tree_answer_queries from the storage branch of any number of blocks — needs no ordering with the tree's stream.
+// A WITNESS tree (storage_witness_kernels.cuh) is the same handle with `witness` set: a sorted table of get_leaf answers for one state,
+// built once (zkw_storage_tree_create_witness / _extract_witness), read like a tree, never changed.
 #include "zkw_ctx.h"
-#include "storage_tree_kernels.cuh"
+#include "storage_witness_kernels.cuh"
 #include "radix_sort.cuh"
 #include "scan_kernels.cuh"
 
@@ -18,12 +20,17 @@ struct zkw_storage_tree {
     int cur = 0;
     u32 *nodes = nullptr, *empty = nullptr, *d = nullptr, *nxt = nullptr, *root_dev = nullptr;
     uint8_t root[32] = {}, empty_root[32] = {};
+    // a witness tree: keys[0] / index[0] / values[0] are the table's sorted entries (cap of them, n with a nonzero index) and `paths` their
+    // Merkle paths; nothing else is allocated
+    bool witness = false;
+    u32* paths = nullptr;
     void release() {
-        void* ptrs[] = {keys[0], keys[1], index[0], index[1], values[0], values[1], nodes, empty, d, nxt, root_dev};
+        void* ptrs[] = {keys[0], keys[1], index[0], index[1], values[0], values[1], nodes, empty, d, nxt, root_dev, paths};
         for (void* p : ptrs)
             if (p) dev_free(p);
     }
     StView view() const { return StView{keys[cur], index[cur], values[cur], nodes, empty, (u64)n, (u64)cap}; }
+    SwView table() const { return SwView{keys[0], index[0], values[0], paths, (u64)cap}; }
 };
 
 // bytes of HBM per leaf of capacity: the nodes (256 x 32), two sides of key / index / value (2 x 72), d and nxt (2 x 4)
@@ -88,11 +95,13 @@ extern "C" int zkw_storage_tree_root(const zkw_storage_tree* t, uint8_t out[32])
 extern "C" uint64_t zkw_storage_tree_next_enumeration_index(const zkw_storage_tree* t) { return t ? t->next_index : 0; }
 extern "C" int zkw_storage_tree_set_next_enumeration_index(zkw_storage_tree* t, uint64_t next) {
     if (!t || next == 0) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_set_next_enumeration_index: bad argument (index 0 is the empty leaf's)");
+    if (t->witness) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_set_next_enumeration_index: a witness tree does not change");
     t->next_index = next;
     return ZKW_OK;
 }
 extern "C" size_t zkw_storage_tree_num_leaves(const zkw_storage_tree* t) { return t ? t->n : 0; }
 extern "C" size_t zkw_storage_tree_capacity(const zkw_storage_tree* t) { return t ? t->cap : 0; }
+extern "C" int zkw_storage_tree_is_witness(const zkw_storage_tree* t) { return t && t->witness; }
 int zkw_storage_tree_device(const zkw_storage_tree* t) { return t ? t->ctx->device : -1; }
 
 // every height over the leaves of side `cur`, then the root to the host
@@ -120,13 +129,10 @@ static int st_rebuild(zkw_storage_tree* t) {
     return ctx->read_small(t->root, t->root_dev, 32);
 }
 
-// m pairs in device memory, inserted one after another in array order (insert_many_leafs, tree/mod.rs:65-81)
-static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d_values, size_t m) {
-    zkw_ctx* ctx = t->ctx;
-    if (m == 0) return ZKW_OK;
-    const size_t N = t->n + m;
-    if (N >= (1ull << 32) - 1) return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves and %zu pairs are more than one insert sorts", t->n, m);
-    u32 *perm0 = nullptr, *perm1 = nullptr, *new_first = nullptr, *new_rank = nullptr, *heads = nullptr;
+// the stable sort by key of the N entries of `g` (the tree's leaves, then a batch): four passes of 64 bits, least significant first, over
+// a permutation. *perm = the scratch buffer that holds the result.
+static int st_sort_merged(zkw_ctx* ctx, const StMerge& g, size_t N, const u32** perm) {
+    u32 *perm0 = nullptr, *perm1 = nullptr;
     u64 *k64a = nullptr, *k64b = nullptr;
     void* tmp = nullptr;
     const size_t tmp_bytes = radix_temp_bytes(N);
@@ -135,13 +141,7 @@ static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d
     ZKW_TRY(ctx->scratch_t<u64>("st_k64a", N, &k64a));
     ZKW_TRY(ctx->scratch_t<u64>("st_k64b", N, &k64b));
     ZKW_TRY(ctx->scratch("st_sort_tmp", tmp_bytes + 256, &tmp));
-    ZKW_TRY(ctx->scratch_t<u32>("st_new_first", m, &new_first));
-    ZKW_TRY(ctx->scratch_t<u32>("st_new_rank", m + 1, &new_rank));
-    ZKW_TRY(ctx->scratch_t<u32>("st_heads", N + 1, &heads));
-    const int cur = t->cur, oth = cur ^ 1;
-    StMerge g{t->keys[cur], t->index[cur], t->values[cur], d_keys, d_values, (u64)t->n, (u64)m, t->next_index};
     const unsigned grid = blocks_for(N, 256);
-    // the stable sort by key: four passes of 64 bits, least significant first
     { Prof _p(ctx, "k_st_iota"); ZKW_LAUNCH(ctx, k_st_iota, grid, 256, perm0, (u64)N); }
     ZKW_TRY(launch_check("k_st_iota"));
     u32 *pc = perm0, *pn = perm1;
@@ -151,8 +151,29 @@ static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, pc, pn, N, 64)); }
         u32* x = pc; pc = pn; pn = x;
     }
+    *perm = pc;
+    return ZKW_OK;
+}
+// a bare key set as the "batch" of an empty tree
+static StMerge st_keys_only(const u32* d_keys, size_t n) { return StMerge{nullptr, nullptr, nullptr, d_keys, nullptr, 0, (u64)n, 0}; }
+
+// m pairs in device memory, inserted one after another in array order (insert_many_leafs, tree/mod.rs:65-81)
+static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d_values, size_t m) {
+    zkw_ctx* ctx = t->ctx;
+    if (m == 0) return ZKW_OK;
+    const size_t N = t->n + m;
+    if (N >= (1ull << 32) - 1) return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves and %zu pairs are more than one insert sorts", t->n, m);
+    u32 *new_first = nullptr, *new_rank = nullptr, *heads = nullptr;
+    ZKW_TRY(ctx->scratch_t<u32>("st_new_first", m, &new_first));
+    ZKW_TRY(ctx->scratch_t<u32>("st_new_rank", m + 1, &new_rank));
+    ZKW_TRY(ctx->scratch_t<u32>("st_heads", N + 1, &heads));
+    const int cur = t->cur, oth = cur ^ 1;
+    StMerge g{t->keys[cur], t->index[cur], t->values[cur], d_keys, d_values, (u64)t->n, (u64)m, t->next_index};
+    const unsigned grid = blocks_for(N, 256);
+    const u32* pc = nullptr;
+    ZKW_TRY(st_sort_merged(ctx, g, N, &pc));
     // which batch entries bring a new leaf, and their ranks in array order
-    { Prof _p(ctx, "k_st_mark"); ZKW_LAUNCH(ctx, k_st_mark, grid, 256, g, (const u32*)pc, (u64)N, new_first); }
+    { Prof _p(ctx, "k_st_mark"); ZKW_LAUNCH(ctx, k_st_mark, grid, 256, g, pc, (u64)N, new_first); }
     ZKW_TRY(launch_check("k_st_mark"));
     ZKW_TRY(flag_prefix(ctx, "k_st_new_rank", StArrayFlag{new_first}, m, new_rank));
     u32 n_new = 0;
@@ -160,7 +181,7 @@ static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d
     if (t->n + n_new > t->cap)  // nothing of the tree has been written yet
         return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves + %u new ones exceed the capacity of %zu", t->n, n_new, t->cap);
     ZKW_TRY(flag_prefix(ctx, "k_st_heads", StHeadFlag{g, pc}, N, heads));
-    { Prof _p(ctx, "k_st_emit"); ZKW_LAUNCH(ctx, k_st_emit, grid, 256, g, (const u32*)pc, (u64)N, (const u32*)heads, (const u32*)new_rank, t->keys[oth], t->index[oth], t->values[oth]); }
+    { Prof _p(ctx, "k_st_emit"); ZKW_LAUNCH(ctx, k_st_emit, grid, 256, g, pc, (u64)N, (const u32*)heads, (const u32*)new_rank, t->keys[oth], t->index[oth], t->values[oth]); }
     ZKW_TRY(launch_check("k_st_emit"));
     t->cur = oth;
     t->n += n_new;
@@ -170,6 +191,7 @@ static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d
 
 extern "C" int zkw_storage_tree_insert(zkw_storage_tree* t, const uint8_t* keys, const uint8_t* values, size_t n) {
     if (!t || (n && (!keys || !values))) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_insert: null argument");
+    if (t->witness) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_insert: a witness tree does not change");
     zkw_ctx* ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const uint8_t *d_k = nullptr, *d_v = nullptr;
@@ -178,7 +200,12 @@ extern "C" int zkw_storage_tree_insert(zkw_storage_tree* t, const uint8_t* keys,
     return st_insert_device(t, reinterpret_cast<const u32*>(d_k), reinterpret_cast<const u32*>(d_v), n);
 }
 
-static int st_query(zkw_ctx* ctx, const zkw_storage_tree* t, const StQuery& q, size_t n) {
+// `missing`: the flag word of k_sw_lookup, or NULL; a full tree answers every key and leaves it alone
+static int st_query(zkw_ctx* ctx, const zkw_storage_tree* t, const StQuery& q, size_t n, u32* missing = nullptr) {
+    if (t->witness) {
+        { Prof _p(ctx, "k_sw_lookup"); ZKW_LAUNCH(ctx, k_sw_lookup, n, ST_DEPTH, t->table(), q, missing); }
+        return launch_check("k_sw_lookup");
+    }
     { Prof _p(ctx, "k_st_query"); ZKW_LAUNCH(ctx, k_st_query, n, ST_DEPTH, t->view(), q); }
     return launch_check("k_st_query");
 }
@@ -198,7 +225,16 @@ extern "C" int zkw_storage_tree_get_leaves(const zkw_storage_tree* t, const uint
     if (values) ZKW_TRY(ctx->out("st_q_values", values, n * 32, &d_val));
     if (merkle_paths) ZKW_TRY(ctx->out("st_q_paths", merkle_paths, n * ST_DEPTH * 32, &d_paths));
     StQuery q{nullptr, reinterpret_cast<const u32*>(d_k), d_idx, reinterpret_cast<u32*>(d_val), reinterpret_cast<u32*>(d_paths)};
-    ZKW_TRY(st_query(ctx, t, q, n));
+    if (t->witness) {  // a key outside the table is the caller's error (in device pointer mode the kernel has written the caller's buffers by then)
+        u32 *d_missing = nullptr, missing = 0;
+        ZKW_TRY(ctx->scratch_t<u32>("sw_missing", 1, &d_missing));
+        HIP_TRY(ctx->memset_async(d_missing, 0, sizeof(u32)));
+        ZKW_TRY(st_query(ctx, t, q, n, d_missing));
+        ZKW_TRY(ctx->read_small(&missing, d_missing, sizeof missing));
+        if (missing) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_get_leaves: the key at position %zu is not in the witness tree", n - missing);
+    } else {
+        ZKW_TRY(st_query(ctx, t, q, n));
+    }
     if (leaf_indexes) ZKW_TRY(ctx->finish_out(leaf_indexes, d_idx, n));
     if (values) ZKW_TRY(ctx->finish_out(values, d_val, n * 32));
     if (merkle_paths) ZKW_TRY(ctx->finish_out(merkle_paths, d_paths, n * ST_DEPTH * 32));
@@ -215,9 +251,22 @@ extern "C" int zkw_storage_tree_answer_queries(const zkw_storage_tree* t, zkw_ct
     return st_query(ctx, t, q, n);
 }
 
+// the same with the flag word of a witness tree's lookup (zkw_internal.h): d_missing is zeroed here, ahead of the lookup, on ctx's stream
+int zkw_storage_tree_answer_queries_flagged(const zkw_storage_tree* t, zkw_ctx* ctx, const zkw_log_query* queries, size_t n, uint64_t* leaf_indexes,
+                                            uint8_t* merkle_paths, uint32_t* d_missing) {
+    if (!t || !ctx || !d_missing || (n && !queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: null argument");
+    if (ctx->device != t->ctx->device) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: the tree lives on device %d, the context on device %d", t->ctx->device, ctx->device);
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_answer_queries: too many queries");
+    HIP_TRY(ctx->memset_async(d_missing, 0, sizeof(u32)));
+    if (n == 0) return ZKW_OK;
+    StQuery q{queries, nullptr, leaf_indexes, nullptr, reinterpret_cast<u32*>(merkle_paths)};
+    return st_query(ctx, t, q, n, d_missing);
+}
+
 // queries in DEVICE memory (zkw_internal.h: zkw_block_apply_storage hands over the block's own deduplicated queue)
 int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_query* d_queries, size_t n) {
     if (!t || (n && !d_queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: null argument");
+    if (t->witness) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: a witness tree does not change");
     if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: too many queries");
     zkw_ctx* ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -236,9 +285,137 @@ int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_que
 
 extern "C" int zkw_storage_tree_apply_queries(zkw_storage_tree* t, const zkw_log_query* queries, size_t n) {
     if (!t || (n && !queries)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: null argument");
+    if (t->witness) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_apply_queries: a witness tree does not change");
     zkw_ctx* ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const zkw_log_query* d_q = nullptr;
     ZKW_TRY(ctx->in("st_ap_queries", queries, n, &d_q));
     return zkw_storage_tree_apply_queries_device(t, d_q, n);
+}
+
+// ------------------------------------------------------------------------------------------------ witness trees
+// an empty table for up to `entries` entries on ctx (not yet retained: the caller does that once the table is complete)
+static int sw_alloc(zkw_ctx* ctx, size_t entries, const char* who, zkw_storage_tree** out) {
+    zkw_storage_tree* t = new zkw_storage_tree();
+    t->ctx = ctx;
+    t->witness = true;
+    t->cap = entries;
+    hipError_t e = dev_malloc(&t->keys[0], entries * 32 + 64);
+    if (e == hipSuccess) e = dev_malloc(&t->index[0], entries * 8 + 64);
+    if (e == hipSuccess) e = dev_malloc(&t->values[0], entries * 32 + 64);
+    if (e == hipSuccess) e = dev_malloc(&t->paths, entries * (size_t)ST_DEPTH * 32 + 64);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        t->release();
+        delete t;
+        return fail(ZKW_ERR_OOM, "%s: %zu entries need %zu bytes of device memory: %s", who, entries, entries * (size_t)(ST_DEPTH * 32 + 72), hipGetErrorString(e));
+    }
+    *out = t;
+    return ZKW_OK;
+}
+static int sw_drop(zkw_storage_tree* t, int rc) {
+    (void)t->ctx->sync_stream();  // nothing queued may still write the table
+    t->release();
+    delete t;
+    return rc;
+}
+
+static const char* sw_reason(u32 status) {
+    if (status & SW_BAD_INDEX) return "its leaf index is not below the next enumeration index";
+    if (status & SW_BAD_EMPTY) return "index 0 (an absent key) with a nonzero value";
+    if (status & SW_BAD_ROOT) return "its Merkle path does not lead to the root";
+    return "its key repeats an earlier entry's";
+}
+
+extern "C" int zkw_storage_tree_create_witness(zkw_ctx* ctx, const uint8_t* keys, const uint64_t* leaf_indexes, const uint8_t* values,
+                                               const uint8_t* merkle_paths, size_t n, const uint8_t root[32], uint64_t next_enumeration_index,
+                                               zkw_storage_tree** out) {
+    if (!ctx || !out || !root || (n && (!keys || !leaf_indexes || !values || !merkle_paths)))
+        return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: null argument");
+    if (next_enumeration_index == 0) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: the next enumeration index is at least 1 (index 0 is the empty leaf's)");
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: at most 2^31 - 1 entries");
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: the context belongs to a batch of blocks");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    const uint8_t *d_k = nullptr, *d_v = nullptr, *d_p = nullptr;
+    const uint64_t* d_i = nullptr;
+    ZKW_TRY(ctx->in("sw_in_keys", keys, n * 32, &d_k));
+    ZKW_TRY(ctx->in("sw_in_index", leaf_indexes, n, &d_i));
+    ZKW_TRY(ctx->in("sw_in_values", values, n * 32, &d_v));
+    ZKW_TRY(ctx->in("sw_in_paths", merkle_paths, n * (size_t)ST_DEPTH * 32, &d_p));
+    u32 *status = nullptr, *meta = nullptr;  // meta[0] = the first bad entry, meta[1] = entries with a nonzero index
+    ZKW_TRY(ctx->scratch_t<u32>("sw_status", n + 1, &status));
+    ZKW_TRY(ctx->scratch_t<u32>("sw_meta", 2, &meta));
+    zkw_storage_tree* t = nullptr;
+    ZKW_TRY(sw_alloc(ctx, n, "zkw_storage_tree_create_witness", &t));
+    memcpy(t->root, root, 32);
+    t->next_index = next_enumeration_index;
+    u32 h_meta[2] = {~0u, 0};
+    int rc = [&]() -> int {
+        HIP_TRY(ctx->memset_async(meta, 0xFF, sizeof(u32)));
+        HIP_TRY(ctx->memset_async(meta + 1, 0, sizeof(u32)));
+        if (n == 0) return ZKW_OK;
+        SwEntries e{reinterpret_cast<const u32*>(d_k), d_i, reinterpret_cast<const u32*>(d_v), reinterpret_cast<const u32*>(d_p), (u64)n, next_enumeration_index, {}};
+        memcpy(e.root, root, 32);
+        { Prof _p(ctx, "k_sw_verify"); ZKW_LAUNCH(ctx, k_sw_verify, blocks_for(n, 64), 64, e, status, meta); }
+        const u32* perm = nullptr;
+        ZKW_TRY(st_sort_merged(ctx, st_keys_only(e.keys, n), n, &perm));
+        { Prof _p(ctx, "k_sw_gather"); ZKW_LAUNCH(ctx, k_sw_gather, n, ST_DEPTH, e, perm, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}, status, meta); }
+        { Prof _p(ctx, "k_sw_count"); ZKW_LAUNCH(ctx, k_sw_count, blocks_for(n, 256), 256, (const u64*)t->index[0], (u64)n, meta + 1); }
+        return ctx->read_small(h_meta, meta, sizeof h_meta);
+    }();
+    if (rc != ZKW_OK) return sw_drop(t, rc);
+    if (h_meta[0] != ~0u) {
+        u32 st = 0;
+        rc = ctx->read_small(&st, status + h_meta[0], sizeof st);
+        if (rc != ZKW_OK) return sw_drop(t, rc);
+        return sw_drop(t, fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: entry %u is not a proof for this root: %s", h_meta[0], sw_reason(st)));
+    }
+    t->n = h_meta[1];
+    ctx_retain(ctx);
+    *out = t;
+    return ZKW_OK;
+}
+
+extern "C" int zkw_storage_tree_extract_witness(const zkw_storage_tree* tree, zkw_ctx* ctx, const uint8_t* keys, size_t n, zkw_storage_tree** out) {
+    if (!tree || !ctx || !out || (n && !keys)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_extract_witness: null argument");
+    if (tree->witness) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_extract_witness: the source is a witness tree; a witness is cut out of a full tree");
+    if (ctx->device != tree->ctx->device) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_extract_witness: the tree lives on device %d, the context on device %d", tree->ctx->device, ctx->device);
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_extract_witness: at most 2^31 - 1 keys");
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_extract_witness: the context belongs to a batch of blocks");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    const uint8_t* d_k = nullptr;
+    ZKW_TRY(ctx->in("sw_in_keys", keys, n * 32, &d_k));
+    const u32* d_keys = reinterpret_cast<const u32*>(d_k);
+    // the distinct keys in order: the sort, then a count of the runs' heads
+    u32 unique = 0, *heads = nullptr;
+    const u32* perm = nullptr;
+    if (n) {
+        ZKW_TRY(ctx->scratch_t<u32>("st_heads", n + 1, &heads));
+        ZKW_TRY(st_sort_merged(ctx, st_keys_only(d_keys, n), n, &perm));
+        ZKW_TRY(flag_prefix(ctx, "k_st_heads", StHeadFlag{st_keys_only(d_keys, n), perm}, n, heads));
+        ZKW_TRY(ctx->read_small(&unique, heads + n, sizeof unique));
+    }
+    zkw_storage_tree* t = nullptr;
+    ZKW_TRY(sw_alloc(ctx, unique, "zkw_storage_tree_extract_witness", &t));
+    memcpy(t->root, tree->root, 32);
+    t->next_index = tree->next_index;
+    u32 count = 0;
+    int rc = [&]() -> int {
+        if (unique == 0) return ZKW_OK;
+        u32* d_count = nullptr;
+        ZKW_TRY(ctx->scratch_t<u32>("sw_meta", 2, &d_count));
+        HIP_TRY(ctx->memset_async(d_count, 0, sizeof(u32)));
+        { Prof _p(ctx, "k_sw_unique_keys"); ZKW_LAUNCH(ctx, k_sw_unique_keys, blocks_for(n, 256), 256, d_keys, perm, (const u32*)heads, (u64)n, t->keys[0]); }
+        // the full tree's answers straight into the table
+        ZKW_TRY(st_query(ctx, tree, StQuery{nullptr, t->keys[0], t->index[0], t->values[0], t->paths}, unique));
+        { Prof _p(ctx, "k_sw_count"); ZKW_LAUNCH(ctx, k_sw_count, blocks_for(unique, 256), 256, (const u64*)t->index[0], (u64)unique, d_count); }
+        return ctx->read_small(&count, d_count, sizeof count);
+    }();
+    if (rc != ZKW_OK) return sw_drop(t, rc);
+    t->n = count;
+    ctx_retain(ctx);
+    *out = t;
+    return ZKW_OK;
 }

@@ -172,6 +172,9 @@ SYMBOLS = [
     ("zkw_storage_tree_get_leaves", _int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zkw_storage_tree_answer_queries", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_storage_tree_apply_queries", _int, [_vp, _vp, _sz]),
+    ("zkw_storage_tree_create_witness", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("zkw_storage_tree_extract_witness", _int, [_vp, _vp, _vp, _sz, C.POINTER(_vp)]),
+    ("zkw_storage_tree_is_witness", _int, [_vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -578,12 +581,56 @@ class StorageTreeDevice:
     `ctx`'s device — depth 256, Blake2s-256, the conventions of synthetic.StorageTree. Keys and values are 32 bytes each: numpy
     arrays [n, 32] of uint8 (or anything np.asarray makes one of, a list of `bytes` included) on a context in host pointer mode; torch
     uint8 tensors on the context's device when it is in device pointer mode (Context.set_pointer_mode(PTR_DEVICE)) — results then
-    come back as tensors too. `capacity_leaves` bounds the tree: bytes_per_leaf() bytes of device memory each, allocated here."""
+    come back as tensors too. `capacity_leaves` bounds the tree: bytes_per_leaf() bytes of device memory each, allocated here.
+    A WITNESS tree (`from_proofs`, `extract_witness`; `.is_witness`) holds the answers for a key set in one state only: it is read like a
+    tree — `Block(storage_tree_device=...)`, `run_many` with one per block — and its mutators raise ZkwError(ERR_INVALID)."""
 
     def __init__(self, ctx, capacity_leaves):
         self.ctx = ctx
         self.handle = C.c_void_p(None)
         _check(load().zkw_storage_tree_create(ctx.handle, capacity_leaves, C.byref(self.handle)))
+
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        t = cls.__new__(cls)
+        t.ctx, t.handle = ctx, handle
+        return t
+
+    @classmethod
+    def from_proofs(cls, ctx, keys, leaf_indexes, values, paths, root, next_enumeration_index):
+        """zkw_storage_tree_create_witness: a WITNESS tree — the get_leaf answers of `keys` in one state of a tree, in any order — from
+        (leaf index, value, Merkle path [256, 32]) per key, the state's root and next enumeration index. Every entry is verified on the
+        device; a forged one raises ZkwError(ERR_INVALID) naming its position. Arrays as for `insert` (`leaf_indexes`: uint64, an int64
+        tensor in device pointer mode)."""
+        t = cls._adopt(ctx, C.c_void_p(None))
+        kp, n, _k = t._rows32(keys)
+        vp, nv, _v = t._rows32(values)
+        pp, npth, _p = t._rows32(paths)
+        if t._device_mode():
+            idx = leaf_indexes.contiguous()
+            assert idx.is_cuda and idx.element_size() == 8
+            ip, ni = C.c_void_p(idx.data_ptr() if idx.numel() else None), idx.numel()
+        else:
+            idx = np.ascontiguousarray(leaf_indexes, dtype=np.uint64).reshape(-1)
+            ip, ni = (_np_ptr(idx) if idx.size else None), idx.size
+        assert n == nv == ni and npth == 256 * n
+        r = np.frombuffer(bytes(root), np.uint8).copy()
+        assert r.size == 32
+        _check(load().zkw_storage_tree_create_witness(ctx.handle, kp, ip, vp, pp, n, _np_ptr(r), int(next_enumeration_index), C.byref(t.handle)))
+        return t
+
+    def extract_witness(self, keys, ctx=None):
+        """zkw_storage_tree_extract_witness: the witness tree of `keys` (they may repeat) in this tree's CURRENT state, device to device on
+        `ctx`'s stream (default: the tree's context). The tree may change right after; the witness tree does not."""
+        ctx = ctx or self.ctx
+        w = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
+        kp, n, _k = w._rows32(keys)
+        _check(load().zkw_storage_tree_extract_witness(self.handle, ctx.handle, kp, n, C.byref(w.handle)))
+        return w
+
+    @property
+    def is_witness(self) -> bool:
+        return bool(load().zkw_storage_tree_is_witness(self.handle))
 
     @staticmethod
     def bytes_per_leaf():
@@ -1694,7 +1741,9 @@ class Block:
     capacity (default geometry_config.rs); `storage_tree`: callable(dedup_queries) -> (leaf_indexes, merkle_paths,
     initial_root, next_enumeration_index is given separately) or None; `storage_tree_device`: a StorageTreeDevice the block's
     storage queries are answered from on the device instead (root and next enumeration index are the tree's) — the form
-    run_many / prepare_many / run_sharded take too, as one tree for all blocks or a list with a tree or None per block."""
+    run_many / prepare_many / run_sharded take too, as one tree for all blocks or a list with a tree or None per block. A witness
+    tree (StorageTreeDevice.from_proofs / .extract_witness) goes wherever a tree does: consecutive blocks each bring the witness tree of
+    their own pre-state and leave in one run_many; a block whose witness tree lacks one of its slots raises ZkwError(ERR_INVALID)."""
 
     WITNESS_GETTERS = {2: "zkw_decommit_witness", 3: "zkw_decommitter_witness", 4: "zkw_demux_witness", 5: "zkw_precompile_witness",
                        6: "zkw_precompile_witness", 7: "zkw_precompile_witness", 8: "zkw_ram_witness", 9: "zkw_storage_witness",

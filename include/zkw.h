@@ -615,6 +615,39 @@ int zkw_storage_tree_answer_queries(const zkw_storage_tree *tree, zkw_ctx *ctx, 
    (ZKW_STO_RESULT_QUERIES). See zkw_block_apply_storage for a block's own queue. */
 int zkw_storage_tree_apply_queries(zkw_storage_tree *tree, const zkw_log_query *queries, size_t n);
 
+/* A WITNESS tree: the answers get_leaf gives for n keys in ONE state of a tree, and nothing else — what a prover-side host has
+   when the node hands it, per block, the Merkle paths of the slots the block touches (the reference reads exactly that through
+   `get_leaf`, storage_application.rs:217-266), and what a host that chains consecutive blocks cuts out of its full tree before
+   it applies a block's writes. The handle is a zkw_storage_tree: it goes wherever a tree is READ — zkw_block_inputs.
+   storage_tree_device above all, so that every block of one zkw_blocks_run brings its own pre-state. 8 264 bytes of device
+   memory per entry (csrc/storage_witness_kernels.cuh), immutable, any number of readers.
+   On a witness tree: zkw_storage_tree_root and _next_enumeration_index are the state's; _num_leaves = the entries with a
+   nonzero index (the present keys), _capacity = the entries. zkw_storage_tree_get_leaves answers the table's keys exactly as
+   the full tree would and returns ZKW_ERR_INVALID, naming the position, for a key outside the table; the contents of the
+   three output arrays are then unspecified (in device pointer mode the lookup has written them).
+   zkw_storage_tree_answer_queries is enqueued and not synchronised, so it cannot return that error: for a query whose key is
+   not in the table it writes leaf_indexes[i] = UINT64_MAX and a zero path. A block whose witness tree lacks one of its slots
+   fails with ZKW_ERR_INVALID, and zkw_block_last_error names the deduplicated query (position, address, key); inside
+   zkw_blocks_run that is the call's failure. zkw_storage_tree_insert, _apply_queries, _set_next_enumeration_index and
+   zkw_block_apply_storage return ZKW_ERR_INVALID and change nothing. */
+/* From proofs: keys[n][32], leaf_indexes[n], values[n][32], merkle_paths[n][256][32] follow ctx's pointer mode, in any order
+   (they are sorted on the device); root and next_enumeration_index are host values; n == 0 is valid (a block without storage
+   queries still needs a root and an index). An absent key is index 0 with a zero value. Every entry is verified on the device
+   before the handle is returned (verify_inclusion_proxy, storage_application.rs:230,266): the leaf hash of (leaf_index as 8
+   big-endian bytes || value), folded up the 256 siblings by the key's bits, must equal root. An entry that does not verify,
+   whose leaf_index >= next_enumeration_index, that has a nonzero value at index 0, or whose key an earlier entry has, gives
+   ZKW_ERR_INVALID with the position IN THE CALLER'S ORDER of the first such entry in zkw_last_error; nothing is returned. */
+int zkw_storage_tree_create_witness(zkw_ctx *ctx, const uint8_t *keys /*[n][32]*/, const uint64_t *leaf_indexes /*[n]*/,
+                                    const uint8_t *values /*[n][32]*/, const uint8_t *merkle_paths /*[n][256][32]*/, size_t n,
+                                    const uint8_t root[32], uint64_t next_enumeration_index, zkw_storage_tree **out);
+/* Cut out of a full tree (a witness tree as `tree` -> ZKW_ERR_INVALID) in its current state: get_leaf of keys[n][32] (ctx's
+   pointer mode; ctx on the tree's device) straight into the new table, device to device on ctx's stream. Keys may repeat —
+   derive_final_address of all of a block's storage log queries, as they come — and collapse to one entry. Nothing is
+   verified: the tree computed the paths. Returns when the table is complete: the tree may be changed right after. */
+int zkw_storage_tree_extract_witness(const zkw_storage_tree *tree, zkw_ctx *ctx, const uint8_t *keys, size_t n,
+                                     zkw_storage_tree **out);
+int zkw_storage_tree_is_witness(const zkw_storage_tree *tree);
+
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
 /* kind = ZKW_PRECOMPILE_KECCAK256: keccak256_decompose_into_per_circuit_witness,
