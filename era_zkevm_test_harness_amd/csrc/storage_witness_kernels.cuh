@@ -173,4 +173,235 @@ static __device__ __forceinline__ void k_sw_count(const VB& vb, const u64* __res
     if (i < n && index[i] != 0) atomicAdd(count, 1u);
 }
 
+// ------------------------------------------------------------------------------------------------ advance
+// zkw_storage_tree_advance_witness / _by_queries: a NEW table with the same keys in the state after a call's writes. A write changes its
+// key's own path and the siblings that hang off it, and the written keys' old paths hold every sibling hash that does not change. So:
+//   * locate (k_swa_locate): a thread per position p of the call — pair p, or query p when it writes: the key's entry by lower bound;
+//     first[entry] / last[entry] = the least / greatest writing position (atomicMin / atomicMax); a key outside the table raises the
+//     `missing` word as k_sw_lookup does. Two flag_prefix passes follow: over the positions (p is the first write of an entry with
+//     index 0: its rank among the NEW leaves, in array order) and over the entries (written: the rank w in the written set W, which
+//     is sorted by key because the table is);
+//   * k_swa_compact, k_swa_leaves: wlist[w] = the entry, its new (index, value), the new leaf hash and d[w] = the highest bit where
+//     written key w differs from written key w - 1;
+//   * fold (k_swa_fold for |W| <= ST_PERSISTENT_MAX, else k_swa_level per height): the build of storage_tree_kernels.cuh over W alone.
+//     The written keys under one node of height L are a contiguous range of W; the node's hash is kept at the range's first key:
+//     up[L][a], level-major [257][bound][8]. Height L + 1 of range start a = H(up[L][a], s) ordered by the sides, where s =
+//     up[L][m] when the next range m = nxt[a] lies under the same parent (d[m] == L), else the sibling subtree holds no written key
+//     and s = the OLD path[L] of a's entry. up[256][0] = the new root;
+//   * paths (k_swa_paths): a workgroup per entry of the table, thread L: the sibling subtree at level L is a prefix; the first
+//     written key not below it starts that node's range if it shares the prefix, and the new path[L] = up[L][that], else the old one.
+//     The same pass copies the key and writes the new index and value: the table is copied once.
+// Nothing is read back before the end: grids are sized by bound = min(positions, entries) >= |W|, the kernels read |W| from meta.
+constexpr u32 SWA_NONE = ~0u;        // first[e] of an entry no position writes
+constexpr int SWA_META_MISSING = 0;  // k_sw_lookup's convention: 0, or (positions - the first position whose key the table lacks)
+constexpr int SWA_META_NW = 1;       // |W|
+constexpr int SWA_META_NEW = 2;      // entries that become present
+constexpr int SWA_META_ROOT = 4;     // [8]: up[256][0]
+constexpr int SWA_META_WORDS = 16;   // `last` follows in the same zeroed buffer
+
+// the call's writes: the queries with rw_flag set, or (queries == NULL) n pairs
+struct SwaWrites {
+    const zkw_log_query* queries;
+    const u32* keys;    // [n][8]
+    const u32* values;  // [n][8]
+    u64 n;
+    __device__ __forceinline__ bool writes(u64 p) const { return !queries || queries[p].rw_flag != 0; }
+    __device__ __forceinline__ u32 value_word(u64 p, int w) const { return queries ? bswap32(queries[p].written_value[7 - w]) : values[8 * p + w]; }
+};
+
+static __device__ __forceinline__ void k_swa_locate(const VB& vb, SwView t, SwaWrites wr, u32* __restrict__ ent, u32* __restrict__ first,
+                                                    u32* __restrict__ last, u32* __restrict__ meta) {
+    const u64 p = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (p >= wr.n) return;
+    if (!wr.writes(p)) { ent[p] = SWA_NONE; return; }
+    u32 key[8];
+    if (wr.queries) {
+        sap_derive_key(wr.queries + p, key);
+    } else {
+#pragma unroll
+        for (int w = 0; w < 8; w++) key[w] = wr.keys[8 * p + w];
+    }
+    u64 lo = 0, hi = t.n;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (st_cmp(t.keys + 8 * mid, key) < 0) lo = mid + 1; else hi = mid;
+    }
+    const bool hit = lo < t.n && st_cmp(t.keys + 8 * lo, key) == 0;
+    ent[p] = hit ? (u32)lo : SWA_NONE;
+    if (hit) {
+        atomicMin(first + lo, (u32)p);
+        atomicMax(last + lo, (u32)p);
+    } else {
+        atomicMax(meta + SWA_META_MISSING, (u32)(wr.n - p));
+    }
+}
+// position p is the first write of an entry that is absent so far
+struct SwaNewFlag {
+    const u32 *ent, *first;
+    const u64* index;
+    __device__ __forceinline__ u32 operator()(size_t p) const {
+        const u32 e = ent[p];
+        return e != SWA_NONE && first[e] == (u32)p && index[e] == 0;
+    }
+};
+struct SwaWrittenFlag {
+    const u32* first;
+    __device__ __forceinline__ u32 operator()(size_t e) const { return first[e] != SWA_NONE; }
+};
+
+// what the fold works on; `bound` = the pitch of up's levels
+struct SwaFold {
+    SwView t;
+    const u32* wlist;  // [|W|]: the written entries, ascending
+    u32* up;           // [257][bound][8]
+    u32* d;            // [|W|]
+    u32* nxt;          // [|W|]
+    u32* meta;
+    u64 bound;
+};
+
+// wrank[e] = written entries before e; new_rank[p] = new leaves before position p
+static __device__ __forceinline__ void k_swa_compact(const VB& vb, const u32* __restrict__ first, const u32* __restrict__ wrank, const u32* __restrict__ new_rank,
+                                                     u64 entries, u64 positions, u32* __restrict__ wlist, u32* __restrict__ meta) {
+    const u64 e = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (e >= entries) return;
+    if (first[e] != SWA_NONE) wlist[wrank[e]] = (u32)e;
+    if (e == 0) {
+        meta[SWA_META_NW] = wrank[entries];
+        meta[SWA_META_NEW] = new_rank[positions];
+    }
+}
+
+// written key w: its new index and value (widx, wval: what k_swa_paths writes into the table), the leaf hash, d and nxt
+static __device__ __forceinline__ void k_swa_leaves(const VB& vb, SwaFold f, SwaWrites wr, const u32* __restrict__ first, const u32* __restrict__ last,
+                                                    const u32* __restrict__ new_rank, u64 next_index, u64* __restrict__ widx, u32* __restrict__ wval) {
+    const u64 w = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (w >= f.meta[SWA_META_NW]) return;
+    const u64 e = f.wlist[w];
+    const u64 old = f.t.index[e], index = old ? old : next_index + new_rank[first[e]];
+    const u64 p = last[e];
+    u32 v[8], h[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = wr.value_word(p, k);
+    sap_leaf_hash_bytes(index, v, h);
+    widx[w] = index;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        wval[8 * w + k] = v[k];
+        f.up[8 * w + k] = h[k];
+    }
+    f.d[w] = w ? (u32)st_top_diff(f.t.keys + 8 * e, f.t.keys + 8 * (u64)f.wlist[w - 1]) : (u32)ST_DEPTH;
+    f.nxt[w] = (u32)(w + 1);
+}
+
+// the node of height L + 1 over `mine` (height L, the range that starts at written entry e): its sibling is `other`, the next range's
+// node (then `mine` is the left child: W is sorted), or NULL: the entry's old path[L], on the side the key's bit L says
+__device__ __forceinline__ void swa_parent(const SwView& t, int L, u64 e, const u32* mine, const u32* other, u32 o[8]) {
+    bool right = false;
+    uint4 s0, s1;
+    if (other) {
+        s0 = make_uint4(other[0], other[1], other[2], other[3]);
+        s1 = make_uint4(other[4], other[5], other[6], other[7]);
+    } else {
+        const uint4* sib = reinterpret_cast<const uint4*>(t.paths + (e * ST_DEPTH + L) * 8);
+        s0 = sib[0];
+        s1 = sib[1];
+        right = (t.keys[8 * e + (L >> 5)] >> (L & 31)) & 1;
+    }
+    const u32 c[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    u32 l[8], r[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const u32 a = mine[k];
+        l[k] = right ? c[k] : a;
+        r[k] = right ? a : c[k];
+    }
+    sap_node_hash(l, r, o);
+}
+
+// one height per launch: grid = the written keys, 64 threads
+static __device__ __forceinline__ void k_swa_level(const VB& vb, SwaFold f, int L) {
+    const u64 i = (u64)vb.x * blockDim.x + threadIdx.x;
+    const u32 nw = f.meta[SWA_META_NW];
+    if (i >= nw || f.d[i] <= (u32)L) return;  // not the first written key of a node of height L + 1
+    const u32 m = f.nxt[i];
+    const bool has_sibling = m < nw && f.d[m] == (u32)L;
+    u32 o[8];
+    swa_parent(f.t, L, f.wlist[i], f.up + ((u64)L * f.bound + i) * 8, has_sibling ? f.up + ((u64)L * f.bound + m) * 8 : nullptr, o);
+    u32* out = f.up + ((u64)(L + 1) * f.bound + i) * 8;
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = o[k];
+    if (L + 1 == ST_DEPTH)
+        for (int k = 0; k < 8; k++) f.meta[SWA_META_ROOT + k] = o[k];
+    if (has_sibling) f.nxt[i] = f.nxt[m];  // (m starts no node of height L + 1: nobody writes nxt[m] at this height)
+}
+
+// all heights in one launch, one workgroup, |W| <= ST_PERSISTENT_MAX: the current height's hashes, d, nxt and wlist live in LDS, so
+// the barrier per height needs no device-scope fence (k_st_levels pays one per height: its hashes travel through global memory);
+// up[] is only written here, for k_swa_paths. A slot is read by its own thread and by the one range start to its left, which
+// then computes while the slot's owner does not: in place, one barrier per height.
+static __device__ __forceinline__ void k_swa_fold(const VB& vb, SwaFold f) {
+    __shared__ u32 s_h[ST_PERSISTENT_MAX][8];
+    __shared__ u32 s_d[ST_PERSISTENT_MAX], s_nxt[ST_PERSISTENT_MAX], s_e[ST_PERSISTENT_MAX];
+    const u32 nw = f.meta[SWA_META_NW];
+    if (nw > ST_PERSISTENT_MAX) return;  // (the driver sizes by bound >= |W|)
+    for (u32 i = threadIdx.x; i < nw; i += ST_PERSISTENT_THREADS) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) s_h[i][k] = f.up[8 * (u64)i + k];
+        s_d[i] = f.d[i];
+        s_nxt[i] = i + 1;
+        s_e[i] = f.wlist[i];
+    }
+    __syncthreads();
+    for (int L = 0; L < ST_DEPTH; L++) {
+        for (u32 i = threadIdx.x; i < nw; i += ST_PERSISTENT_THREADS) {
+            if (s_d[i] <= (u32)L) continue;
+            const u32 m = s_nxt[i];
+            const bool has_sibling = m < nw && s_d[m] == (u32)L;
+            u32 o[8];
+            swa_parent(f.t, L, s_e[i], s_h[i], has_sibling ? s_h[m] : nullptr, o);
+            u32* out = f.up + ((u64)(L + 1) * f.bound + i) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { s_h[i][k] = o[k]; out[k] = o[k]; }
+            if (L + 1 == ST_DEPTH)
+                for (int k = 0; k < 8; k++) f.meta[SWA_META_ROOT + k] = o[k];
+            if (has_sibling) s_nxt[i] = s_nxt[m];
+        }
+        __syncthreads();
+    }
+}
+
+// grid = the entries, 256 threads: thread L writes level L of entry e's new path
+static __device__ __forceinline__ void k_swa_paths(const VB& vb, SwaFold f, const u32* __restrict__ first, const u32* __restrict__ wrank,
+                                                   const u64* __restrict__ widx, const u32* __restrict__ wval, SwTable out) {
+    const u64 e = vb.x;
+    const int L = threadIdx.x;
+    const u32 nw = f.meta[SWA_META_NW];
+    u32 key[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = f.t.keys[8 * e + w];
+    if (L < 8) {
+        const bool written = first[e] != SWA_NONE;
+        out.keys[8 * e + L] = f.t.keys[8 * e + L];
+        out.values[8 * e + L] = written ? wval[8 * (u64)wrank[e] + L] : f.t.values[8 * e + L];
+        if (L == 0) out.index[e] = written ? widx[wrank[e]] : f.t.index[e];
+    }
+    // the sibling subtree at level L: the key with bit L flipped and the bits below cleared (k_st_query)
+    const int wl = L >> 5;
+#pragma unroll
+    for (int w = 0; w < 8; w++)
+        if (w < wl) key[w] = 0;
+        else if (w == wl) key[w] = (key[w] ^ (1u << (L & 31))) & ~((1u << (L & 31)) - 1u);
+    u32 lo = 0, hi = nw;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (st_cmp(f.t.keys + 8 * (u64)f.wlist[mid], key) < 0) lo = mid + 1; else hi = mid;
+    }
+    const bool hit = lo < nw && st_top_diff(f.t.keys + 8 * (u64)f.wlist[lo], key) < L;  // a written key under the sibling: lo starts its range
+    const uint4* src = reinterpret_cast<const uint4*>(hit ? f.up + ((u64)L * f.bound + lo) * 8 : f.t.paths + (e * ST_DEPTH + L) * 8);
+    uint4* dst = reinterpret_cast<uint4*>(out.paths + (e * ST_DEPTH + L) * 8);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
 }  // namespace zkw

@@ -3,7 +3,8 @@
 // storage_tree_kernels.cuh. Every call that changes the tree ends with the new root on the host (one small readback), so a call that
 // only reads — zkw_storage_tree_answer_queries from the storage branch of any number of blocks — needs no ordering with the tree's stream.
 // A WITNESS tree (storage_witness_kernels.cuh) is the same handle with `witness` set: a sorted table of get_leaf answers for one state,
-// built once (zkw_storage_tree_create_witness / _extract_witness), read like a tree, never changed.
+// built once (zkw_storage_tree_create_witness / _extract_witness), read like a tree, never changed; zkw_storage_tree_advance_witness makes
+// the table of the NEXT state out of it, as a new handle.
 #include "zkw_ctx.h"
 #include "storage_witness_kernels.cuh"
 #include "radix_sort.cuh"
@@ -418,4 +419,94 @@ extern "C" int zkw_storage_tree_extract_witness(const zkw_storage_tree* tree, zk
     ctx_retain(ctx);
     *out = t;
     return ZKW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ advancing a witness tree
+// the writes `wr` (device memory) applied to the state `src` holds: storage_witness_kernels.cuh, "advance". One readback at the end: the
+// flag word of a key outside the table, |W|, the new leaves and the root together.
+static int sw_advance(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx, const SwaWrites& wr, zkw_storage_tree** out) {
+    const size_t entries = src->cap, n = (size_t)wr.n;
+    const size_t bound = std::min(entries, n);  // >= the written entries
+    u32 *first = nullptr, *meta = nullptr, *ent = nullptr, *new_rank = nullptr, *wrank = nullptr, *wlist = nullptr, *wval = nullptr, *up = nullptr, *d = nullptr, *nxt = nullptr;
+    u64* widx = nullptr;
+    ZKW_TRY(ctx->scratch_t<u32>("swa_first", entries, &first));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_meta_last", SWA_META_WORDS + entries, &meta));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_ent", n, &ent));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_new_rank", n + 1, &new_rank));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_wrank", entries + 1, &wrank));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_wlist", bound, &wlist));
+    ZKW_TRY(ctx->scratch_t<u64>("swa_widx", bound, &widx));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_wval", bound * 8, &wval));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_d", bound, &d));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_nxt", bound, &nxt));
+    ZKW_TRY(ctx->scratch_t<u32>("swa_up", bound * (size_t)(ST_DEPTH + 1) * 8, &up));
+    u32* last = meta + SWA_META_WORDS;
+    zkw_storage_tree* t = nullptr;
+    ZKW_TRY(sw_alloc(ctx, entries, who, &t));
+    u32 h_meta[SWA_META_WORDS] = {};
+    int rc = [&]() -> int {
+        if (entries) HIP_TRY(ctx->memset_async(first, 0xFF, entries * sizeof(u32)));
+        HIP_TRY(ctx->memset_async(meta, 0, (SWA_META_WORDS + entries) * sizeof(u32)));
+        const SwView tv = src->table();
+        const SwaFold f{tv, wlist, up, d, nxt, meta, (u64)bound};
+        { Prof _p(ctx, "k_swa_locate"); ZKW_LAUNCH(ctx, k_swa_locate, blocks_for(n, 64), 64, tv, wr, ent, first, last, meta); }
+        ZKW_TRY(flag_prefix(ctx, "k_swa_new_rank", SwaNewFlag{ent, first, tv.index}, n, new_rank));
+        ZKW_TRY(flag_prefix(ctx, "k_swa_wrank", SwaWrittenFlag{first}, entries, wrank));
+        { Prof _p(ctx, "k_swa_compact"); ZKW_LAUNCH(ctx, k_swa_compact, blocks_for(entries, 256), 256, (const u32*)first, (const u32*)wrank, (const u32*)new_rank, (u64)entries, (u64)n, wlist, meta); }
+        { Prof _p(ctx, "k_swa_leaves"); ZKW_LAUNCH(ctx, k_swa_leaves, blocks_for(bound, 64), 64, f, wr, (const u32*)first, (const u32*)last, (const u32*)new_rank, src->next_index, widx, wval); }
+        if (bound <= ST_PERSISTENT_MAX) {
+            Prof _p(ctx, "k_swa_fold");
+            ZKW_LAUNCH(ctx, k_swa_fold, bound ? 1 : 0, ST_PERSISTENT_THREADS, f);
+        } else {
+            for (int L = 0; L < ST_DEPTH; L++) {
+                Prof _p(ctx, "k_swa_level");
+                ZKW_LAUNCH(ctx, k_swa_level, blocks_for(bound, 64), 64, f, L);
+            }
+        }
+        { Prof _p(ctx, "k_swa_paths"); ZKW_LAUNCH(ctx, k_swa_paths, entries, ST_DEPTH, f, (const u32*)first, (const u32*)wrank, (const u64*)widx, (const u32*)wval, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}); }
+        return ctx->read_small(h_meta, meta, sizeof h_meta);
+    }();
+    if (rc != ZKW_OK) return sw_drop(t, rc);
+    if (h_meta[SWA_META_MISSING])
+        return sw_drop(t, fail(ZKW_ERR_INVALID, "%s: the key written at position %zu is not in the witness tree", who, n - h_meta[SWA_META_MISSING]));
+    memcpy(t->root, h_meta[SWA_META_NW] ? reinterpret_cast<const uint8_t*>(h_meta + SWA_META_ROOT) : src->root, 32);
+    t->n = src->n + h_meta[SWA_META_NEW];
+    t->next_index = src->next_index + h_meta[SWA_META_NEW];
+    ctx_retain(ctx);
+    *out = t;
+    return ZKW_OK;
+}
+
+static int sw_advance_check(const char* who, const zkw_storage_tree* w, zkw_ctx* ctx, size_t n, zkw_storage_tree** out) {
+    if (!w || !ctx || !out) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (!w->witness) return fail(ZKW_ERR_INVALID, "%s: the source is a full tree; it takes zkw_storage_tree_insert / _apply_queries", who);
+    if (ctx->device != w->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the tree lives on device %d, the context on device %d", who, w->ctx->device, ctx->device);
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "%s: at most 2^31 - 1 writes", who);
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "%s: the context belongs to a batch of blocks", who);
+    *out = nullptr;
+    return ZKW_OK;
+}
+
+extern "C" int zkw_storage_tree_advance_witness(const zkw_storage_tree* witness, zkw_ctx* ctx, const uint8_t* keys, const uint8_t* values, size_t n,
+                                                zkw_storage_tree** out) {
+    static const char who[] = "zkw_storage_tree_advance_witness";
+    if (n && (!keys || !values)) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    ZKW_TRY(sw_advance_check(who, witness, ctx, n, out));
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_k = nullptr, *d_v = nullptr;
+    ZKW_TRY(ctx->in("swa_in_keys", keys, n * 32, &d_k));
+    ZKW_TRY(ctx->in("swa_in_values", values, n * 32, &d_v));
+    return sw_advance(who, witness, ctx, SwaWrites{nullptr, reinterpret_cast<const u32*>(d_k), reinterpret_cast<const u32*>(d_v), (u64)n}, out);
+}
+
+extern "C" int zkw_storage_tree_advance_witness_by_queries(const zkw_storage_tree* witness, zkw_ctx* ctx, const zkw_log_query* queries, size_t n,
+                                                           zkw_storage_tree** out) {
+    static const char who[] = "zkw_storage_tree_advance_witness_by_queries";
+    if (n && !queries) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    ZKW_TRY(sw_advance_check(who, witness, ctx, n, out));
+    HIP_TRY(hipSetDevice(ctx->device));
+    const zkw_log_query* d_q = nullptr;
+    ZKW_TRY(ctx->in("swa_in_queries", queries, n, &d_q));
+    // (n == 0: no query is read, and SwaWrites with queries == NULL is the pair form with no pair)
+    return sw_advance(who, witness, ctx, SwaWrites{d_q, nullptr, nullptr, (u64)n}, out);
 }

@@ -174,6 +174,8 @@ SYMBOLS = [
     ("zkw_storage_tree_apply_queries", _int, [_vp, _vp, _sz]),
     ("zkw_storage_tree_create_witness", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("zkw_storage_tree_extract_witness", _int, [_vp, _vp, _vp, _sz, C.POINTER(_vp)]),
+    ("zkw_storage_tree_advance_witness", _int, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_vp)]),
+    ("zkw_storage_tree_advance_witness_by_queries", _int, [_vp, _vp, _vp, _sz, C.POINTER(_vp)]),
     ("zkw_storage_tree_is_witness", _int, [_vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
@@ -583,7 +585,8 @@ class StorageTreeDevice:
     uint8 tensors on the context's device when it is in device pointer mode (Context.set_pointer_mode(PTR_DEVICE)) — results then
     come back as tensors too. `capacity_leaves` bounds the tree: bytes_per_leaf() bytes of device memory each, allocated here.
     A WITNESS tree (`from_proofs`, `extract_witness`; `.is_witness`) holds the answers for a key set in one state only: it is read like a
-    tree — `Block(storage_tree_device=...)`, `run_many` with one per block — and its mutators raise ZkwError(ERR_INVALID)."""
+    tree — `Block(storage_tree_device=...)`, `run_many` with one per block — and its mutators raise ZkwError(ERR_INVALID); `advance` /
+    `advance_by_queries` return the witness tree of the state after a block's writes, so ONE proof set serves K consecutive blocks."""
 
     def __init__(self, ctx, capacity_leaves):
         self.ctx = ctx
@@ -626,6 +629,32 @@ class StorageTreeDevice:
         w = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
         kp, n, _k = w._rows32(keys)
         _check(load().zkw_storage_tree_extract_witness(self.handle, ctx.handle, kp, n, C.byref(w.handle)))
+        return w
+
+    def advance(self, keys, values, ctx=None):
+        """zkw_storage_tree_advance_witness: a NEW witness tree with this one's keys in the state after inserting the pairs one after
+        another (a block: in the order of its deduplicated storage queue). This one stays as it is. A written key outside the table
+        raises ZkwError(ERR_INVALID) naming its position."""
+        ctx = ctx or self.ctx
+        w = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
+        kp, n, _k = w._rows32(keys)
+        vp, nv, _v = w._rows32(values)
+        assert n == nv
+        _check(load().zkw_storage_tree_advance_witness(self.handle, ctx.handle, kp, vp, n, C.byref(w.handle)))
+        return w
+
+    def advance_by_queries(self, queries, ctx=None):
+        """zkw_storage_tree_advance_witness_by_queries: the same with the writes of a block's deduplicated storage queue, as
+        `apply_queries` takes them; reads are skipped."""
+        ctx = ctx or self.ctx
+        w = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
+        if w._device_mode():
+            q = queries.contiguous()
+            qp, n = C.c_void_p(q.data_ptr() if q.numel() else None), q.numel() // LOG_QUERY.itemsize
+        else:
+            q = np.ascontiguousarray(queries, dtype=LOG_QUERY)
+            qp, n = (_np_ptr(q) if q.size else None), q.size
+        _check(load().zkw_storage_tree_advance_witness_by_queries(self.handle, ctx.handle, qp, n, C.byref(w.handle)))
         return w
 
     @property

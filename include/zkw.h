@@ -620,7 +620,8 @@ int zkw_storage_tree_apply_queries(zkw_storage_tree *tree, const zkw_log_query *
    `get_leaf`, storage_application.rs:217-266), and what a host that chains consecutive blocks cuts out of its full tree before
    it applies a block's writes. The handle is a zkw_storage_tree: it goes wherever a tree is READ — zkw_block_inputs.
    storage_tree_device above all, so that every block of one zkw_blocks_run brings its own pre-state. 8 264 bytes of device
-   memory per entry (csrc/storage_witness_kernels.cuh), immutable, any number of readers.
+   memory per entry (csrc/storage_witness_kernels.cuh), immutable, any number of readers; the table of the next state is a
+   new handle (zkw_storage_tree_advance_witness below).
    On a witness tree: zkw_storage_tree_root and _next_enumeration_index are the state's; _num_leaves = the entries with a
    nonzero index (the present keys), _capacity = the entries. zkw_storage_tree_get_leaves answers the table's keys exactly as
    the full tree would and returns ZKW_ERR_INVALID, naming the position, for a key outside the table; the contents of the
@@ -646,6 +647,30 @@ int zkw_storage_tree_create_witness(zkw_ctx *ctx, const uint8_t *keys /*[n][32]*
    verified: the tree computed the paths. Returns when the table is complete: the tree may be changed right after. */
 int zkw_storage_tree_extract_witness(const zkw_storage_tree *tree, zkw_ctx *ctx, const uint8_t *keys, size_t n,
                                      zkw_storage_tree **out);
+/* Advance: the table of the NEXT state. A host that proves K consecutive blocks needs the Merkle paths of K pre-states, and the
+   node has to be asked for ONE proof set only: the union of the K blocks' slots in the state before the first block
+   (zkw_storage_tree_create_witness). A block's writes change the written keys' own paths and the siblings that hang off them,
+   and the written keys' paths hold every other sibling, so the table after the block follows from the table before it — on the
+   device, without a full tree. Both calls return a NEW witness tree with the same keys; `witness` itself stays as it is (other
+   blocks may be reading it) and may come from proofs, from an extraction or from an earlier advance. A table grows by
+   nothing: its key set is fixed when the first table is made, and a written key outside it is an error.
+   insert_many_leafs (tree/mod.rs:65-81) applied to the STATE a witness tree holds: a new witness tree with the same keys in the
+   state after inserting the n pairs one after another in array order — what zkw_storage_tree_insert on the full tree followed
+   by zkw_storage_tree_extract_witness of the same keys gives. A key that repeats takes its last value; a written entry with
+   index 0 becomes present (a zero value too) with index next_enumeration_index + its rank among the call's newly present
+   keys in ARRAY order of first occurrence, so for a block the pairs come in the order of its deduplicated storage queue
+   (ZKW_STO_RESULT_QUERIES); a present key keeps its index. The paths of ALL entries, root, _next_enumeration_index and
+   _num_leaves are the new state's, _capacity the input's. n == 0 gives an equal table. keys and values follow ctx's pointer
+   mode; ctx on the tree's device. Returns when the table is complete, with its root on the host. A full tree as `witness`, a
+   NULL argument or a context of another device: ZKW_ERR_INVALID; a written key outside the table: ZKW_ERR_INVALID with the
+   position IN THE CALLER'S ORDER of the first such pair in zkw_last_error; no memory: ZKW_ERR_OOM. An error returns nothing. */
+int zkw_storage_tree_advance_witness(const zkw_storage_tree *witness, zkw_ctx *ctx, const uint8_t *keys /*[n][32]*/,
+                                     const uint8_t *values /*[n][32]*/, size_t n, zkw_storage_tree **out);
+/* the same for what zkw_storage_tree_apply_queries does to a full tree: insert(derive_final_address(q), q.written_value) for every
+   query with rw_flag set, in order; queries with rw_flag clear are skipped and not looked up (a READ of a key outside the
+   table is no error). queries follow ctx's pointer mode; an error names the position of the QUERY. */
+int zkw_storage_tree_advance_witness_by_queries(const zkw_storage_tree *witness, zkw_ctx *ctx, const zkw_log_query *queries,
+                                                size_t n, zkw_storage_tree **out);
 int zkw_storage_tree_is_witness(const zkw_storage_tree *tree);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */

@@ -16,6 +16,13 @@ Every GPU step is a child process of its own under its own time limit; the steps
                  witness tree per block on this one, three child processes each in turn (a warm-up round and one timed round per process);
                  the batch's own launch accounting (ZKW_BATCH_LOG: in all, and per kernel for the lookup — K blocks' lookups of a stage
                  as ONE merged launch carrying K jobs); the witness trees' HBM per block
+  advance        zkw_storage_tree_advance_witness_by_queries (-> profiles/r12/storage_witness_advance.json; needs no parent library:
+                 `--skip tables --skip gate --skip batched --out profiles/r12/storage_witness_advance.json`): 66 entries / 30 writes,
+                 512 / 256 and 1 920 / 30 (the union of 64 blocks' slots), wall clock around the synchronised call, warm, median of five,
+                 and one profiled call for the split; against the route the parent commit offers for the same step — extract_witness +
+                 apply_queries on a full tree of 2^20 leaves (code this library has unchanged), five runs, with its min-max spread; then
+                 the tables of 64 consecutive blocks of 30 slots each: one extraction of the union + 63 advances against 64 x (extraction +
+                 apply_queries), and their HBM
 """
 import argparse
 import json
@@ -108,6 +115,93 @@ def step_tables():
     return out
 
 
+def step_advance():
+    import numpy as np
+
+    from era_zkevm_test_harness_amd import native as nv, synthetic
+
+    ctx = nv.Context(0)
+    rng = np.random.default_rng(43)
+    n_full = 1 << 20
+    K, slots = 64, 30
+    q = np.ascontiguousarray(synthetic.storage_application_trace(K * slots, seed=5)[0], dtype=nv.LOG_QUERY)
+    q["rw_flag"] = 1
+    qkeys = np.frombuffer(b"".join(synthetic.derive_final_address(x) for x in q), np.uint8).reshape(-1, 32)
+    leaves = rng.integers(0, 256, size=(n_full - K * slots, 32), dtype=np.uint8)
+    leaves[:K * slots // 2] = qkeys[::2]  # every other slot exists before the first block
+    full = nv.StorageTreeDevice(ctx, n_full)
+    full.insert(leaves, rng.integers(0, 256, size=leaves.shape, dtype=np.uint8))
+    out = {"full_tree_leaves": int(full.num_leaves), "bytes_per_entry": BYTES_PER_ENTRY, "shapes": {}}
+
+    def profiled(fn):
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        fn()
+        prof = ctx.profile()
+        ctx.profile_enable(False)
+        return {k: round(v[0], 4) for k, v in prof.items()} if isinstance(prof, dict) else prof
+
+    for entries, writes in ((66, 30), (512, 256), (1920, 30)):
+        keys, batch = qkeys[:entries], q[:writes]
+        table = full.extract_witness(keys)
+        table.advance_by_queries(batch).free()  # warm: scratch, buffers
+        new = []
+        for _ in range(5):
+            ms, t = _time_ms(lambda: table.advance_by_queries(batch), ctx.synchronize)
+            new.append(ms)
+            t.free()
+        split = profiled(lambda: table.advance_by_queries(batch).free())
+        table.free()
+        # the parent's route for the same step: the next block's table cut out of the full tree, then the block's writes applied to it
+        full.extract_witness(keys).free()
+        parent, parts = [], []
+        for _ in range(5):
+            ms_x, t = _time_ms(lambda: full.extract_witness(keys), ctx.synchronize)
+            ms_a, _r = _time_ms(lambda: full.apply_queries(batch), ctx.synchronize)
+            t.free()
+            parent.append(ms_x + ms_a)
+            parts.append([round(ms_x, 4), round(ms_a, 4)])
+        spread = max(parent) - min(parent)
+        mn, mp = statistics.median(new), statistics.median(parent)
+        out["shapes"][f"{entries}_entries_{writes}_writes"] = {
+            "advance_by_queries_wall_ms": [round(x, 4) for x in new], "advance_median_ms": round(mn, 4), "advance_kernels_ms_profiled_run": split,
+            "parent_route_wall_ms": [round(x, 4) for x in parent], "parent_route_extract_apply_ms": parts, "parent_route_median_ms": round(mp, 4),
+            "parent_route_min_max_spread_ms": round(spread, 4), "below_parent_median_minus_spread": bool(mn < mp - spread),
+            "table_hbm_bytes": entries * BYTES_PER_ENTRY}
+    # the tables of K consecutive blocks: block k writes slots [30 k, 30 k + 30)
+    union = qkeys[:K * slots]
+
+    def by_advance():
+        tables = [full.extract_witness(union)]
+        for k in range(K - 1):
+            tables.append(tables[-1].advance_by_queries(q[k * slots:(k + 1) * slots]))
+        return tables
+
+    for t in by_advance():
+        t.free()
+    ms_adv, tables = _time_ms(by_advance, ctx.synchronize)
+    hbm_adv = sum(t.capacity for t in tables) * BYTES_PER_ENTRY
+    for t in tables:
+        t.free()
+
+    def by_extraction():
+        tables = []
+        for k in range(K):
+            tables.append(full.extract_witness(qkeys[k * slots:(k + 1) * slots]))
+            full.apply_queries(q[k * slots:(k + 1) * slots])
+        return tables
+
+    ms_ext, tables = _time_ms(by_extraction, ctx.synchronize)
+    hbm_ext = sum(t.capacity for t in tables) * BYTES_PER_ENTRY
+    for t in tables:
+        t.free()
+    out["tables_of_64_blocks"] = {"one_extraction_63_advances_ms": round(ms_adv, 3), "tables_hbm_bytes": hbm_adv,
+                                  "per_block_extraction_and_apply_on_the_full_tree_ms": round(ms_ext, 3), "per_block_tables_hbm_bytes": hbm_ext,
+                                  "full_tree_hbm_bytes": n_full * nv.StorageTreeDevice.bytes_per_leaf()}
+    full.free()
+    return out
+
+
 def _production_block_and_pairs(nv, synthetic, np, seed):
     """(generated on the host in tens of seconds: the probe's child processes share one copy per seed in the temporary directory, keyed on
     the generator's source so that a copy from another version of it is never read)"""
@@ -196,6 +290,8 @@ def step_batched_one(witness):
 def run_step(name):
     if name == "tables":
         return step_tables()
+    if name == "advance":
+        return step_advance()
     if name in ("gate_full", "gate_witness"):
         return step_gate_one(name == "gate_witness")
     if name in ("batched_full", "batched_witness"):
@@ -220,10 +316,12 @@ def main():
     if a.step:
         print(json.dumps(run_step(a.step)))
         return 0
-    assert a.parent_lib and os.path.exists(a.parent_lib), "--parent-lib: libzkw.so of the parent commit"
+    if not {"gate", "batched"} <= set(a.skip):
+        assert a.parent_lib and os.path.exists(a.parent_lib), "--parent-lib: libzkw.so of the parent commit"
     plan = [("tables", "tables", False, 240)]
     plan += [x for _ in range(5) for x in (("gate", "gate_full", True, 240), ("gate", "gate_witness", False, 240))]
     plan += [x for _ in range(3) for x in (("batched", "batched_full", True, 420), ("batched", "batched_witness", False, 420))]
+    plan += [("advance", "advance", False, 420)]
     result = {"source": "tools/probe_storage_witness_tree.py on one MI355X; wall-clock times around synchronised calls", "steps": {}}
     rc = 0
 
