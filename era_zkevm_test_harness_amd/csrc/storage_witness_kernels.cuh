@@ -404,4 +404,214 @@ static __device__ __forceinline__ void k_swa_paths(const VB& vb, SwaFold f, cons
     dst[1] = src[1];
 }
 
+// ------------------------------------------------------------------------------------------------ chain
+// zkw_storage_tree_advance_witness_chain: the pre-states of K consecutive blocks out of ONE table over (at least) the union of their
+// slots, in one call. out[k] is a table of block k's OWN keys in the state after blocks 0 .. k - 1; one working copy of the union is
+// advanced in place and becomes the final state. The key set is fixed, so an entry never moves: E = the table's entries, N = the
+// queries of all blocks, flat index (k, e) = k E + e.
+//   * locate (k_swc_locate): a thread per position p of all blocks (a query, or a pair of the pair form: always a write): its block by binary search over the offsets, its entry by lower
+//     bound; READS are located too (the block will look them up). touched[k E + e] = 1; a write leaves first / last[k E + e]
+//     (atomicMin / atomicMax of the global position) and cfirst[e] = the first writing position of the whole chain; a miss raises
+//     meta[0] to at least N - p, so the first bad (block, position) falls out;
+//   * ranks: flag_prefix over the K E touched flags (trank: where (k, e) goes in out[k], already sorted because the union is), over
+//     the K E written flags (wrank: the written lists W_k back to back, `bound` = min(N, K E) slots) and over the positions (new_rank:
+//     the first write of the chain to an entry whose index is 0). k_swc_compact leaves wlist / wblk and the per-block bases tbase,
+//     wbase [K + 1] next to the miss word: the FIRST readback, which sizes the K tables;
+//   * walk (k_swc_walk): a thread per entry walks k = 0 .. K - 1 with its current (index, value): writes them with the key into
+//     out[k] where block k touches the entry, then applies block k's last write and leaves the new leaf hash, d and nxt at its slot
+//     of W_k. Counts the new leaves per block and the present entries per table; its last state goes into the working table;
+//   * the wavefront (k_swc_step, one launch per step s = 0 .. 256 + K - 2): block k is at height L = s - k.
+//       fold: a range start of W_k at height L makes its parent (swa_parent) from its hash and the next range's when that lies under
+//       the same parent, else the WORKING table's path[L] of its entry. Two heights per block (ping-pong on L & 1); height 256 is
+//       block k's root.
+//       update and capture: thread (k, e) reads the working cell path[e][L]; if block k touches e the old cell is out[k]'s path[L];
+//       if a key of W_k lies under e's sibling subtree at L (k_swa_paths' lower bound over W_k) that node's hash replaces the cell.
+//     The fold reads a cell only where no written key of block k lies under the sibling — where the update does not write. The
+//     other blocks of the step are at other levels, and blocks < k were at level L in earlier steps: a step is race-free in place.
+// Scratch, in 32-bit words: 5 K E + 2 (touched, first, last, trank, wrank) + E (cfirst) + 2 N + 1 (ent, new_rank) + 20 bound (wlist,
+// wblk, d, nxt, two heights of 8 words) + 2 K + 18 (the first readback) + 10 K + 1 (the second: roots, new leaves, present entries)
+// + 9 K + 1 (the offsets and the K tables' pointers) = 5 K E + E + 2 N + 20 bound + 21 K + 23.
+constexpr int SWC_HDR_MISSING = 0;  // k_sw_lookup's convention over the N positions of the chain
+constexpr int SWC_HDR_WORDS = 16;   // tbase [K + 1] and wbase [K + 1] follow
+
+// all blocks' queries (or pairs: each one a write) back to back; offs [K + 1] in device memory
+struct SwcQueries {
+    SwaWrites wr;
+    const u32* offs;
+    u32 blocks;
+};
+
+static __device__ __forceinline__ void k_swc_locate(const VB& vb, SwView t, SwcQueries cq, u32* __restrict__ ent, u32* __restrict__ touched,
+                                                    u32* __restrict__ first, u32* __restrict__ last, u32* __restrict__ cfirst, u32* __restrict__ hdr) {
+    const u64 p = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (p >= cq.wr.n) return;
+    u32 k = 0, kh = cq.blocks;  // the last block that starts at or before p (an empty block starts where the next one does)
+    while (kh - k > 1) {
+        const u32 mid = (k + kh) >> 1;
+        if (cq.offs[mid] <= p) k = mid; else kh = mid;
+    }
+    u32 key[8];
+    if (cq.wr.queries) {
+        sap_derive_key(cq.wr.queries + p, key);
+    } else {
+#pragma unroll
+        for (int w = 0; w < 8; w++) key[w] = cq.wr.keys[8 * p + w];
+    }
+    u64 lo = 0, hi = t.n;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (st_cmp(t.keys + 8 * mid, key) < 0) lo = mid + 1; else hi = mid;
+    }
+    const bool hit = lo < t.n && st_cmp(t.keys + 8 * lo, key) == 0;
+    ent[p] = hit ? (u32)lo : SWA_NONE;
+    if (!hit) {
+        atomicMax(hdr + SWC_HDR_MISSING, (u32)(cq.wr.n - p));
+        return;
+    }
+    const u64 i = (u64)k * t.n + lo;
+    touched[i] = 1;
+    if (cq.wr.writes(p)) {
+        atomicMin(first + i, (u32)p);
+        atomicMax(last + i, (u32)p);
+        atomicMin(cfirst + lo, (u32)p);
+    }
+}
+struct SwcTouchedFlag {
+    const u32* touched;
+    __device__ __forceinline__ u32 operator()(size_t i) const { return touched[i] != 0; }
+};
+// position p is the first write of the chain to an entry that is absent before block 0
+struct SwcNewFlag {
+    const u32 *ent, *cfirst;
+    const u64* index;
+    __device__ __forceinline__ u32 operator()(size_t p) const {
+        const u32 e = ent[p];
+        return e != SWA_NONE && cfirst[e] == (u32)p && index[e] == 0;
+    }
+};
+
+// what the walk and the wavefront work on
+struct SwcChain {
+    const u32* keys;      // [E][8]: the union's keys
+    SwTable work;         // the working copy of the union: the state after the blocks that have passed a level
+    const SwTable* outs;  // [K]
+    const u32 *touched, *first, *trank, *wrank;  // [K E], the ranks [K E + 1]
+    const u32 *tbase, *wbase;                    // [K + 1]
+    u32 *wlist, *wblk, *d, *nxt;                 // [bound]: W_0, W_1, ... back to back
+    u32* h;                                      // [2][bound][8]: height L of a block at h[L & 1]
+    u32* fin;                                    // [8 K] roots, [K] new leaves, [K + 1] present entries (the last: the final table's)
+    u64 entries, bound;
+    u32 blocks;
+};
+
+static __device__ __forceinline__ void k_swc_compact(const VB& vb, SwcChain c, u32* __restrict__ tbase, u32* __restrict__ wbase) {
+    const u64 i = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (i <= c.blocks) {
+        tbase[i] = c.trank[i * c.entries];
+        wbase[i] = c.wrank[i * c.entries];
+    }
+    if (i >= (u64)c.blocks * c.entries || c.first[i] == SWA_NONE) return;
+    const u32 w = c.wrank[i];
+    c.wlist[w] = (u32)(i % c.entries);
+    c.wblk[w] = (u32)(i / c.entries);
+}
+
+static __device__ __forceinline__ void k_swc_walk(const VB& vb, const SwcChain& c, SwaWrites wr, const u64* __restrict__ index0,
+                                                  const u32* __restrict__ values0, const u32* __restrict__ last, const u32* __restrict__ cfirst,
+                                                  const u32* __restrict__ new_rank, u64 next_index) {
+    const u64 e = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (e >= c.entries) return;
+    u64 index = index0[e];
+    u32 key[8], v[8], h[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) { key[w] = c.keys[8 * e + w]; v[w] = values0[8 * e + w]; }
+    for (u32 k = 0; k < c.blocks; k++) {
+        const u64 i = (u64)k * c.entries + e;
+        if (!c.touched[i]) continue;
+        const SwTable o = c.outs[k];
+        const u64 j = c.trank[i] - c.tbase[k];
+        o.index[j] = index;
+#pragma unroll
+        for (int w = 0; w < 8; w++) { o.keys[8 * j + w] = key[w]; o.values[8 * j + w] = v[w]; }
+        if (index) atomicAdd(c.fin + 9 * (u64)c.blocks + k, 1u);
+        if (c.first[i] == SWA_NONE) continue;
+        if (index == 0) {
+            index = next_index + new_rank[cfirst[e]];
+            atomicAdd(c.fin + 8 * (u64)c.blocks + k, 1u);
+        }
+        const u64 p = last[i];
+#pragma unroll
+        for (int w = 0; w < 8; w++) v[w] = wr.value_word(p, w);
+        sap_leaf_hash_bytes(index, v, h);
+        const u32 w = c.wrank[i];
+#pragma unroll
+        for (int q = 0; q < 8; q++) c.h[8 * (u64)w + q] = h[q];
+        c.d[w] = w > c.wbase[k] ? (u32)st_top_diff(c.keys + 8 * e, c.keys + 8 * (u64)c.wlist[w - 1]) : (u32)ST_DEPTH;
+        c.nxt[w] = w + 1;
+    }
+    c.work.index[e] = index;
+#pragma unroll
+    for (int w = 0; w < 8; w++) c.work.values[8 * e + w] = v[w];
+    if (index) atomicAdd(c.fin + 10 * (u64)c.blocks, 1u);
+}
+
+// one step of the wavefront: the first `fold_wgs` workgroups fold (a thread per slot of the written lists), the others update and
+// capture (a thread per (entry, block), the blocks of an entry side by side: their cells at levels s - k are neighbours in memory)
+static __device__ __forceinline__ void k_swc_step(const VB& vb, const SwcChain& c, u32 fold_wgs, int s) {
+    if (vb.x < fold_wgs) {
+        const u64 i = (u64)vb.x * blockDim.x + threadIdx.x;
+        if (i >= c.wbase[c.blocks]) return;
+        const u32 k = c.wblk[i];
+        const int L = s - (int)k;
+        if (L < 0 || L >= ST_DEPTH || c.d[i] <= (u32)L) return;  // not the first written key of a node of height L + 1
+        const u32 m = c.nxt[i];
+        const bool has_sibling = m < c.wbase[k + 1] && c.d[m] == (u32)L;
+        const u32* cur = c.h + (u64)(L & 1) * c.bound * 8;
+        u32 o[8];
+        swa_parent(SwView{c.keys, nullptr, nullptr, c.work.paths, c.entries}, L, c.wlist[i], cur + 8 * i, has_sibling ? cur + 8 * (u64)m : nullptr, o);
+        u32* out = c.h + ((u64)((L + 1) & 1) * c.bound + i) * 8;
+#pragma unroll
+        for (int q = 0; q < 8; q++) out[q] = o[q];
+        if (L + 1 == ST_DEPTH)
+            for (int q = 0; q < 8; q++) c.fin[8 * (u64)k + q] = o[q];
+        if (has_sibling) c.nxt[i] = c.nxt[m];  // (k_swa_level: m starts no node of height L + 1)
+        return;
+    }
+    const u64 u = (u64)(vb.x - fold_wgs) * blockDim.x + threadIdx.x;
+    if (u >= c.entries * c.blocks) return;
+    const u64 e = u / c.blocks;
+    const u32 k = (u32)(u % c.blocks);
+    const int L = s - (int)k;
+    if (L < 0 || L >= ST_DEPTH) return;
+    const u64 i = (u64)k * c.entries + e;
+    const bool touched = c.touched[i] != 0;
+    const u32 w0 = c.wbase[k], w1 = c.wbase[k + 1];
+    if (!touched && w0 == w1) return;
+    uint4* cell = reinterpret_cast<uint4*>(c.work.paths + (e * ST_DEPTH + L) * 8);
+    if (touched) {
+        uint4* dst = reinterpret_cast<uint4*>(c.outs[k].paths + ((u64)(c.trank[i] - c.tbase[k]) * ST_DEPTH + L) * 8);
+        dst[0] = cell[0];
+        dst[1] = cell[1];
+    }
+    if (w0 == w1) return;
+    // the sibling subtree at level L: the key with bit L flipped and the bits below cleared (k_swa_paths)
+    u32 key[8];
+    const int wl = L >> 5;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        const u32 x = c.keys[8 * e + w];
+        key[w] = w < wl ? 0u : w == wl ? (x ^ (1u << (L & 31))) & ~((1u << (L & 31)) - 1u) : x;
+    }
+    u32 lo = w0, hi = w1;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (st_cmp(c.keys + 8 * (u64)c.wlist[mid], key) < 0) lo = mid + 1; else hi = mid;
+    }
+    if (lo < w1 && st_top_diff(c.keys + 8 * (u64)c.wlist[lo], key) < L) {  // a written key of block k under the sibling: lo starts its range
+        const uint4* src = reinterpret_cast<const uint4*>(c.h + ((u64)(L & 1) * c.bound + lo) * 8);
+        cell[0] = src[0];
+        cell[1] = src[1];
+    }
+}
+
 }  // namespace zkw

@@ -510,3 +510,162 @@ extern "C" int zkw_storage_tree_advance_witness_by_queries(const zkw_storage_tre
     // (n == 0: no query is read, and SwaWrites with queries == NULL is the pair form with no pair)
     return sw_advance(who, witness, ctx, SwaWrites{d_q, nullptr, nullptr, (u64)n}, out);
 }
+
+// ------------------------------------------------------------------------------------------------ a chain of K blocks in one call
+// storage_witness_kernels.cuh, "chain". Two readbacks: the blocks' entry counts with the miss word (the K tables are allocated after
+// it), and the roots and counts at the end. The 256 + K - 1 steps of the wavefront are plain launches on ctx's stream.
+static int sw_chain(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx, SwaWrites wr, const std::vector<u32>& offs, zkw_storage_tree** out,
+                    zkw_storage_tree** final_state) {
+    const size_t K = offs.size() - 1, E = src->cap, N = offs[K], KE = K * E;
+    const size_t bound = std::min(N, KE);  // >= the written (block, entry) pairs
+    u32 *flags = nullptr, *trank = nullptr, *wrank = nullptr, *cfirst = nullptr, *ent = nullptr, *new_rank = nullptr, *wl = nullptr, *h = nullptr, *hdr = nullptr,
+        *fin = nullptr, *d_offs = nullptr;
+    ZKW_TRY(ctx->scratch_t<u32>("swc_flags", 3 * KE, &flags));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_trank", KE + 1, &trank));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_wrank", KE + 1, &wrank));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_cfirst", E, &cfirst));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_ent", N, &ent));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_new_rank", N + 1, &new_rank));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_wlists", 4 * bound, &wl));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_heights", 16 * bound, &h));
+    const size_t hdr_words = SWC_HDR_WORDS + 2 * (K + 1), fin_words = 10 * K + 1;
+    ZKW_TRY(ctx->scratch_t<u32>("swc_hdr", hdr_words, &hdr));
+    ZKW_TRY(ctx->scratch_t<u32>("swc_fin", fin_words, &fin));
+    ZKW_TRY(ctx->upload("swc_offs", offs, &d_offs));
+    u32 *touched = flags, *first = flags + KE, *last = flags + 2 * KE, *tbase = hdr + SWC_HDR_WORDS, *wbase = tbase + K + 1;
+    const SwView tv = src->table();
+    SwcChain c{tv.keys, SwTable{}, nullptr, touched, first, trank, wrank, tbase, wbase, wl, wl + bound, wl + 2 * bound, wl + 3 * bound, h, fin, (u64)E, (u64)bound, (u32)K};
+    // locate, ranks, and the first readback
+    std::vector<u32> h_hdr(hdr_words);
+    {
+        if (KE) {
+            HIP_TRY(ctx->memset_async(touched, 0, KE * sizeof(u32)));
+            HIP_TRY(ctx->memset_async(first, 0xFF, KE * sizeof(u32)));
+            HIP_TRY(ctx->memset_async(last, 0, KE * sizeof(u32)));
+            HIP_TRY(ctx->memset_async(cfirst, 0xFF, E * sizeof(u32)));
+        }
+        HIP_TRY(ctx->memset_async(hdr, 0, hdr_words * sizeof(u32)));
+        HIP_TRY(ctx->memset_async(fin, 0, fin_words * sizeof(u32)));
+        { Prof _p(ctx, "k_swc_locate"); ZKW_LAUNCH(ctx, k_swc_locate, blocks_for(N, 64), 64, tv, SwcQueries{wr, d_offs, (u32)K}, ent, touched, first, last, cfirst, hdr); }
+        ZKW_TRY(flag_prefix(ctx, "k_swc_trank", SwcTouchedFlag{touched}, KE, trank));
+        ZKW_TRY(flag_prefix(ctx, "k_swc_wrank", SwaWrittenFlag{first}, KE, wrank));
+        ZKW_TRY(flag_prefix(ctx, "k_swc_new_rank", SwcNewFlag{ent, cfirst, tv.index}, N, new_rank));
+        { Prof _p(ctx, "k_swc_compact"); ZKW_LAUNCH(ctx, k_swc_compact, blocks_for(std::max(KE, K + 1), 256), 256, c, tbase, wbase); }
+        ZKW_TRY(ctx->read_small(h_hdr.data(), hdr, hdr_words * sizeof(u32)));
+    }
+    if (h_hdr[SWC_HDR_MISSING]) {
+        const size_t p = N - h_hdr[SWC_HDR_MISSING];
+        size_t k = 0;
+        while (offs[k + 1] <= p) k++;
+        return fail(ZKW_ERR_INVALID, "%s: the key at (block %zu, position %zu) is not in the witness tree", who, k, p - offs[k]);
+    }
+    const u32 *h_tbase = h_hdr.data() + SWC_HDR_WORDS, *h_wbase = h_tbase + K + 1;
+    // the K tables and the working copy
+    std::vector<zkw_storage_tree*> made;
+    auto drop_all = [&](int rc) {
+        (void)ctx->sync_stream();  // nothing queued may still write a table
+        for (zkw_storage_tree* t : made) { t->release(); delete t; }
+        return rc;
+    };
+    for (size_t k = 0; k <= K; k++) {
+        zkw_storage_tree* t = nullptr;
+        const int rc = sw_alloc(ctx, k < K ? h_tbase[k + 1] - h_tbase[k] : E, who, &t);
+        if (rc != ZKW_OK) return drop_all(rc);
+        made.push_back(t);
+    }
+    zkw_storage_tree* work = made[K];
+    std::vector<u32> h_fin(fin_words);
+    int rc = [&]() -> int {
+        std::vector<SwTable> tabs(K);
+        for (size_t k = 0; k < K; k++) tabs[k] = SwTable{made[k]->keys[0], made[k]->index[0], made[k]->values[0], made[k]->paths};
+        SwTable* d_tabs = nullptr;
+        ZKW_TRY(ctx->upload("swc_tables", tabs, &d_tabs));
+        c.outs = d_tabs;
+        c.work = SwTable{work->keys[0], work->index[0], work->values[0], work->paths};
+        if (E) {
+            HIP_TRY(ctx->copy_async(work->keys[0], tv.keys, E * 32, hipMemcpyDeviceToDevice));
+            Prof _p(ctx, "swc_copy_paths");
+            HIP_TRY(ctx->copy_async(work->paths, tv.paths, E * (size_t)ST_DEPTH * 32, hipMemcpyDeviceToDevice));
+        }
+        { Prof _p(ctx, "k_swc_walk"); ZKW_LAUNCH(ctx, k_swc_walk, blocks_for(E, 64), 64, c, wr, tv.index, tv.values, (const u32*)last, (const u32*)cfirst, (const u32*)new_rank, src->next_index); }
+        const unsigned fold_wgs = blocks_for(h_wbase[K], 256), all_wgs = fold_wgs + blocks_for(KE, 256);
+        if (h_tbase[K])  // (a chain without a query captures and folds nothing)
+            for (int s = 0; s < ST_DEPTH + (int)K - 1; s++) {
+                Prof _p(ctx, "k_swc_step");
+                ZKW_LAUNCH(ctx, k_swc_step, all_wgs, 256, c, fold_wgs, s);
+            }
+        return ctx->read_small(h_fin.data(), fin, fin_words * sizeof(u32));
+    }();
+    if (rc != ZKW_OK) return drop_all(rc);
+    // roots and indices are carried over the blocks: a block without writes leaves the state as it is
+    uint8_t root[32];
+    memcpy(root, src->root, 32);
+    u64 next = src->next_index;
+    for (size_t k = 0; k <= K; k++) {
+        zkw_storage_tree* t = made[k];
+        memcpy(t->root, root, 32);
+        t->next_index = next;
+        t->n = h_fin[9 * K + k];
+        if (k < K && h_wbase[k + 1] != h_wbase[k]) memcpy(root, h_fin.data() + 8 * k, 32);
+        if (k < K) next += h_fin[8 * K + k];
+    }
+    if (final_state) {
+        *final_state = work;
+        ctx_retain(ctx);
+    } else {
+        work->release();  // (the readback has synchronised the stream)
+        delete work;
+    }
+    for (size_t k = 0; k < K; k++) {
+        out[k] = made[k];
+        ctx_retain(ctx);
+    }
+    return ZKW_OK;
+}
+
+// the argument checks of both forms; offs = the offsets as the kernels take them
+static int sw_chain_check(const char* who, const zkw_storage_tree* w, zkw_ctx* ctx, bool have_input, const uint64_t* block_offsets, size_t n_blocks,
+                          zkw_storage_tree** out, zkw_storage_tree** final_state, std::vector<u32>* offs) {
+    if (!w || !ctx || !block_offsets || !out) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (n_blocks == 0) return fail(ZKW_ERR_INVALID, "%s: no blocks", who);
+    if (block_offsets[0] != 0) return fail(ZKW_ERR_INVALID, "%s: block_offsets[0] is %llu, not 0", who, (unsigned long long)block_offsets[0]);
+    for (size_t k = 0; k < n_blocks; k++)
+        if (block_offsets[k + 1] < block_offsets[k]) return fail(ZKW_ERR_INVALID, "%s: block_offsets decrease at block %zu", who, k);
+    const uint64_t n = block_offsets[n_blocks];
+    if (n && !have_input) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (!w->witness) return fail(ZKW_ERR_INVALID, "%s: the source is a full tree; it takes zkw_storage_tree_insert / _apply_queries", who);
+    if (ctx->device != w->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the tree lives on device %d, the context on device %d", who, w->ctx->device, ctx->device);
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "%s: the context belongs to a batch of blocks", who);
+    if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "%s: at most 2^31 - 1 queries", who);
+    if ((uint64_t)n_blocks * std::max<uint64_t>(w->cap, 1) >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "%s: %zu blocks x %zu entries are 2^31 or more", who, n_blocks, w->cap);
+    for (size_t k = 0; k < n_blocks; k++) out[k] = nullptr;
+    if (final_state) *final_state = nullptr;
+    offs->assign(block_offsets, block_offsets + n_blocks + 1);
+    return ZKW_OK;
+}
+
+extern "C" int zkw_storage_tree_advance_witness_chain(const zkw_storage_tree* witness, zkw_ctx* ctx, const zkw_log_query* queries, const uint64_t* block_offsets,
+                                                      size_t n_blocks, zkw_storage_tree** out, zkw_storage_tree** final_state) {
+    static const char who[] = "zkw_storage_tree_advance_witness_chain";
+    std::vector<u32> offs;
+    ZKW_TRY(sw_chain_check(who, witness, ctx, queries != nullptr, block_offsets, n_blocks, out, final_state, &offs));
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = offs[n_blocks];
+    const zkw_log_query* d_q = nullptr;
+    ZKW_TRY(ctx->in("swc_in_queries", queries, n, &d_q));
+    // (n == 0: no query is read, and SwaWrites with queries == NULL is the pair form with no pair)
+    return sw_chain(who, witness, ctx, SwaWrites{d_q, nullptr, nullptr, (u64)n}, offs, out, final_state);
+}
+
+extern "C" int zkw_storage_tree_advance_witness_chain_pairs(const zkw_storage_tree* witness, zkw_ctx* ctx, const uint8_t* keys, const uint8_t* values,
+                                                            const uint64_t* block_offsets, size_t n_blocks, zkw_storage_tree** out, zkw_storage_tree** final_state) {
+    static const char who[] = "zkw_storage_tree_advance_witness_chain_pairs";
+    std::vector<u32> offs;
+    ZKW_TRY(sw_chain_check(who, witness, ctx, keys && values, block_offsets, n_blocks, out, final_state, &offs));
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = offs[n_blocks];
+    const uint8_t *d_k = nullptr, *d_v = nullptr;
+    ZKW_TRY(ctx->in("swc_in_keys", keys, n * 32, &d_k));
+    ZKW_TRY(ctx->in("swc_in_values", values, n * 32, &d_v));
+    return sw_chain(who, witness, ctx, SwaWrites{nullptr, reinterpret_cast<const u32*>(d_k), reinterpret_cast<const u32*>(d_v), (u64)n}, offs, out, final_state);
+}

@@ -176,6 +176,8 @@ SYMBOLS = [
     ("zkw_storage_tree_extract_witness", _int, [_vp, _vp, _vp, _sz, C.POINTER(_vp)]),
     ("zkw_storage_tree_advance_witness", _int, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_vp)]),
     ("zkw_storage_tree_advance_witness_by_queries", _int, [_vp, _vp, _vp, _sz, C.POINTER(_vp)]),
+    ("zkw_storage_tree_advance_witness_chain", _int, [_vp, _vp, _vp, C.POINTER(C.c_uint64), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("zkw_storage_tree_advance_witness_chain_pairs", _int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     ("zkw_storage_tree_is_witness", _int, [_vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
@@ -656,6 +658,58 @@ class StorageTreeDevice:
             qp, n = (_np_ptr(q) if q.size else None), q.size
         _check(load().zkw_storage_tree_advance_witness_by_queries(self.handle, ctx.handle, qp, n, C.byref(w.handle)))
         return w
+
+    def advance_chain(self, blocks_queries, ctx=None, final=False):
+        """zkw_storage_tree_advance_witness_chain: the pre-states of K consecutive blocks in one call. `blocks_queries`: a list of
+        LOG_QUERY arrays (torch uint8 tensors of them in device pointer mode), block k's deduplicated storage queue, reads and writes.
+        Returns the list of K witness trees — table k holds block k's own keys in the state after blocks 0 .. k - 1 — or
+        (tables, final_table) with `final=True`: this table's keys in the state after the last block. This one stays as it is. A query
+        whose key is outside this table, a read too, raises ZkwError(ERR_INVALID) naming its block and position."""
+        ctx = ctx or self.ctx
+        probe = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
+        if probe._device_mode():
+            import torch
+
+            parts = [b.contiguous().reshape(-1).view(torch.uint8) for b in blocks_queries]
+            counts = [p.numel() // LOG_QUERY.itemsize for p in parts]
+            q = torch.cat(parts) if sum(counts) else None
+            if q is not None:
+                torch.cuda.synchronize(q.device)  # joined on torch's stream, read on the context's
+            qp = C.c_void_p(q.data_ptr()) if q is not None else None
+        else:
+            parts = [np.ascontiguousarray(b, dtype=LOG_QUERY).reshape(-1) for b in blocks_queries]
+            counts = [p.size for p in parts]
+            q = np.concatenate(parts) if parts else np.zeros(0, LOG_QUERY)
+            qp = _np_ptr(q) if q.size else None
+        return self._chain(ctx, "zkw_storage_tree_advance_witness_chain", (qp,), counts, final)
+
+    def advance_chain_pairs(self, blocks_pairs, ctx=None, final=False):
+        """zkw_storage_tree_advance_witness_chain_pairs: `advance_chain` for blocks given as (keys, values) as `advance` takes them:
+        every pair is a write"""
+        ctx = ctx or self.ctx
+        probe = StorageTreeDevice._adopt(ctx, C.c_void_p(None))
+        rows = [(probe._rows32(k)[2], probe._rows32(v)[2]) for k, v in blocks_pairs]
+        counts = [k.shape[0] for k, _v in rows]
+        if probe._device_mode() and rows:
+            import torch
+
+            keys, values = torch.cat([k for k, _v in rows]), torch.cat([v for _k, v in rows])
+            torch.cuda.synchronize(keys.device)  # joined on torch's stream, read on the context's
+        else:
+            keys, values = (np.concatenate([x[i] for x in rows]) if rows else np.zeros((0, 32), np.uint8) for i in (0, 1))
+        assert counts == [v.shape[0] for _k, v in rows]
+        kp, _n, _k = probe._rows32(keys)
+        vp, _n, _v = probe._rows32(values)
+        return self._chain(ctx, "zkw_storage_tree_advance_witness_chain_pairs", (kp, vp), counts, final)
+
+    def _chain(self, ctx, symbol, inputs, counts, final):
+        k = len(counts)
+        offsets = (C.c_uint64 * (k + 1))(*([0] + [int(x) for x in np.cumsum(counts, dtype=np.int64)]))
+        handles = (_vp * max(k, 1))()
+        last = _vp(None)
+        _check(getattr(load(), symbol)(self.handle, ctx.handle, *inputs, offsets, k, handles, C.byref(last) if final else None))
+        tables = [StorageTreeDevice._adopt(ctx, C.c_void_p(handles[i])) for i in range(k)]
+        return (tables, StorageTreeDevice._adopt(ctx, C.c_void_p(last.value))) if final else tables
 
     @property
     def is_witness(self) -> bool:

@@ -671,6 +671,35 @@ int zkw_storage_tree_advance_witness(const zkw_storage_tree *witness, zkw_ctx *c
    table is no error). queries follow ctx's pointer mode; an error names the position of the QUERY. */
 int zkw_storage_tree_advance_witness_by_queries(const zkw_storage_tree *witness, zkw_ctx *ctx, const zkw_log_query *queries,
                                                 size_t n, zkw_storage_tree **out);
+/* A chain: the pre-states of n_blocks consecutive blocks in ONE call, each as a table of the block's OWN keys. `witness` is a table
+   over at least the union of the blocks' slots in the state before block 0 (from proofs, an extraction or an earlier advance); it
+   is only read. Block k's queries are queries[block_offsets[k] .. block_offsets[k + 1]): its deduplicated storage queue
+   (ZKW_STO_RESULT_QUERIES), reads and writes. queries follow ctx's pointer mode; block_offsets [n_blocks + 1] and out [n_blocks]
+   are host arrays. out[k] is a NEW witness tree in the state after blocks 0 .. k - 1 that holds exactly the distinct
+   derive_final_address keys of block k's queries, reads included: root, _next_enumeration_index and _num_leaves (its present
+   entries) are that state's, _capacity its entry count; a block without queries gives a table of 0 entries with the state's root
+   and index. Its contents equal, byte for byte, what k calls of zkw_storage_tree_advance_witness_by_queries on the union table
+   give for those keys, at 8 264 bytes per slot the block touches instead of per slot of the union. *final_state (if not NULL)
+   is the union table in the state after the last block: the next chain starts from it. A write follows
+   zkw_storage_tree_advance_witness: the last value stays; an absent key becomes present at its first write over the whole chain
+   with index next_enumeration_index + its rank among the chain's newly present keys in array order across blocks, a zero value
+   too. Errors return nothing — every out[k] and *final_state are NULL, and nothing queued still writes anywhere. ZKW_ERR_INVALID:
+   a NULL argument, a full tree as `witness`, a context of another device or of a batch, n_blocks == 0, block_offsets[0] != 0,
+   decreasing offsets; and a query, a READ or a write, whose key is not in `witness` (the block will look it up): zkw_last_error
+   names the block and the position inside the block of the first such query in (block, position) order. ZKW_ERR_OOM: no memory,
+   before anything is returned. Device scratch of ctx, in 32-bit words, for E entries of `witness`, K blocks and N queries in all:
+   5 K E + E + 2 N + 20 min(N, K E) + 21 K + 23, next to one working copy of the union (8 264 E bytes, handed out as *final_state
+   or freed). Two readbacks in the whole call; the 256 + K - 1 steps in between are plain launches on ctx's stream.
+   Which route at which K: docs/KERNELS.md §3.23, "A chain of K blocks in one call". */
+int zkw_storage_tree_advance_witness_chain(const zkw_storage_tree *witness, zkw_ctx *ctx, const zkw_log_query *queries,
+                                           const uint64_t *block_offsets /*[n_blocks + 1], HOST*/, size_t n_blocks,
+                                           zkw_storage_tree **out /*[n_blocks], HOST*/,
+                                           zkw_storage_tree **final_state /* may be NULL */);
+/* the same for pairs, as zkw_storage_tree_advance_witness takes them: block k inserts (keys[i], values[i]) for i in
+   block_offsets[k] .. block_offsets[k + 1]) one after another; every pair is a write, and out[k] holds the block's distinct keys. */
+int zkw_storage_tree_advance_witness_chain_pairs(const zkw_storage_tree *witness, zkw_ctx *ctx, const uint8_t *keys /*[n][32]*/,
+                                                 const uint8_t *values /*[n][32]*/, const uint64_t *block_offsets, size_t n_blocks,
+                                                 zkw_storage_tree **out, zkw_storage_tree **final_state);
 int zkw_storage_tree_is_witness(const zkw_storage_tree *tree);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */

@@ -23,6 +23,13 @@ Every GPU step is a child process of its own under its own time limit; the steps
                  apply_queries on a full tree of 2^20 leaves (code this library has unchanged), five runs, with its min-max spread; then
                  the tables of 64 consecutive blocks of 30 slots each: one extraction of the union + 63 advances against 64 x (extraction +
                  apply_queries), and their HBM
+  chain          zkw_storage_tree_advance_witness_chain (-> profiles/r13/storage_witness_chain.json; needs no parent library:
+                 `--skip tables --skip gate --skip batched --skip advance --out profiles/r13/storage_witness_chain.json`): K = 64, 16, 4
+                 and 1 consecutive blocks of 30 slots each, every slot written, over the table of the 64 blocks' union (1 920 entries).
+                 In one process, wall clock around the synchronised calls, warm, five runs each: the chain call without and with the
+                 final state, and the parent commit's route on the same table (code this library has unchanged) — K - 1 calls of
+                 advance_by_queries for the K pre-states, K calls for the final state too — with its min-max spread; one profiled chain
+                 call for the split; the HBM of both routes
 """
 import argparse
 import json
@@ -202,6 +209,72 @@ def step_advance():
     return out
 
 
+def step_chain():
+    import numpy as np
+
+    from era_zkevm_test_harness_amd import native as nv, synthetic
+
+    ctx = nv.Context(0)
+    rng = np.random.default_rng(47)
+    n_full, K_max, slots = 1 << 16, 64, 30
+    q = np.ascontiguousarray(synthetic.storage_application_trace(K_max * slots, seed=5)[0], dtype=nv.LOG_QUERY)
+    q["rw_flag"] = 1
+    qkeys = np.frombuffer(b"".join(synthetic.derive_final_address(x) for x in q), np.uint8).reshape(-1, 32)
+    leaves = rng.integers(0, 256, size=(n_full - K_max * slots, 32), dtype=np.uint8)
+    leaves[:K_max * slots // 2] = qkeys[::2]  # every other slot exists before the first block
+    full = nv.StorageTreeDevice(ctx, n_full)
+    full.insert(leaves, rng.integers(0, 256, size=leaves.shape, dtype=np.uint8))
+    union = full.extract_witness(qkeys)
+    full.free()
+    entries = int(union.capacity)
+    out = {"union_entries": entries, "slots_per_block": slots, "bytes_per_entry": BYTES_PER_ENTRY, "blocks": {}}
+
+    def free(x):
+        for t in x if isinstance(x, (list, tuple)) else [x]:
+            free(t) if isinstance(t, (list, tuple)) else t.free()
+
+    def sequential(blocks, calls):
+        tables = [union]
+        for b in blocks[:calls]:
+            tables.append(tables[-1].advance_by_queries(b))
+        return tables[1:]
+
+    def five(fn):
+        free(fn())  # warm: scratch, buffers
+        walls = []
+        for _ in range(5):
+            ms, r = _time_ms(fn, ctx.synchronize)
+            walls.append(ms)
+            free(r)
+        return walls
+
+    for K in (64, 16, 4, 1):
+        blocks = [q[k * slots:(k + 1) * slots] for k in range(K)]
+        rec = {}
+        for what, final in (("pre_states", False), ("pre_states_and_final", True)):
+            new = five(lambda: union.advance_chain(blocks, final=final))
+            parent = five(lambda: sequential(blocks, K if final else K - 1))
+            spread = max(parent) - min(parent)
+            mn, mp = statistics.median(new), statistics.median(parent)
+            rec[what] = {"chain_wall_ms": [round(x, 4) for x in new], "chain_median_ms": round(mn, 4),
+                         "sequential_calls": K if final else K - 1, "sequential_wall_ms": [round(x, 4) for x in parent], "sequential_median_ms": round(mp, 4),
+                         "sequential_min_max_spread_ms": round(spread, 4), "below_sequential_median_minus_spread": bool(mn < mp - spread)}
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        tables = union.advance_chain(blocks)
+        prof = ctx.profile()
+        ctx.profile_enable(False)
+        rec["chain_kernels_ms_launches_profiled_run"] = {k: [round(v[0], 4), int(v[1])] for k, v in prof.items()} if isinstance(prof, dict) else prof
+        own = sum(t.capacity for t in tables)
+        free(tables)
+        rec["hbm_bytes"] = {"chain_tables": own * BYTES_PER_ENTRY, "chain_working_copy_of_the_union": entries * BYTES_PER_ENTRY,
+                            "chain_scratch": 4 * (5 * K * entries + entries + 2 * K * slots + 20 * min(K * slots, K * entries) + 21 * K + 23),
+                            "sequential_tables": K * entries * BYTES_PER_ENTRY}
+        out["blocks"][str(K)] = rec
+    union.free()
+    return out
+
+
 def _production_block_and_pairs(nv, synthetic, np, seed):
     """(generated on the host in tens of seconds: the probe's child processes share one copy per seed in the temporary directory, keyed on
     the generator's source so that a copy from another version of it is never read)"""
@@ -292,6 +365,8 @@ def run_step(name):
         return step_tables()
     if name == "advance":
         return step_advance()
+    if name == "chain":
+        return step_chain()
     if name in ("gate_full", "gate_witness"):
         return step_gate_one(name == "gate_witness")
     if name in ("batched_full", "batched_witness"):
@@ -321,7 +396,7 @@ def main():
     plan = [("tables", "tables", False, 240)]
     plan += [x for _ in range(5) for x in (("gate", "gate_full", True, 240), ("gate", "gate_witness", False, 240))]
     plan += [x for _ in range(3) for x in (("batched", "batched_full", True, 420), ("batched", "batched_witness", False, 420))]
-    plan += [("advance", "advance", False, 420)]
+    plan += [("advance", "advance", False, 420), ("chain", "chain", False, 300)]
     result = {"source": "tools/probe_storage_witness_tree.py on one MI355X; wall-clock times around synchronised calls", "steps": {}}
     rc = 0
 
