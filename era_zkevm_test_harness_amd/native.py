@@ -179,6 +179,12 @@ SYMBOLS = [
     ("zkw_storage_tree_advance_witness_chain", _int, [_vp, _vp, _vp, C.POINTER(C.c_uint64), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     ("zkw_storage_tree_advance_witness_chain_pairs", _int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     ("zkw_storage_tree_is_witness", _int, [_vp]),
+    ("zkw_kzg_settings_create", _int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    ("zkw_kzg_settings_free", None, [_vp]),
+    ("zkw_kzg_settings_num_points", _sz, [_vp]),
+    ("zkw_kzg_settings_bytes", _sz, [_vp]),
+    ("zkw_kzg_commit", _int, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    ("zkw_eip4844_witness", _int, [_vp, _vp, _vp, _sz, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -803,6 +809,92 @@ class StorageTreeDevice:
     def free(self):
         if self.handle:
             load().zkw_storage_tree_free(self.handle)
+            self.handle = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+EIP4844_RECORD = np.dtype([("linear_hash", "u1", (32,)), ("versioned_hash", "u1", (32,)), ("output_hash", "u1", (32,)),
+                           ("evaluation_point", "u1", (16,)), ("opening_value", "u1", (32,)), ("commitment", "u1", (48,))])
+assert EIP4844_RECORD.itemsize == 192
+EIP4844_BLOB_BYTES = 4096 * 31
+
+
+class KzgSettings:
+    """zkw_kzg_settings: the monomial KZG trusted setup S[k] = [tau^k] G1 (`g1_monomial`: n x 48 bytes of compressed points, n <= 4096)
+    as a fixed-base table in the HBM of `ctx`'s device — what `KzgSettings::new` is to the reference (kzg/src/lib.rs:78-148), without
+    its inverse FFT. Every point is decompressed and checked on the device (curve, order-r subgroup); a bad one raises
+    ZkwError(ERR_INVALID) naming its position. Immutable afterwards: `commit` and `eip4844_witness` may run on any context of the same
+    device (`ctx=`), several at once. Arrays are numpy uint8 on a context in host pointer mode, torch uint8 tensors on the context's
+    device in device pointer mode (results then come back as tensors)."""
+
+    def __init__(self, ctx, g1_monomial):
+        self.ctx = ctx
+        self.handle = C.c_void_p(None)
+        ptr, n, _keep = self._bytes(ctx, g1_monomial, 48)
+        _check(load().zkw_kzg_settings_create(ctx.handle, ptr, n, C.byref(self.handle)))
+
+    @staticmethod
+    def _bytes(ctx, a, row):
+        """(pointer, rows, keep-alive) of an array of rows of `row` bytes"""
+        if ctx.pointer_mode == PTR_DEVICE:
+            t = a.contiguous()
+            assert t.is_cuda and t.element_size() == 1 and t.numel() % row == 0
+            return C.c_void_p(t.data_ptr() if t.numel() else None), t.numel() // row, t
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(bytes(a), np.uint8)
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        assert a.size % row == 0
+        return (_np_ptr(a) if a.size else None), a.size // row, a
+
+    @property
+    def num_points(self) -> int:
+        return load().zkw_kzg_settings_num_points(self.handle)
+
+    @property
+    def nbytes(self) -> int:
+        """device memory held by the table"""
+        return load().zkw_kzg_settings_bytes(self.handle)
+
+    def commit(self, coeffs, n_coeffs, ctx=None):
+        """zkw_kzg_commit: `coeffs` = [n_polys, n_coeffs, 32] bytes, a coefficient as 32 little-endian bytes below r (one at or above
+        r raises ZkwError(ERR_INVALID)); returns [n_polys, 48]: compress(sum_i coeffs[j][i] S[i])."""
+        ctx = ctx or self.ctx
+        ptr, rows, _keep = self._bytes(ctx, coeffs, 32)
+        n_polys = rows // n_coeffs if n_coeffs else 0
+        assert n_polys * n_coeffs == rows
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty((n_polys, 48), dtype=torch.uint8, device=_keep.device)
+            _check(load().zkw_kzg_commit(self.handle, ctx.handle, ptr, n_coeffs, n_polys, C.c_void_p(out.data_ptr() if n_polys else None)))
+            return out
+        out = np.zeros((n_polys, 48), np.uint8)
+        _check(load().zkw_kzg_commit(self.handle, ctx.handle, ptr, n_coeffs, n_polys, _np_ptr(out) if n_polys else None))
+        return out
+
+    def eip4844_witness(self, blobs, ctx=None):
+        """zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:123): `blobs` = [n, 126976] bytes; returns n records — a numpy
+        structured array of EIP4844_RECORD (host pointer mode) or a uint8 tensor [n, 192] of the same layout (device pointer mode)."""
+        ctx = ctx or self.ctx
+        ptr, n, _keep = self._bytes(ctx, blobs, EIP4844_BLOB_BYTES)
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty((n, EIP4844_RECORD.itemsize), dtype=torch.uint8, device=_keep.device)
+            _check(load().zkw_eip4844_witness(self.handle, ctx.handle, ptr, n, C.c_void_p(out.data_ptr() if n else None)))
+            return out
+        out = np.zeros(n, EIP4844_RECORD)
+        _check(load().zkw_eip4844_witness(self.handle, ctx.handle, ptr, n, _np_ptr(out) if n else None))
+        return out
+
+    def free(self):
+        if self.handle:
+            load().zkw_kzg_settings_free(self.handle)
             self.handle = C.c_void_p(None)
 
     def __del__(self):

@@ -702,6 +702,37 @@ int zkw_storage_tree_advance_witness_chain_pairs(const zkw_storage_tree *witness
                                                  zkw_storage_tree **out, zkw_storage_tree **final_state);
 int zkw_storage_tree_is_witness(const zkw_storage_tree *tree);
 
+/* ---- EIP-4844 blob witness: KZG commitment, hashes and opening ---------------------------------------
+   generate_eip4844_witness (src/utils.rs:119-231; kzg/src/lib.rs) on the device. A settings handle holds the monomial trusted
+   setup S[k] = [tau^k] G1 as a fixed-base table in HBM (2^(8 w) S[k] for the 32 byte positions w of a scalar, affine:
+   3 072 bytes a point). It is immutable after creation: any number of contexts of its device may commit on it at once, each on its
+   own stream; it keeps the creating context alive and is freed by the caller once no call on it is in flight
+   (zkw_storage_tree_create_witness is the model). Pointers follow the context's pointer mode; `out` handles are host pointers.
+   zkw_kzg_settings_create: n_points compressed G1 points (48 bytes: big-endian x, bit 7 of byte 0 set, bit 6 = infinity with
+   every other bit 0, bit 5 = y is the larger root), 1 <= n_points <= 4096. ZKW_ERR_INVALID, with the position IN THE CALLER'S
+   ORDER of the first bad point in zkw_last_error, for: bit 7 clear; the infinity flag with other bits set; x >= p; an x with no y
+   on y^2 = x^3 + 4; a point outside the order-r subgroup. The point at infinity is accepted and contributes nothing. */
+typedef struct zkw_kzg_settings zkw_kzg_settings;
+int zkw_kzg_settings_create(zkw_ctx *ctx, const uint8_t *g1_monomial /*[n_points][48]*/, size_t n_points, zkw_kzg_settings **out);
+void zkw_kzg_settings_free(zkw_kzg_settings *s);
+size_t zkw_kzg_settings_num_points(const zkw_kzg_settings *s);
+size_t zkw_kzg_settings_bytes(const zkw_kzg_settings *s); /* HBM held */
+/* out[j] = compress(sum_i coeffs[j][i] * S[i]). A coefficient is 32 little-endian bytes below r; a value >= r is
+   ZKW_ERR_INVALID (its position in zkw_last_error), n_coeffs <= num_points. One readback per call (the range check). */
+int zkw_kzg_commit(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *coeffs /*[n_polys][n_coeffs][32]*/, size_t n_coeffs,
+                   size_t n_polys, uint8_t *out /*[n_polys][48]*/);
+/* One record per blob of 4 096 x 31 bytes (element i = the little-endian integer of its i-th 31 bytes, the coefficient of
+   X^(4095 - i)): linear_hash = Keccak-256(blob); commitment = compress(sum_i e_i S[4095 - i]); versioned_hash =
+   SHA-256(commitment) with byte 0 = 0x01; evaluation_point z = bytes 16..32 of Keccak-256(linear_hash || versioned_hash)
+   (big-endian); opening_value = p(z) mod r (32 big-endian bytes); output_hash = Keccak-256(versioned_hash || z || y).
+   Requires num_points == 4096. Nothing is read back: in device pointer mode the call only enqueues. */
+typedef struct zkw_eip4844_record {
+    uint8_t linear_hash[32], versioned_hash[32], output_hash[32];
+    uint8_t evaluation_point[16], opening_value[32], commitment[48];
+} zkw_eip4844_record;
+int zkw_eip4844_witness(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n_blobs,
+                        zkw_eip4844_record *out /*[n]*/);
+
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
 /* kind = ZKW_PRECOMPILE_KECCAK256: keccak256_decompose_into_per_circuit_witness,
