@@ -29,9 +29,7 @@ struct SynthJob {
     const u64* u_mark;         // [12] full unsorted / sorted queue tail after this instance's last item
     const u64* s_mark;
     const u64* challenges;  // [2][9]
-    const u64* lhs_z;       // [2][n_block] grand-product chains of the instance's block
-    const u64* rhs_z;
-    u64 n_block;            // items in the block (stride between the two repetitions)
+    const u64* gp_ckpt;     // [ceil(capacity/64)][4] this instance's grand-product checkpoints: {lhs r0, lhs r1, rhs r0, rhs r1} entering cycle 64 g
     u64* trace;             // [RC_COLS][n_rows]
     u32* hist;              // [256] lookup-value histogram of this trace (zeroed before the fills)
     u32* nd_tiles;          // [ceil(capacity/256)] exclusive prefix of nondeterministic writes per 256-cycle tile
@@ -168,9 +166,20 @@ __device__ __forceinline__ void cycle_ctx(const SynthJob& job, u32 i, CycleCtx& 
     c.p_ptr = c.pq.value_is_pointer ? 1 : 0;
 }
 
-// accumulator entering cycle i: FSM input for i = 0, else the chain value at the last popped item
-__device__ __forceinline__ u64 acc_before(const u64* z, size_t first, size_t m, u32 i, u64 fsm_in) {
-    return i == 0 ? fsm_in : z[first + (i - 1 < m ? i - 1 : m - 1)];
+// Exclusive product scan of a pair of factors over the wave's 64 cycles, times the pair's checkpoint: the accumulators entering each
+// lane's cycle (canonical). Lane 0 takes the checkpoints alone. Every lane of the wave takes part, a lane that pops nothing with 1.
+// One step's two products, then a barrier: more in flight and their carry flags run the SGPRs out (as the dot products of row A).
+__device__ __forceinline__ void acc_before_pair(u64 fl, u64 fr, u64 ckpt_l, u64 ckpt_r, int lane, u64& pl, u64& pr) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 ol = __shfl_up(fl, d, 64), orr = __shfl_up(fr, d, 64);
+        if (lane >= d) { fl = gl::mul(fl, ol); fr = gl::mul(fr, orr); }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const u64 el = __shfl_up(fl, 1, 64), er = __shfl_up(fr, 1, 64);
+    pl = lane == 0 ? ckpt_l : gl::canon(gl::mul(ckpt_l, el));
+    pr = lane == 0 ? ckpt_r : gl::canon(gl::mul(ckpt_r, er));
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // Rows A and B have no kernel of their own: the lane of k_ram_fill_poseidon that runs cycle i's permutation writes them too (A with
@@ -180,24 +189,29 @@ __device__ __forceinline__ void fill_row_A(const SynthJob& job, u32 i, u32 capac
                                            const u64 eu[8], const u64 es[8], u32* sh_hist) {
     u64* trace = job.trace;
     const size_t row = (size_t)RC_ROW_A * RC_REGION_STRIDE(capacity) + i;
-    if (i < capacity) {
-        const zkw_ram_instance* in = job.inst;
-        const size_t first = in->first_item, m = in->num_items, n_total = job.n_block;
-        const bool can_pop = i < m;
-        const u64 rw = q.rw_flag ? 1 : 0, ptr = q.value_is_pointer ? 1 : 0;
+    const bool live = i < capacity;
+    const bool can_pop = live && i < job.inst->num_items;
+    // The workgroup is one wave of 64 consecutive cycles, group i / 64 of the instance (a region's stride is capacity rounded up to 64, so
+    // the group has a live cycle and a checkpoint). The accumulators entering a cycle = the group's checkpoint times the factors of the
+    // cycles before it in the wave: the gap lanes (i >= capacity) run the scan too, with the neutral 1, and store nothing.
+    const int lane = threadIdx.x & 63;
+    const u64* ckpt = job.gp_ckpt + 4 * (size_t)((u32)__builtin_amdgcn_readfirstlane((int)i) >> 6);
+    if (live) {
 #pragma unroll
         for (int k = 0; k < 8; k++) { TR(RC_A_eu0 + k, row) = eu[k]; TR(RC_A_ts + k, row) = es[k]; }
-        for (int r = 0; r < 2; r++) {
-            const u64* ch = job.challenges + 9 * r;
-            u64 lc = ch[8], rc = ch[8];
+    }
+    for (int r = 0; r < 2; r++) {
+        const u64* ch = job.challenges + 9 * r;
+        u64 lc = ch[8], rc = ch[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) {
-                lc = gl::add(lc, gl::mul(eu[k], ch[k]));
-                rc = gl::add(rc, gl::mul(es[k], ch[k]));
-                __builtin_amdgcn_sched_barrier(0);  // two products in flight, not 32: their carries live in SGPR pairs (as P2_SBOX_GROUP)
-            }
-            const u64 pl = acc_before(job.lhs_z + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.lhs_accumulator[r]);
-            const u64 pr = acc_before(job.rhs_z + (size_t)r * n_total, first, m, i, in->hidden_fsm_input.rhs_accumulator[r]);
+        for (int k = 0; k < 8; k++) {
+            lc = gl::add(lc, gl::mul(eu[k], ch[k]));
+            rc = gl::add(rc, gl::mul(es[k], ch[k]));
+            __builtin_amdgcn_sched_barrier(0);  // two products in flight, not 32: their carries live in SGPR pairs (as P2_SBOX_GROUP)
+        }
+        u64 pl, pr;
+        acc_before_pair(can_pop ? lc : 1, can_pop ? rc : 1, ckpt[r], ckpt[2 + r], lane, pl, pr);
+        if (live) {
             const u64 nl = gl::canon(gl::mul(pl, lc)), nr = gl::canon(gl::mul(pr, rc));
             const int o = r * (RC_A_lc1 - RC_A_lc0);
 #pragma unroll
@@ -207,8 +221,11 @@ __device__ __forceinline__ void fill_row_A(const SynthJob& job, u32 i, u32 capac
             TR(RC_A_lhs0 + o, row) = can_pop ? nl : pl;
             TR(RC_A_rc0 + o, row) = gl::canon(rc); TR(RC_A_P_rhs0 + o, row) = pr; TR(RC_A_nr0 + o, row) = nr;
             TR(RC_A_rhs0 + o, row) = can_pop ? nr : pr;
-            __builtin_amdgcn_sched_barrier(0);
         }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (live) {
+        const u64 rw = q.rw_flag ? 1 : 0, ptr = q.value_is_pointer ? 1 : 0;
         TR(RC_A_rw, row) = rw; TR(RC_A_ptr, row) = ptr; TR(RC_A_idx, row) = q.index;
         TR(RC_A_v2, row) = q.value[2]; TR(RC_A_v3, row) = q.value[3]; TR(RC_A_v0, row) = q.value[0];
         TR(RC_A_v5_b3c, row) = q.value[5] >> 24; TR(RC_A_can_pop, row) = can_pop ? 1 : 0;
@@ -571,9 +588,6 @@ ZKW_CF_TABLES(RC, rc)
 
 // the register rows BND_IN / BND_OUT (one lane)
 __device__ __forceinline__ void ram_fill_register_rows(const SynthJob& job, u32 capacity, size_t n_rows) {
-    const u64* lhs_z_all = job.lhs_z;
-    const u64* rhs_z_all = job.rhs_z;
-    const size_t n_total = job.n_block;
     u64* trace = job.trace;
     const zkw_ram_instance* in = job.inst;
     const zkw_ram_fsm& fi = in->hidden_fsm_input;
@@ -607,8 +621,9 @@ __device__ __forceinline__ void ram_fill_register_rows(const SynthJob& job, u32 
     }
     TR(RC_BND_OUT_len_u, bout) = len_out; TR(RC_BND_OUT_len_s, bout) = len_out;
     for (int r = 0; r < 2; r++) {
-        TR(RC_BND_OUT_lhs0 + r, bout) = lhs_z_all[(size_t)r * n_total + last];
-        TR(RC_BND_OUT_rhs0 + r, bout) = rhs_z_all[(size_t)r * n_total + last];
+        // the chain values at the instance's last item: k_ram_instances put them into the output FSM
+        TR(RC_BND_OUT_lhs0 + r, bout) = in->hidden_fsm_output.lhs_accumulator[r];
+        TR(RC_BND_OUT_rhs0 + r, bout) = in->hidden_fsm_output.rhs_accumulator[r];
     }
     zkw_mem_query lq;
     memset(&lq, 0, sizeof lq);

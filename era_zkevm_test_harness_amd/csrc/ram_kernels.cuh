@@ -541,6 +541,7 @@ struct RamBlock {
     const u64* rhs_z;               // [2][n]
     zkw_ram_instance* instances;    // [ceil(n/capacity)]
     u32* nondet_prefix;             // [n_instances] scratch: nondeterministic writes per chunk
+    u64* gp_ckpt;                   // [n_instances][ceil(capacity/64)][4] grand-product checkpoints of the block's instances
     u64 n;
     u32 capacity;
     u32 num_nondet_heap_queries;
@@ -626,6 +627,25 @@ static __device__ __forceinline__ void k_ram_instances(const VB& vb, const RamBl
     }
 }
 
+// pass 3: grand-product checkpoints, one lane per (instance, group of 64 cycles): the four accumulators (lhs r0, lhs r1, rhs r0, rhs r1)
+// entering the group's first cycle = the FSM input for group 0, else the chain value at the instance's last item popped before that
+// cycle. Row A of the synthesis finishes the scan inside its wave from these (ram_circuit_kernels.cuh), so that no synthesis call
+// needs the chains. first_item is no multiple of 64 for an instance's continuations: the groups are the INSTANCE's, not the chain tiles'.
+static __device__ __forceinline__ void k_ram_gp_ckpt(const VB& vb, const RamBlock* __restrict__ blocks) {
+    const RamBlock b = blocks[vb.y];
+    const u64 n_inst = (b.n + b.capacity - 1) / b.capacity, groups = (b.capacity + 63) / 64;
+    const u64 j = (u64)vb.x * blockDim.x + threadIdx.x;
+    if (j >= n_inst * groups) return;
+    const u64 idx = j / groups, g = j % groups;
+    const zkw_ram_instance& in = b.instances[idx];
+    const u64 first = in.first_item, m = in.num_items;
+    u64* out = b.gp_ckpt + 4 * j;
+    for (int r = 0; r < 2; r++) {
+        const u64 at = (u64)r * b.n + first + (64 * g - 1 < m ? 64 * g - 1 : m - 1);  // (unused for g = 0)
+        out[r] = g == 0 ? in.hidden_fsm_input.lhs_accumulator[r] : b.lhs_z[at];
+        out[2 + r] = g == 0 ? in.hidden_fsm_input.rhs_accumulator[r] : b.rhs_z[at];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // Full tails on demand: tails[i] = permute(enc[i] || caps[i-1]) (zero capacity at the first item of a queue).

@@ -1069,12 +1069,15 @@ struct zkw_ram_witness {
     u64 *unsorted_caps = nullptr, *sorted_caps = nullptr, *unsorted_marks = nullptr, *sorted_marks = nullptr;
     u64 *unsorted_tails = nullptr, *sorted_tails = nullptr;
     bool tails_valid = false;
-    // grand-product chains: the builder only needs them at instance boundaries and the fills only inside the block
-    // being filled, so they live in a window (zbuf_*, zcap items) that is recomputed per group of blocks / per synthesis
-    // call (16 B per query and side instead of 32 B resident); the [total] arrays of the C ABI are computed on first access
+    // grand-product chains: the builder only needs them at instance boundaries, so they live in a window (zbuf_*, zcap items)
+    // that it computes per group of blocks (16 B per query and side instead of 32 B resident); the [total] arrays of the C ABI
+    // are computed on first access. What the synthesis needs of them stays behind as gp_ckpt: the four accumulators entering
+    // every group of 64 cycles of every instance ([n_instances][ceil(capacity/64)][4], written group by group while the chains
+    // are in the window); row A scans the 64 cycles in between itself
     u64 *challenges = nullptr, *lhs_z = nullptr, *rhs_z = nullptr;
     bool z_valid = false;
     u64 *zbuf_l = nullptr, *zbuf_r = nullptr;
+    u64* gp_ckpt = nullptr;
     zkw_mem_query* sq_win = nullptr;  // the sorted queries of the blocks being synthesized, gathered per synthesis call
     size_t zcap = 0, sqcap = 0;       // capacity of the chain windows / of the sorted window, in queue items
     zkw_ram_instance* instances = nullptr;
@@ -1084,7 +1087,7 @@ struct zkw_ram_witness {
     void release() {
         void* ptrs[] = {sorted_q, perm, owned_q, unsorted_enc, sorted_enc, unsorted_caps, sorted_caps, unsorted_marks, sorted_marks,
                         unsorted_tails, sorted_tails, challenges,
-                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, zbuf_l, zbuf_r, sq_win};
+                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, zbuf_l, zbuf_r, sq_win, gp_ckpt};
         for (void* p : ptrs)
             if (p) dev_free(p);
         sorted_q = nullptr;
@@ -1098,6 +1101,7 @@ struct zkw_ram_witness {
         tails_valid = false;
         z_valid = false;
         zbuf_l = zbuf_r = nullptr;
+        gp_ckpt = nullptr;
         sq_win = nullptr;
         zcap = sqcap = 0;
         instances = nullptr;
@@ -1107,6 +1111,7 @@ struct zkw_ram_witness {
 };
 
 extern "C" void zkw_ram_witness_free(zkw_ram_witness* w);
+static inline size_t ram_gp_groups(uint32_t capacity) { return ((size_t)capacity + 63) / 64; }  // checkpoints per instance
 static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
     const size_t t = w->total, ni = w->n_instances;
     HIP_TRY(dev_malloc((void**)&w->perm, (t + 1) * sizeof(u32)));
@@ -1126,6 +1131,7 @@ static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
         HIP_TRY(dev_malloc((void**)&w->zbuf_r, (w->zcap + 1) * 2 * sizeof(u64)));
         HIP_TRY(dev_malloc((void**)&w->sq_win, (w->sqcap + 1) * sizeof(zkw_mem_query)));
     }
+    HIP_TRY(dev_malloc((void**)&w->gp_ckpt, (ni * ram_gp_groups(w->capacity) + 1) * 4 * sizeof(u64)));
     HIP_TRY(dev_malloc((void**)&w->instances, (ni + 1) * sizeof(zkw_ram_instance)));
     HIP_TRY(dev_malloc((void**)&w->nondet_counts, (ni + 1) * sizeof(u32)));
     HIP_TRY(dev_malloc((void**)&w->compact_forms, (ni + 1) * COMPACT_FORM_LEN * sizeof(u64)));
@@ -1351,6 +1357,7 @@ static int ram_run(zkw_ctx* ctx, zkw_ram_witness* w, const zkw_mem_query* d_q, c
                                       w->zbuf_r + 2 * (lo - base),
                                       w->instances + w->inst_offsets[b],
                                       w->nondet_counts + w->inst_offsets[b],
+                                      w->gp_ckpt + 4 * ram_gp_groups(w->capacity) * w->inst_offsets[b],
                                       n,
                                       w->capacity,
                                       n_nondet ? n_nondet[b] : 0u};
@@ -1362,6 +1369,9 @@ static int ram_run(zkw_ctx* ctx, zkw_ram_witness* w, const zkw_mem_query* d_q, c
         ZKW_TRY(launch_check("k_ram_count_nondet"));
         { Prof _p(ctx, "k_ram_instances"); ZKW_LAUNCH_2D(ctx, k_ram_instances, blocks_for(max_inst, 64), gy, 64, d_blocks); }
         ZKW_TRY(launch_check("k_ram_instances"));
+        // the group's chains are still in the window: leave the synthesis its checkpoints (it never recomputes the chains)
+        { Prof _p(ctx, "k_ram_gp_ckpt"); ZKW_LAUNCH_2D(ctx, k_ram_gp_ckpt, blocks_for(max_inst * ram_gp_groups(w->capacity), 256), gy, 256, d_blocks); }
+        ZKW_TRY(launch_check("k_ram_gp_ckpt"));
         b0 = b1;
     }
     // a20: compact forms and public inputs of every instance (postprocessing/mod.rs:353-369)
@@ -1526,6 +1536,7 @@ static const void* ram_array(const zkw_ram_witness* w, int what, size_t* bytes, 
         case ZKW_RAM_INSTANCES: *bytes = w->n_instances * sizeof(zkw_ram_instance); p = w->instances; break;
         case ZKW_RAM_COMPACT_FORMS: *bytes = w->n_instances * COMPACT_FORM_LEN * 8; p = w->compact_forms; break;
         case ZKW_RAM_PUBLIC_INPUTS: *bytes = w->n_instances * 32; p = w->public_inputs; break;
+        case ZKW_RAM_GP_CKPT: *bytes = w->n_instances * ram_gp_groups(w->capacity) * 32; p = w->gp_ckpt; break;
         default: *bytes = 0; st = ZKW_ERR_INVALID; break;
     }
 #undef RAM_LAZY
@@ -1637,13 +1648,13 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     if (n_rows & 1) return fail(ZKW_ERR_INVALID, "trace length must be even (it is a power of two in every circuit)");
     if (n_instances == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    // the grand-product chains of the blocks these instances belong to, recomputed into the witness's window
+    // the blocks these instances belong to: their sorted queries go through the witness's window
     const size_t n_blocks = w->offsets.size() - 1;
     size_t b_first = 0;
     while (b_first + 1 < n_blocks && w->inst_offsets[b_first + 1] <= first_instance) b_first++;
     size_t b_end = b_first + 1;  // one past the last block touched
     while (b_end < n_blocks && w->inst_offsets[b_end] < first_instance + n_instances) b_end++;
-    const size_t win = std::min(w->zcap, w->sqcap);
+    const size_t win = w->sqcap;
     if (w->offsets[b_end] - w->offsets[b_first] > win) {  // too many blocks for one window: split at a block boundary
         size_t b_mid = b_first + 1;
         while (b_mid + 1 < b_end && w->offsets[b_mid + 1] - w->offsets[b_first] <= win) b_mid++;
@@ -1651,7 +1662,6 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
         ZKW_TRY(zkw_ram_synthesize(ctx, w, first_instance, n_head, t, first_slot));
         return zkw_ram_synthesize(ctx, w, first_instance + n_head, n_instances - n_head, t, first_slot + n_head);
     }
-    ZKW_TRY(ram_gp_blocks(ctx, w, b_first, b_end, w->zbuf_l, w->zbuf_r));
     const size_t z_base = w->offsets[b_first];
     {   // the fills read the sorted queue contiguously: gather the touched blocks once per call
         const size_t cnt = w->offsets[b_end] - z_base;
@@ -1671,7 +1681,7 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     for (size_t k = 0; k < n_instances; k++) {
         const size_t idx = first_instance + k;
         while (b + 1 < n_blocks && w->inst_offsets[b + 1] <= idx) b++;
-        const size_t lo = w->offsets[b], nb = w->offsets[b + 1] - lo;
+        const size_t lo = w->offsets[b];
         SynthJob& j = jobs[k];
         j.inst = w->instances + idx;
         j.sorted_q = w->sq_win + (lo - z_base);
@@ -1681,9 +1691,7 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
         j.u_mark = w->unsorted_marks + 12 * idx;
         j.s_mark = w->sorted_marks + 12 * idx;
         j.challenges = w->challenges + 18 * b;
-        j.lhs_z = w->zbuf_l + 2 * (lo - z_base);
-        j.rhs_z = w->zbuf_r + 2 * (lo - z_base);
-        j.n_block = nb;
+        j.gp_ckpt = w->gp_ckpt + 4 * ram_gp_groups(capacity) * idx;
         {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
             const uint64_t tag = ((uint64_t)ZKW_CIRCUIT_RAM_PERMUTATION << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
             const size_t slot = (first_slot + k) % t->n_slots;

@@ -299,7 +299,7 @@ enum {
     ZKW_RAM_SORTED_TAILS = 4,   /* capacity words + the tails at instance ends: 64 instead of 192 bytes per query) */
     ZKW_RAM_CHALLENGES = 5,     /* uint64_t[n_blocks][2][9]       */
     ZKW_RAM_LHS_Z = 6,          /* per block b: uint64_t[2][n_b] at element offset 2*block_offsets[b]; computed on first
-                                   access (builder and synthesis recompute the chains in a window) */
+                                   access (the builder computes the chains in a window and keeps ZKW_RAM_GP_CKPT) */
     ZKW_RAM_RHS_Z = 7,          /* idem                           */
     ZKW_RAM_INSTANCES = 8,      /* zkw_ram_instance[n_instances], blocks in order */
     /* a20, CircuitMaker::process src/witness/postprocessing/mod.rs:353-405 (every instance of a block shares
@@ -307,7 +307,11 @@ enum {
        C(observable_output), C(hidden_fsm_input), C(hidden_fsm_output)], and the public input C(compact form)
        that simulate_public_input_value_from_witness (src/witness/utils.rs:269-306) returns. */
     ZKW_RAM_COMPACT_FORMS = 9,  /* uint64_t[n_instances][18]      */
-    ZKW_RAM_PUBLIC_INPUTS = 10  /* uint64_t[n_instances][4]       */
+    ZKW_RAM_PUBLIC_INPUTS = 10, /* uint64_t[n_instances][4]       */
+    /* grand-product checkpoints: the accumulators {lhs rep 0, lhs rep 1, rhs rep 0, rhs rep 1} entering cycle 64 g of every
+       instance (its FSM input for g = 0, else the chain value at its last item popped before that cycle); what the
+       synthesis reads instead of the chains */
+    ZKW_RAM_GP_CKPT = 11        /* uint64_t[n_instances][ceil(capacity/64)][4] */
 };
 size_t zkw_ram_witness_num_instances(const zkw_ram_witness *w);
 size_t zkw_ram_witness_num_items(const zkw_ram_witness *w);
