@@ -1,8 +1,10 @@
 // zkw_kzg.hip — the EIP-4844 blob witness behind include/zkw.h: zkw_kzg_settings (the monomial trusted setup as a fixed-base table in
-// HBM), zkw_kzg_commit and zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:119-231 of the reference). Kernels and the
-// decomposition: kzg_kernels.cuh; field and group arithmetic: bls12_381.cuh.
+// HBM), zkw_kzg_commit and zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:119-231 of the reference), and the KZG proofs
+// zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs). Kernels and the decomposition: kzg_kernels.cuh,
+// kzg_open_kernels.cuh; field and group arithmetic: bls12_381.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
+#include "kzg_open_kernels.cuh"
 
 #include <cstddef>
 
@@ -11,6 +13,10 @@ static_assert(sizeof(zkw_eip4844_record) == KZG_REC_BYTES && offsetof(zkw_eip484
                   offsetof(zkw_eip4844_record, evaluation_point) == KZG_REC_Z && offsetof(zkw_eip4844_record, opening_value) == KZG_REC_Y &&
                   offsetof(zkw_eip4844_record, commitment) == KZG_REC_COMMITMENT,
               "kzg_kernels.cuh writes zkw_eip4844_record by byte offset");
+static_assert(sizeof(zkw_eip4844_proof_record) == KZG_PRF_BYTES && offsetof(zkw_eip4844_proof_record, opening_proof) == KZG_PRF_OPENING &&
+                  offsetof(zkw_eip4844_proof_record, blob_proof) == KZG_PRF_BLOB && offsetof(zkw_eip4844_proof_record, blob_challenge) == KZG_PRF_CHALLENGE &&
+                  offsetof(zkw_eip4844_proof_record, blob_value) == KZG_PRF_VALUE,
+              "kzg_open_kernels.cuh writes zkw_eip4844_proof_record by byte offset");
 static_assert(sizeof(bls::G1Aff) == 96 && sizeof(bls::G1Jac) == 144, "table entries are 96 bytes, bucket sums 144");
 
 struct zkw_kzg_settings {
@@ -154,5 +160,100 @@ extern "C" int zkw_eip4844_witness(const zkw_kzg_settings* s, zkw_ctx* ctx, cons
     if (beside) ZKW_TRY(ctx->side_join());
     { Prof _p(ctx, "k_kzg_tail"); ZKW_LAUNCH(ctx, k_kzg_tail, n_blobs, KZG_TAIL_THREADS, d_b, rec); }
     ZKW_TRY(ctx->finish_out(out, d_rec, n_blobs));
+    return ctx->sync_if_host();
+}
+
+// ---- the proofs: an opening is the commitment of the quotient, whose rows k_kzg_quotient leaves in context scratch ----------------------
+extern "C" int zkw_kzg_open(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* coeffs, size_t n_coeffs, size_t n_polys, const uint8_t* points,
+                            uint8_t* proofs, uint8_t* values) {
+    if (!s || !ctx || (n_polys && (!points || !proofs || !values || (n_coeffs && !coeffs)))) return fail(ZKW_ERR_INVALID, "zkw_kzg_open: null argument");
+    if (n_coeffs > s->n) return fail(ZKW_ERR_INVALID, "zkw_kzg_open: %zu coefficients, the settings hold %zu points", n_coeffs, s->n);
+    ZKW_TRY(kzg_check_call("zkw_kzg_open", s, ctx, n_polys));
+    if (n_polys == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = n_coeffs * n_polys, n_rows = n_coeffs ? n_coeffs - 1 : 0;
+    const uint8_t *d_c = nullptr, *d_z = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_coeffs", coeffs, total * 32, &d_c));
+    ZKW_TRY(ctx->in("kzg_in_points", points, n_polys * 32, &d_z));
+    {
+        u32 *d_flag = nullptr, h_flag[2] = {~0u, ~0u};  // the first bad coefficient, the first bad point
+        ZKW_TRY(ctx->scratch_t<u32>("kzg_flag", 2, &d_flag));
+        HIP_TRY(ctx->memset_async(d_flag, 0xFF, sizeof h_flag));
+        if (total) { Prof _p(ctx, "k_kzg_check"); ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(total, 256), 256, d_c, (u32)total, d_flag); }
+        { Prof _p(ctx, "k_kzg_check_points"); ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(n_polys, 256), 256, d_z, (u32)n_polys, d_flag + 1); }
+        ZKW_TRY(ctx->read_small(h_flag, d_flag, sizeof h_flag));
+        if (h_flag[0] != ~0u)
+            return fail(ZKW_ERR_INVALID, "zkw_kzg_open: coefficient %zu of polynomial %zu is not below r", (size_t)h_flag[0] % n_coeffs, (size_t)h_flag[0] / n_coeffs);
+        if (h_flag[1] != ~0u) return fail(ZKW_ERR_INVALID, "zkw_kzg_open: the point of polynomial %zu is not below r", (size_t)h_flag[1]);
+    }
+    uint8_t *d_proofs = nullptr, *d_values = nullptr, *d_rows = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", proofs, n_polys * 48, &d_proofs));
+    ZKW_TRY(ctx->out("kzg_out_values", values, n_polys * 32, &d_values));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_quotient_rows", n_polys * n_rows * 32, &d_rows));
+    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, n_polys, KZG_QUO_THREADS, KzgSrc{d_c, (u32)n_coeffs, 0}, (u32)(n_coeffs * 32), d_z, 32u, (u32)KZG_Z_LE32, d_rows, (u32)(n_rows * 32), d_values, 32u, 0u); }
+    ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_rows, (u32)n_rows, 0}, (u32)(n_rows * 32), n_polys, d_proofs, 48));
+    ZKW_TRY(ctx->finish_out(proofs, d_proofs, n_polys * 48));
+    ZKW_TRY(ctx->finish_out(values, d_values, n_polys * 32));
+    return ctx->sync_if_host();
+}
+
+template <auto Body, int BS, class... A> static int kzg_launch_on(hipStream_t st, const char* name, unsigned blocks, size_t lds, const A&... a) {
+    Launcher<Body, BS>::S::template single<Body, BS>(st, dim3(blocks), lds, a...);
+    return launch_check(name);
+}
+
+extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* blobs, size_t n_blobs, const zkw_eip4844_record* records,
+                                 zkw_eip4844_proof_record* out, uint8_t* blob_evaluations) {
+    if (!s || !ctx || (n_blobs && (!blobs || !records || !out))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: null argument");
+    if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: a blob has 4096 elements, the settings hold %zu points", s->n);
+    if (n_blobs > 32767) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: at most 32767 blobs per call (two polynomials each), not %zu", n_blobs);
+    ZKW_TRY(kzg_check_call("zkw_eip4844_prove", s, ctx, 2 * n_blobs));
+    if (n_blobs == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    static bool attr_set[16] = {};
+    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
+        ZKW_TRY((Launcher<&k_kzg_blob_ntt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+        attr_set[ctx->device & 15] = true;
+    }
+    const uint8_t* d_b = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_blobs", blobs, n_blobs * KZG_BLOB_BYTES, &d_b));
+    const zkw_eip4844_record* d_rec = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_records", records, n_blobs, &d_rec));
+    const uint8_t* rec = reinterpret_cast<const uint8_t*>(d_rec);
+    zkw_eip4844_proof_record* d_out = nullptr;
+    ZKW_TRY(ctx->out("kzg_proof_records", out, n_blobs, &d_out));
+    uint8_t *prf = reinterpret_cast<uint8_t*>(d_out), *d_ev = nullptr, *d_rows = nullptr, *d_proofs = nullptr;
+    if (blob_evaluations) ZKW_TRY(ctx->out("kzg_evals", blob_evaluations, n_blobs * KZG_EVAL_BYTES, &d_ev));
+    else ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_evals", n_blobs * KZG_EVAL_BYTES, &d_ev));  // the challenge hashes it either way
+    bls::Fr* d_tw = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
+    // blob j's two quotients side by side: rows 2 j (at the record's z) and 2 j + 1 (at the challenge), so are their proofs
+    constexpr u32 ROWS = (KZG_BLOB_ELEMENTS - 1) * 32;
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_quotient_rows", 2 * n_blobs * ROWS, &d_rows));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_proofs", 2 * n_blobs * 48, &d_proofs));
+    const KzgSrc blob_src{d_b, (u32)KZG_BLOB_ELEMENTS, 1};
+    const unsigned nb = (unsigned)n_blobs;
+    // the evaluation form and its sponge depend on nothing the opening at z writes: beside it on a stream of the pool, joined ahead of the
+    // opening at the challenge. (A context of a batch has one stream; under zkw_profile every span times its own kernel.)
+    const bool beside = !ctx->batched() && !ctx->profiling;
+    if (beside) {
+        hipStream_t side = nullptr;
+        ZKW_TRY(ctx->side_fork(&side));
+        ZKW_TRY((kzg_launch_on<&k_kzg_twiddles, 256>(side, "k_kzg_twiddles", 8, 0, d_tw)));
+        ZKW_TRY((kzg_launch_on<&k_kzg_blob_ntt, KZG_NTT_THREADS>(side, "k_kzg_blob_ntt", nb, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev)));
+        ZKW_TRY((kzg_launch_on<&k_kzg_blob_challenge, 64>(side, "k_kzg_blob_challenge", nb, 0, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES,
+                                                               prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES)));
+    } else {
+        { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
+        { Prof _p(ctx, "k_kzg_blob_ntt"); ZKW_LAUNCH_D(ctx, k_kzg_blob_ntt, "k_kzg_blob_ntt", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev); }
+        { Prof _p(ctx, "k_kzg_blob_challenge"); ZKW_LAUNCH(ctx, k_kzg_blob_challenge, nb, 64, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES, prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES); }
+    }
+    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, rec + KZG_REC_Z, (u32)KZG_REC_BYTES, (u32)KZG_Z_BE16, d_rows, 2 * ROWS, (uint8_t*)nullptr, 0u, 0u); }
+    if (beside) ZKW_TRY(ctx->side_join());
+    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, (const uint8_t*)prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES, (u32)KZG_Z_BE32, d_rows + ROWS, 2 * ROWS, prf + KZG_PRF_VALUE, (u32)KZG_PRF_BYTES, 1u); }
+    ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_rows, (u32)KZG_BLOB_ELEMENTS - 1, 0}, ROWS, 2 * n_blobs, d_proofs, 48));
+    { Prof _p(ctx, "k_kzg_proofs_out"); ZKW_LAUNCH(ctx, k_kzg_proofs_out, blocks_for(n_blobs * 96, 256), 256, (const uint8_t*)d_proofs, (u32)nb, prf); }
+    ZKW_TRY(ctx->finish_out(out, d_out, n_blobs));
+    if (blob_evaluations) ZKW_TRY(ctx->finish_out(blob_evaluations, d_ev, n_blobs * KZG_EVAL_BYTES));
     return ctx->sync_if_host();
 }

@@ -185,6 +185,8 @@ SYMBOLS = [
     ("zkw_kzg_settings_bytes", _sz, [_vp]),
     ("zkw_kzg_commit", _int, [_vp, _vp, _vp, _sz, _sz, _vp]),
     ("zkw_eip4844_witness", _int, [_vp, _vp, _vp, _sz, _vp]),
+    ("zkw_kzg_open", _int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    ("zkw_eip4844_prove", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -822,6 +824,9 @@ EIP4844_RECORD = np.dtype([("linear_hash", "u1", (32,)), ("versioned_hash", "u1"
                            ("evaluation_point", "u1", (16,)), ("opening_value", "u1", (32,)), ("commitment", "u1", (48,))])
 assert EIP4844_RECORD.itemsize == 192
 EIP4844_BLOB_BYTES = 4096 * 31
+EIP4844_PROOF_RECORD = np.dtype([("opening_proof", "u1", (48,)), ("blob_proof", "u1", (48,)), ("blob_challenge", "u1", (32,)), ("blob_value", "u1", (32,))])
+assert EIP4844_PROOF_RECORD.itemsize == 160
+EIP4844_EVALUATION_BYTES = 4096 * 32
 
 
 class KzgSettings:
@@ -891,6 +896,51 @@ class KzgSettings:
         out = np.zeros(n, EIP4844_RECORD)
         _check(load().zkw_eip4844_witness(self.handle, ctx.handle, ptr, n, _np_ptr(out) if n else None))
         return out
+
+    def open(self, coeffs, n_coeffs, points, ctx=None):
+        """zkw_kzg_open (compute_proof, kzg/src/lib.rs:218-256): `coeffs` = [n_polys, n_coeffs, 32] bytes as for `commit`, `points` =
+        [n_polys, 32] bytes, a point as 32 little-endian bytes below r; returns (proofs [n_polys, 48], values [n_polys, 32]): the value
+        p_j(points[j]) as 32 little-endian bytes and the compressed commitment of (p_j - value) / (X - points[j])."""
+        ctx = ctx or self.ctx
+        zptr, n_polys, _keep_z = self._bytes(ctx, points, 32)
+        ptr, rows, _keep = self._bytes(ctx, coeffs, 32)
+        assert rows == n_polys * n_coeffs
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            proofs = torch.empty((n_polys, 48), dtype=torch.uint8, device=_keep_z.device)
+            values = torch.empty((n_polys, 32), dtype=torch.uint8, device=_keep_z.device)
+            _check(load().zkw_kzg_open(self.handle, ctx.handle, ptr, n_coeffs, n_polys, zptr, C.c_void_p(proofs.data_ptr() if n_polys else None),
+                                       C.c_void_p(values.data_ptr() if n_polys else None)))
+            return proofs, values
+        proofs, values = np.zeros((n_polys, 48), np.uint8), np.zeros((n_polys, 32), np.uint8)
+        _check(load().zkw_kzg_open(self.handle, ctx.handle, ptr, n_coeffs, n_polys, zptr, _np_ptr(proofs) if n_polys else None, _np_ptr(values) if n_polys else None))
+        return proofs, values
+
+    def eip4844_prove(self, blobs, records, ctx=None, evaluations=False):
+        """zkw_eip4844_prove: `blobs` = [n, 126976] bytes and `records` = what `eip4844_witness` returned for them; returns n records — a
+        numpy structured array of EIP4844_PROOF_RECORD (host pointer mode) or a uint8 tensor [n, 160] of the same layout (device pointer
+        mode). With `evaluations=True` returns (records, [n, 131072] bytes): the blobs in evaluation form, as a transaction's sidecar
+        carries them."""
+        ctx = ctx or self.ctx
+        ptr, n, _keep = self._bytes(ctx, blobs, EIP4844_BLOB_BYTES)
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            rec = records.contiguous()
+            assert rec.is_cuda and rec.element_size() == 1 and rec.numel() == n * EIP4844_RECORD.itemsize
+            out = torch.empty((n, EIP4844_PROOF_RECORD.itemsize), dtype=torch.uint8, device=_keep.device)
+            ev = torch.empty((n, EIP4844_EVALUATION_BYTES), dtype=torch.uint8, device=_keep.device) if evaluations else None
+            _check(load().zkw_eip4844_prove(self.handle, ctx.handle, ptr, n, C.c_void_p(rec.data_ptr() if n else None), C.c_void_p(out.data_ptr() if n else None),
+                                            C.c_void_p(ev.data_ptr() if evaluations and n else None)))
+            return (out, ev) if evaluations else out
+        rec = np.ascontiguousarray(records, dtype=EIP4844_RECORD).reshape(-1)
+        assert rec.size == n
+        out = np.zeros(n, EIP4844_PROOF_RECORD)
+        ev = np.zeros((n, EIP4844_EVALUATION_BYTES), np.uint8) if evaluations else None
+        _check(load().zkw_eip4844_prove(self.handle, ctx.handle, ptr, n, _np_ptr(rec) if n else None, _np_ptr(out) if n else None,
+                                        _np_ptr(ev) if evaluations and n else None))
+        return (out, ev) if evaluations else out
 
     def free(self):
         if self.handle:

@@ -736,6 +736,37 @@ typedef struct zkw_eip4844_record {
 } zkw_eip4844_record;
 int zkw_eip4844_witness(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n_blobs,
                         zkw_eip4844_record *out /*[n]*/);
+/* compute_proof (kzg/src/lib.rs:218-256) on the monomial setup: per polynomial j, values[j] = p_j(points[j]) and
+   proofs[j] = compress(sum_i q_i S[i]) with q = (p_j - values[j]) / (X - points[j]).  Coefficients, points and values
+   are 32 little-endian bytes below r (zkw_kzg_commit's form).  n_coeffs <= num_points.  A polynomial of fewer than
+   two coefficients has the point at infinity as its proof.  The quotient's coefficients are the intermediate values of
+   Horner's walk, for every point alike: one on the evaluation domain is no special case and nothing is inverted.
+   ZKW_ERR_INVALID, with the position in zkw_last_error, for a coefficient or a point that is not below r (the outputs
+   are then untouched).  One readback per call (the two range checks). */
+int zkw_kzg_open(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *coeffs /*[n_polys][n_coeffs][32]*/, size_t n_coeffs,
+                 size_t n_polys, const uint8_t *points /*[n_polys][32]*/, uint8_t *proofs /*[n_polys][48]*/,
+                 uint8_t *values /*[n_polys][32]*/);
+/* The two proofs that put a blob on L1: opening_proof is the fifth input of the point-evaluation precompile
+   (versioned_hash, z, y, commitment, proof), blob_proof the third part of the transaction's sidecar (blob in evaluation
+   form, commitment, proof).  The blob's polynomial is the one zkw_eip4844_witness commits to (element i = the
+   coefficient of X^(4095 - i)).  Its evaluation form is element i = p(w^brp12(i)), w = 7^((r - 1) / 4096) mod r, brp12
+   the 12-bit bit reversal, 32 big-endian bytes each (what eval_poly, kzg/src/lib.rs:327-358, pairs with
+   roots_of_unity_brp[i]).  blob_challenge (compute_challenge, lib.rs:360-383) = SHA-256("FSBLOBVERIFY_V1_" || 4096 as
+   16 big-endian bytes || the 4 096 evaluation-form elements || the 48 commitment bytes), read as a big-endian integer
+   and reduced below r; blob_proof opens the polynomial there (compute_proof_poly, lib.rs:285-288). */
+typedef struct zkw_eip4844_proof_record {      /* 160 bytes */
+    uint8_t opening_proof[48];   /* p(z) = y for the z, y of the blob's zkw_eip4844_record: the precompile's fifth input */
+    uint8_t blob_proof[48];      /* compute_proof_poly: the opening at blob_challenge                                  */
+    uint8_t blob_challenge[32];  /* compute_challenge (lib.rs:360-383), big-endian                                     */
+    uint8_t blob_value[32];      /* p(blob_challenge), big-endian                                                       */
+} zkw_eip4844_proof_record;
+/* records: what zkw_eip4844_witness wrote for the same blobs (commitment and evaluation_point are read).
+   blob_evaluations (may be NULL): the sidecar's blob, 4096 x 32 big-endian bytes, element i = p(w^brp12(i)).
+   Requires num_points == 4096; at most 32 767 blobs per call (two polynomials each).  Nothing is read back: in device
+   pointer mode the call only enqueues. */
+int zkw_eip4844_prove(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n_blobs,
+                      const zkw_eip4844_record *records /*[n]*/, zkw_eip4844_proof_record *out /*[n]*/,
+                      uint8_t *blob_evaluations /*[n][131072] or NULL*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
