@@ -31,8 +31,8 @@ struct SynthJob {
     const u64* challenges;  // [2][9]
     const u64* gp_ckpt;     // [ceil(capacity/64)][4] this instance's grand-product checkpoints: {lhs r0, lhs r1, rhs r0, rhs r1} entering cycle 64 g
     u64* trace;             // [RC_COLS][n_rows]
-    u32* hist;              // [256] lookup-value histogram of this trace (zeroed before the fills)
-    u32* nd_tiles;          // [ceil(capacity/256)] exclusive prefix of nondeterministic writes per 256-cycle tile
+    u32* hist;              // [256] lookup-value histogram of this trace: zero between calls (the boundary block of k_ram_fill_D reads and clears it)
+    const u32* nd_tiles;    // [ceil(capacity/256)] exclusive prefix of nondeterministic writes per 256-cycle tile (the builder's ZKW_RAM_ND_PREFIX)
     const u64* public_input;  // [4] commitment of the instance's closed-form input (k_ram_commitments): not written into the trace (the
                               // closed-form section derives the PI row), kept for callers that compare
     const zkw_ram_instance* first_inst;  // the block's first instance (its observable input is every instance's: postprocessing/mod.rs:358-364)
@@ -40,6 +40,20 @@ struct SynthJob {
                      // rows below the boundary rows, the gap rows of the regions, the unused columns of each row type, rows >= 256 of the multiplicity column —
                      // is still zero: the kernels skip those stores
 };
+
+// The job table of a launch: a call's jobs travel in the kernel's arguments (up to RC_INLINE_JOBS of them, a launch of its own), else
+// the kernels read an uploaded table (more jobs, or a context of a batch, whose merged launches keep their tables in the upload arena).
+// The bodies take either as `const J&` (zkw_launch.h): the same code both ways.
+constexpr int RC_INLINE_JOBS = 32;
+struct SynthJobsRef {
+    const SynthJob* p;
+    __device__ __forceinline__ const SynthJob& operator[](unsigned k) const { return p[k]; }
+};
+struct SynthJobsInline {
+    SynthJob j[RC_INLINE_JOBS];
+    __device__ __forceinline__ const SynthJob& operator[](unsigned k) const { return j[k]; }
+};
+static_assert(sizeof(SynthJobsInline) <= 3968, "the inline job table and the scalar arguments share the 4 KB of kernel arguments");
 
 constexpr int ROW_SLOTS[RC_NUM_ROW_TYPES] = RC_ROW_NUM_SLOTS_INIT;
 constexpr int ROW_LOOKUPS[RC_NUM_ROW_TYPES] = RC_ROW_NUM_LOOKUPS_INIT;
@@ -276,27 +290,18 @@ __device__ __forceinline__ void fill_row_B(const SynthJob& job, u32 i, u32 capac
 // ------------------------------------------------------------------------------------------------
 // Poseidon2 rows (regions PU and PS) and the general row that shares their inputs (A with PU, B with PS): one lane per cycle
 // stores the fused row and the Poseidon2 row's spare and lookup cells, then runs the permutation and stores all 130
-// flattened-gate variables as it goes. SIDE 0 = unsorted queue, 1 = sorted queue. The general row goes FIRST: the query and
-// its encodings are dead when the permutation starts (its 92 registers are the kernel's peak, 5 waves per SIMD), and the
+// flattened-gate variables as it goes. Side 0 = unsorted queue, 1 = sorted queue. The general row goes FIRST: the query and
+// its encodings are dead when the permutation starts (its registers are the kernel's peak, 5 waves per SIMD), and the
 // row's stores drain under the permutation's arithmetic.
+// ONE launch does both sides: grid z is the side. The two prologues are branches of a workgroup-uniform test and the permutation
+// follows them once, so the kernel's text is one side's round loops (two copies side by side would not fit the instruction cache).
 template <int SIDE>
-static __device__ __forceinline__ void k_ram_fill_poseidon(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity,
-                                                          size_t n_rows) {
-    __shared__ u32 sh_hist[256];
-    for (int t = threadIdx.x; t < 256; t += blockDim.x) sh_hist[t] = 0;
-    __syncthreads();
-    const SynthJob job = jobs[vb.y];
-    const u32 i = vb.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void ram_poseidon_prologue(const SynthJob& job, u32 i, u32 capacity, size_t n_rows, size_t row, bool can_pop,
+                                                      u64 s[12], u32* sh_hist) {
     u64* trace = job.trace;
-    const zkw_ram_instance* in = job.inst;
-    const size_t first = in->first_item, m = in->num_items;
-    const bool can_pop = i < capacity && i < m;
-    const size_t row = (size_t)(SIDE == 0 ? RC_ROW_PU : RC_ROW_PS) * RC_REGION_STRIDE(capacity) + i;
+    const size_t first = job.inst->first_item;
     zkw_mem_query q;  // the sorted item of this cycle
     memset(&q, 0, sizeof q);
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = 0;
     if (can_pop) {
         load_query(job.sorted_q + first + i, q);
         if (SIDE == 0) encode_raw_query(load_raw_query(job.unsorted_q + first + i), s); else encode_mem_query(q, s);
@@ -324,11 +329,33 @@ static __device__ __forceinline__ void k_ram_fill_poseidon(const VB& vb, const S
             hist_bytes(sh_hist, q.timestamp); hist_bytes(sh_hist, q.page); hist_bytes(sh_hist, q.value[4]);
         }
         if (!job.tail_clean) for (int c = RC_G + 12; c < RC_G + RC_L; c++) TR(c, row) = 0;
+    }
+}
+
+template <class J>
+static __device__ __forceinline__ void k_ram_fill_poseidon(const VB& vb, const J& jobs, u32 capacity, size_t n_rows) {
+    __shared__ u32 sh_hist[256];
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) sh_hist[t] = 0;
+    __syncthreads();
+    const SynthJob job = jobs[vb.y];
+    const u32 side = vb.z;
+    const u32 i = vb.x * blockDim.x + threadIdx.x;
+    u64* trace = job.trace;
+    const zkw_ram_instance* in = job.inst;
+    const size_t first = in->first_item, m = in->num_items;
+    const bool can_pop = i < capacity && i < m;
+    const size_t row = (size_t)(side == 0 ? RC_ROW_PU : RC_ROW_PS) * RC_REGION_STRIDE(capacity) + i;
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 8; k++) s[k] = 0;
+    if (side == 0) ram_poseidon_prologue<0>(job, i, capacity, n_rows, row, can_pop, s, sh_hist);
+    else ram_poseidon_prologue<1>(job, i, capacity, n_rows, row, can_pop, s, sh_hist);
+    if (i < capacity) {
         __builtin_amdgcn_sched_barrier(0);  // nothing of the rows above moves into the permutation, where every register counts
         const RegsIn ri = regs_in(in);
         // capacity part of the queue head entering this cycle
-        const u64* caps = SIDE == 0 ? job.unsorted_caps : job.sorted_caps;
-        const u64* prev_cap = i == 0 ? (SIDE == 0 ? ri.uh : ri.sh) + 8 : caps + 4 * (first + (i - 1 < m ? i - 1 : m - 1));
+        const u64* caps = side == 0 ? job.unsorted_caps : job.sorted_caps;
+        const u64* prev_cap = i == 0 ? (side == 0 ? ri.uh : ri.sh) + 8 : caps + 4 * (first + (i - 1 < m ? i - 1 : m - 1));
 #pragma unroll
         for (int k = 0; k < 4; k++) s[8 + k] = prev_cap[k];
         fill_flattened_poseidon(trace, n_rows, row, s);
@@ -343,42 +370,8 @@ __device__ __forceinline__ bool nd_flag(bool can_pop, const zkw_mem_query& q) {
     return can_pop && q.timestamp == 0 && q.page == RC_HEAP_PAGE && q.rw_flag && !q.value_is_pointer;
 }
 
-// per 256-cycle tile: number of nondeterministic writes; then an exclusive scan per instance
-static __device__ __forceinline__ void k_ram_nd_tiles(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity) {
-    __shared__ u32 sh[4];
-    const SynthJob job = jobs[vb.y];
-    const u32 i = vb.x * blockDim.x + threadIdx.x;
-    const zkw_ram_instance* in = job.inst;
-    bool f = false;
-    if (i < capacity && i < in->num_items) {
-        zkw_mem_query q;
-        load_query(job.sorted_q + in->first_item + i, q);
-        f = nd_flag(true, q);
-    }
-    u32 cnt = __popcll(__ballot(f));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) job.nd_tiles[vb.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-static __device__ __forceinline__ void k_ram_nd_scan(const VB& vb, const SynthJob* __restrict__ jobs, int n_jobs, u32 n_tiles) {
-    // one wave per job: exclusive prefix over the tile counts, 64 tiles at a time
-    u32* t = jobs[vb.x].nd_tiles;
-    const int lane = threadIdx.x;
-    u32 acc = 0;
-    for (u32 base = 0; base < n_tiles; base += 64) {
-        const u32 k = base + lane;
-        const u32 v = k < n_tiles ? t[k] : 0;
-        u32 incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
-        if (k < n_tiles) t[k] = acc + incl - v;
-        acc += __shfl(incl, 63);
-    }
-}
-
-static __device__ __forceinline__ void k_ram_fill_C(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity, size_t n_rows) {
+template <class J>
+static __device__ __forceinline__ void k_ram_fill_C(const VB& vb, const J& jobs, u32 capacity, size_t n_rows) {
     __shared__ u32 sh_hist[256];
     __shared__ u32 sh_wave[4];
     sh_hist[threadIdx.x] = 0;
@@ -477,11 +470,24 @@ static __device__ __forceinline__ void k_ram_fill_C(const VB& vb, const SynthJob
 // 1-D grid: the first n_jobs blocks fill the boundary rows of one trace each — the register rows and the closed-form section, a chain of a
 // dozen dependent permutations (ram_boundary_block below) — dispatched first and at raised priority so that the row-D blocks' work hides
 // it (it reads the last cycle's row C, an earlier kernel; nothing of row D); then n_tiles blocks of 256 cycles per trace.
+// The boundary block also writes the multiplicities: row D has no lookup cells, so job.hist is final when this kernel starts. It leaves
+// the histogram zero for the next call (no memset per call: the scratch is zero between calls).
 __device__ __forceinline__ void ram_boundary_block(const SynthJob& job, u32 capacity, size_t n_rows);
+constexpr int RC_CF_LOOKUP_CELLS = 24;  // VIN / VOUT byte cells (counted in job.hist by k_ram_fill_C)
+// rows 0..255 of the multiplicity column (256 threads): histogram of the used lookup cells + every unused lookup cell counts as value 0
+__device__ __forceinline__ void ram_fill_multiplicities(const SynthJob& job, u32 capacity, size_t n_rows) {
+    const u32 r = threadIdx.x;
+    u64 v = job.hist[r];
+    job.hist[r] = 0;
+    if (r == 0) v += (u64)RC_L * n_rows - (u64)LOOKUPS_PER_CYCLE * capacity - RC_CF_LOOKUP_CELLS;
+    if (r < n_rows) job.trace[(size_t)RC_MULT_COL * n_rows + r] = v;
+}
 constexpr int RC_D_TILES = 4;  // tiles of 256 cycles per row-D block
-static __device__ __forceinline__ void k_ram_fill_D(const VB& vb, const SynthJob* __restrict__ jobs, u32 n_jobs, u32 n_tiles, u32 capacity, size_t n_rows) {
+template <class J>
+static __device__ __forceinline__ void k_ram_fill_D(const VB& vb, const J& jobs, u32 n_jobs, u32 n_tiles, u32 capacity, size_t n_rows) {
     if (vb.x < n_jobs) {
         __builtin_amdgcn_s_setprio(3);
+        ram_fill_multiplicities(jobs[vb.x], capacity, n_rows);
         ram_boundary_block(jobs[vb.x], capacity, n_rows);
         return;
     }
@@ -543,24 +549,25 @@ static __device__ __forceinline__ void k_ram_fill_D(const VB& vb, const SynthJob
     }
 }
 
-// the zero padding from the first boundary row down (all general + lookup columns) and the multiplicity column.
+// the zero padding of a slot that is not clean (launched only when a call has one): from the first row below the boundary rows down, all
+// general + lookup columns, and rows >= 256 of the multiplicity column (rows 0..255 are the boundary block's, k_ram_fill_D).
 // blockIdx.x = (column, chunk): every block streams one contiguous chunk of one column with 16-byte stores, so
 // at any time the blocks in flight write ~all columns at once (a sweep of all blocks over one column at a time
 // runs at 3.9 TB/s, this at 5.6, tools/ubench_fill.hip). The last TAIL_CHUNKS blocks of a job do the multiplicity
-// column. grid.y = job.
+// column.
 constexpr int TAIL_CHUNKS = 8;
 constexpr int RC_BOUNDARY_ROWS = RC_NUM_ROW_TYPES - RC_ROWS_PER_CYCLE;  // register rows, PI, the closed-form section
-constexpr int RC_CF_LOOKUP_CELLS = 24;                                   // VIN / VOUT byte cells (counted in job.hist by k_ram_fill_C)
 static_assert(RC_BOUNDARY_ROWS % 2 == 0, "the tail's 16-byte stores start below the boundary rows");
-static __device__ __forceinline__ void k_ram_fill_tail(const VB& vb, const SynthJob* __restrict__ jobs, u32 capacity, size_t n_rows) {
+template <class J>
+static __device__ __forceinline__ void k_ram_fill_tail(const VB& vb, const J& jobs, u32 capacity, size_t n_rows) {
     // 1-D grid: (RC_G + RC_L + 1) * TAIL_CHUNKS blocks per trace (the boundary rows above the zero padding are k_ram_fill_D's first blocks)
     constexpr u32 PER_JOB = (RC_G + RC_L + 1) * TAIL_CHUNKS;
     const u32 bid = vb.x % PER_JOB;
     const SynthJob& job = jobs[vb.x / PER_JOB];
+    if (job.tail_clean) return;
     u64* trace = job.trace;
     const int col = bid / TAIL_CHUNKS, ch = bid % TAIL_CHUNKS;
     if (col < RC_G + RC_L) {
-        if (job.tail_clean) return;
         const size_t bnd = (size_t)RC_BOUNDARY_ROW(capacity) + RC_BOUNDARY_ROWS;  // a multiple of 2 rows: 16-byte aligned
         const size_t n_pairs = (n_rows - bnd) / 2;                               // n_rows is even (power of two)
         const size_t per = (n_pairs + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_pairs ? lo + per : n_pairs;
@@ -569,17 +576,9 @@ static __device__ __forceinline__ void k_ram_fill_tail(const VB& vb, const Synth
         for (size_t k = lo + threadIdx.x; k < hi; k += 256) c2[k] = z;
         return;
     }
-    // multiplicities: histogram of the used lookup cells + every unused lookup cell counts as value 0
     u64* m = trace + (size_t)RC_MULT_COL * n_rows;
     const size_t per = (n_rows + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_rows ? lo + per : n_rows;
-    for (size_t r = lo + threadIdx.x; r < (job.tail_clean && hi > 256 ? (lo < 256 ? 256 : lo) : hi); r += 256) {  // (a clean slot: rows >= 256 of the column are still zero)
-        u64 v = 0;
-        if (r < 256) {
-            v = job.hist[r];
-            if (r == 0) v += (u64)RC_L * n_rows - (u64)LOOKUPS_PER_CYCLE * capacity - RC_CF_LOOKUP_CELLS;
-        }
-        m[r] = v;
-    }
+    for (size_t r = (lo < 256 ? 256 : lo) + threadIdx.x; r < hi; r += 256) m[r] = 0;
 }
 
 static __constant__ rc_link c_links[RC_NUM_LINKS] = RC_LINKS_INIT;

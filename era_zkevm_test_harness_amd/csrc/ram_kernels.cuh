@@ -542,6 +542,7 @@ struct RamBlock {
     zkw_ram_instance* instances;    // [ceil(n/capacity)]
     u32* nondet_prefix;             // [n_instances] scratch: nondeterministic writes per chunk
     u64* gp_ckpt;                   // [n_instances][ceil(capacity/64)][4] grand-product checkpoints of the block's instances
+    u32* nd_prefix;                 // [n_instances][ceil(capacity/256)] the circuit's nondeterministic writes of the instance before each tile of 256 cycles
     u64 n;
     u32 capacity;
     u32 num_nondet_heap_queries;
@@ -551,22 +552,38 @@ __device__ __forceinline__ void copy12(u64* dst, const u64* src) {
     for (int k = 0; k < 12; k++) dst[k] = src[k];
 }
 
-// pass 1: count nondeterministic writes per chunk (rw && ts == 0 && page == BOOTLOADER_HEAP_PAGE)
+// pass 1: count nondeterministic writes per chunk (rw && ts == 0 && page == BOOTLOADER_HEAP_PAGE). The walk is tile by tile (256
+// cycles of the instance at a time), so it leaves the synthesis its row-C counter on the way: nd_prefix[inst][t] = the writes that the
+// CIRCUIT counts (the same flag and not a pointer: nd_flag of ram_circuit_kernels.cuh) in the instance's cycles before tile t. Every tile
+// of the capacity gets its entry, also those past a short last instance.
 static __device__ __forceinline__ void k_ram_count_nondet(const VB& vb, const RamBlock* __restrict__ blocks) {
     const RamBlock b = blocks[vb.y];
     const u64 n_inst = (b.n + b.capacity - 1) / b.capacity;
-    __shared__ u32 sh[4];
+    const u32 n_tiles = (b.capacity + 255) / 256;
+    __shared__ u32 sh[2][2][4];  // [tile parity][FSM count, circuit count][wave]: one barrier per tile
     for (u64 inst = vb.x; inst < n_inst; inst += vb.nx) {
         const u64 lo = inst * b.capacity, hi = lo + b.capacity < b.n ? lo + b.capacity : b.n;
-        u32 cnt = 0;
-        for (u64 i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-            const zkw_mem_query* q = b.sorted_q + b.sorted_perm[i];
-            cnt += (q->rw_flag && q->timestamp == 0 && q->page == ZKW_BOOTLOADER_HEAP_PAGE) ? 1u : 0u;
+        u32 cnt = 0, before = 0;  // (thread 0's running sums)
+        for (u32 t = 0; t < n_tiles; t++) {
+            const u64 i = lo + 256 * (u64)t + threadIdx.x;
+            bool f = false, fc = false;
+            if (i < hi) {
+                const zkw_mem_query* q = b.sorted_q + b.sorted_perm[i];
+                f = q->rw_flag && q->timestamp == 0 && q->page == ZKW_BOOTLOADER_HEAP_PAGE;
+                fc = f && !q->value_is_pointer;
+            }
+            const u32 c = __popcll(__ballot(f)), cc = __popcll(__ballot(fc));
+            if ((threadIdx.x & 63) == 0) { sh[t & 1][0][threadIdx.x >> 6] = c; sh[t & 1][1][threadIdx.x >> 6] = cc; }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const u32* s0 = sh[t & 1][0];
+                const u32* s1 = sh[t & 1][1];
+                b.nd_prefix[inst * n_tiles + t] = before;
+                cnt += s0[0] + s0[1] + s0[2] + s0[3];
+                before += s1[0] + s1[1] + s1[2] + s1[3];
+            }
         }
-        for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d, 64);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) b.nondet_prefix[inst] = sh[0] + sh[1] + sh[2] + sh[3];
+        if (threadIdx.x == 0) b.nondet_prefix[inst] = cnt;
         __syncthreads();
     }
 }

@@ -1078,6 +1078,9 @@ struct zkw_ram_witness {
     bool z_valid = false;
     u64 *zbuf_l = nullptr, *zbuf_r = nullptr;
     u64* gp_ckpt = nullptr;
+    // the circuit's nondeterministic writes of an instance before each of its tiles of 256 cycles ([n_instances][ceil(capacity/256)],
+    // left by the builder's counting pass): row C of the synthesis adds its in-tile count, no synthesis call counts again
+    u32* nd_prefix = nullptr;
     zkw_mem_query* sq_win = nullptr;  // the sorted queries of the blocks being synthesized, gathered per synthesis call
     size_t zcap = 0, sqcap = 0;       // capacity of the chain windows / of the sorted window, in queue items
     zkw_ram_instance* instances = nullptr;
@@ -1087,7 +1090,7 @@ struct zkw_ram_witness {
     void release() {
         void* ptrs[] = {sorted_q, perm, owned_q, unsorted_enc, sorted_enc, unsorted_caps, sorted_caps, unsorted_marks, sorted_marks,
                         unsorted_tails, sorted_tails, challenges,
-                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, zbuf_l, zbuf_r, sq_win, gp_ckpt};
+                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, zbuf_l, zbuf_r, sq_win, gp_ckpt, nd_prefix};
         for (void* p : ptrs)
             if (p) dev_free(p);
         sorted_q = nullptr;
@@ -1102,6 +1105,7 @@ struct zkw_ram_witness {
         z_valid = false;
         zbuf_l = zbuf_r = nullptr;
         gp_ckpt = nullptr;
+        nd_prefix = nullptr;
         sq_win = nullptr;
         zcap = sqcap = 0;
         instances = nullptr;
@@ -1112,6 +1116,7 @@ struct zkw_ram_witness {
 
 extern "C" void zkw_ram_witness_free(zkw_ram_witness* w);
 static inline size_t ram_gp_groups(uint32_t capacity) { return ((size_t)capacity + 63) / 64; }  // checkpoints per instance
+static inline size_t ram_nd_tiles(uint32_t capacity) { return ((size_t)capacity + 255) / 256; }  // tiles of 256 cycles per instance
 static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
     const size_t t = w->total, ni = w->n_instances;
     HIP_TRY(dev_malloc((void**)&w->perm, (t + 1) * sizeof(u32)));
@@ -1132,6 +1137,7 @@ static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
         HIP_TRY(dev_malloc((void**)&w->sq_win, (w->sqcap + 1) * sizeof(zkw_mem_query)));
     }
     HIP_TRY(dev_malloc((void**)&w->gp_ckpt, (ni * ram_gp_groups(w->capacity) + 1) * 4 * sizeof(u64)));
+    HIP_TRY(dev_malloc((void**)&w->nd_prefix, (ni * ram_nd_tiles(w->capacity) + 1) * sizeof(u32)));
     HIP_TRY(dev_malloc((void**)&w->instances, (ni + 1) * sizeof(zkw_ram_instance)));
     HIP_TRY(dev_malloc((void**)&w->nondet_counts, (ni + 1) * sizeof(u32)));
     HIP_TRY(dev_malloc((void**)&w->compact_forms, (ni + 1) * COMPACT_FORM_LEN * sizeof(u64)));
@@ -1358,6 +1364,7 @@ static int ram_run(zkw_ctx* ctx, zkw_ram_witness* w, const zkw_mem_query* d_q, c
                                       w->instances + w->inst_offsets[b],
                                       w->nondet_counts + w->inst_offsets[b],
                                       w->gp_ckpt + 4 * ram_gp_groups(w->capacity) * w->inst_offsets[b],
+                                      w->nd_prefix + ram_nd_tiles(w->capacity) * w->inst_offsets[b],
                                       n,
                                       w->capacity,
                                       n_nondet ? n_nondet[b] : 0u};
@@ -1537,6 +1544,7 @@ static const void* ram_array(const zkw_ram_witness* w, int what, size_t* bytes, 
         case ZKW_RAM_COMPACT_FORMS: *bytes = w->n_instances * COMPACT_FORM_LEN * 8; p = w->compact_forms; break;
         case ZKW_RAM_PUBLIC_INPUTS: *bytes = w->n_instances * 32; p = w->public_inputs; break;
         case ZKW_RAM_GP_CKPT: *bytes = w->n_instances * ram_gp_groups(w->capacity) * 32; p = w->gp_ckpt; break;
+        case ZKW_RAM_ND_PREFIX: *bytes = w->n_instances * ram_nd_tiles(w->capacity) * sizeof(u32); p = w->nd_prefix; break;
         default: *bytes = 0; st = ZKW_ERR_INVALID; break;
     }
 #undef RAM_LAZY
@@ -1670,19 +1678,28 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     }
     ZKW_TRY(launch_check("k_gather_encode"));
     const u32 rstride = (u32)RC_REGION_STRIDE(capacity);  // rows per region incl. the alignment gap
-    const u32 n_tiles = (rstride + 255) / 256;
-    u32 *d_hist = nullptr, *d_nd = nullptr;
-    ZKW_TRY(ctx->scratch_t<u32>("synth_hist", n_instances * 256, &d_hist));
-    ZKW_TRY(ctx->scratch_t<u32>("synth_nd", n_instances * n_tiles, &d_nd));
-    HIP_TRY(ctx->memset_async(d_hist, 0, n_instances * 256 * sizeof(u32)));
+    const u32 n_tiles = (rstride + 255) / 256;             // (= ram_nd_tiles(capacity): the stride rounds up to 64)
+    u32* d_hist = nullptr;
+    {   // the histograms are zero between calls (zkw_ctx.h synth_hist_dirty): no memset on a warm call
+        const DevBuf& hb = ctx->pool["synth_hist"];
+        const void* had = hb.p;
+        ZKW_TRY(ctx->scratch_t<u32>("synth_hist", n_instances * 256, &d_hist));
+        if (hb.p != had || ctx->synth_hist_dirty) HIP_TRY(ctx->memset_async(hb.p, 0, hb.cap));  // new or grown, or left behind by a failed call
+        ctx->synth_hist_dirty = true;  // until the last launch of this call is queued
+    }
     SlotClaims claims(t);
-    std::vector<SynthJob> jobs(n_instances);
+    // up to RC_INLINE_JOBS jobs travel in the kernels' arguments: no copy, no staging buffer to wait for. A context of a batch, and a
+    // longer call, upload the table.
+    const bool inline_jobs = n_instances <= (size_t)RC_INLINE_JOBS && !ctx->batched();
+    SynthJobsInline tab;
+    std::vector<SynthJob> jobs(inline_jobs ? 0 : n_instances);
+    bool all_clean = true;
     size_t b = b_first;
     for (size_t k = 0; k < n_instances; k++) {
         const size_t idx = first_instance + k;
         while (b + 1 < n_blocks && w->inst_offsets[b + 1] <= idx) b++;
         const size_t lo = w->offsets[b];
-        SynthJob& j = jobs[k];
+        SynthJob& j = inline_jobs ? tab.j[k] : jobs[k];
         j.inst = w->instances + idx;
         j.sorted_q = w->sq_win + (lo - z_base);
         j.unsorted_q = w->unsorted_q + lo;
@@ -1698,32 +1715,42 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
             bool clean = false;
             j.trace = claims.claim(slot, tag, &clean);
             j.tail_clean = clean;
+            all_clean = all_clean && clean;
         }
         j.hist = d_hist + 256 * k;
-        j.nd_tiles = d_nd + (size_t)n_tiles * k;
+        j.nd_tiles = w->nd_prefix + (size_t)n_tiles * idx;
         j.public_input = w->public_inputs + 4 * idx;
         j.first_inst = w->instances + w->inst_offsets[b];
     }
-    SynthJob* d_jobs = nullptr;
-    ZKW_TRY(ctx->upload("synth_jobs", jobs, &d_jobs));
+    SynthJobsRef ref{nullptr};
+    if (!inline_jobs) {
+        SynthJob* d_jobs = nullptr;
+        ZKW_TRY(ctx->upload("synth_jobs", jobs, &d_jobs));
+        ref.p = d_jobs;
+    } else {
+        for (size_t k = n_instances; k < (size_t)RC_INLINE_JOBS; k++) tab.j[k] = tab.j[0];  // (never indexed: the grids cover n_instances jobs)
+    }
+    // one body, the job table either way (a launch of its own with the table in its arguments is never left with a batch)
+#define SYNTH_LAUNCH(kernel, name, grid, bs, ...)                                                                                  \
+    do {                                                                                                                           \
+        if (inline_jobs) {                                                                                                         \
+            LaunchSig<decltype(&kernel<SynthJobsInline>)>::template single<&kernel<SynthJobsInline>, bs>(ctx->stream, grid, 0, tab, __VA_ARGS__); \
+            ZKW_TRY(launch_check(name));                                                                                           \
+        } else {                                                                                                                   \
+            ZKW_LAUNCH_D(ctx, (kernel<SynthJobsRef>), name, grid, bs, 0, ref, __VA_ARGS__);                                        \
+        }                                                                                                                          \
+    } while (0)
     const unsigned nj = (unsigned)n_instances;
-    const dim3 g64((rstride + 63) / 64, nj), g256(n_tiles, nj);
-    { Prof _p(ctx, "k_ram_nd_tiles"); ZKW_LAUNCH_D(ctx, (k_ram_nd_tiles), "k_ram_nd_tiles", g256, 256, 0, d_jobs, capacity); }
-    ZKW_TRY(launch_check("k_ram_nd_tiles"));
-    { Prof _p(ctx, "k_ram_nd_scan"); ZKW_LAUNCH(ctx, k_ram_nd_scan, nj, 64, d_jobs, (int)nj, n_tiles); }
-    ZKW_TRY(launch_check("k_ram_nd_scan"));
-    // <0> fills the PU rows and row A, <1> the PS rows and row B (one lane per cycle writes both)
-    { Prof _p(ctx, "k_ram_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ram_fill_poseidon<0>), "k_ram_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_poseidon<0>"));
-    { Prof _p(ctx, "k_ram_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ram_fill_poseidon<1>), "k_ram_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_poseidon<1>"));
-    { Prof _p(ctx, "k_ram_fill_C"); ZKW_LAUNCH_D(ctx, (k_ram_fill_C), "k_ram_fill_C", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_C"));
+    const dim3 g64x2((rstride + 63) / 64, nj, 2), g256(n_tiles, nj);
+    // row C needs nothing but the gathered window (its counter's tile prefixes are the builder's); the boundary rows read its last row
+    { Prof _p(ctx, "k_ram_fill_C"); SYNTH_LAUNCH(k_ram_fill_C, "k_ram_fill_C", g256, 256, capacity, n_rows); }
+    // grid z = 0 fills the PU rows and row A, z = 1 the PS rows and row B (one lane per cycle writes both): one launch, two in the profile
+    { Prof _p(ctx, "k_ram_fill_poseidon", 2); SYNTH_LAUNCH(k_ram_fill_poseidon, "k_ram_fill_poseidon", g64x2, 64, capacity, n_rows); }
     { Prof _p(ctx, "k_ram_fill_D"); const unsigned d_tiles = (unsigned)((rstride + RC_D_TILES * 256 - 1) / (RC_D_TILES * 256));  // row D: RC_D_TILES tiles per block (they share one inversion per lane)
-      ZKW_LAUNCH(ctx, k_ram_fill_D, nj * (d_tiles + 1), 256, d_jobs, nj, d_tiles, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_D"));
-    { Prof _p(ctx, "k_ram_fill_tail"); ZKW_LAUNCH(ctx, k_ram_fill_tail, nj * ((RC_G + RC_L + 1) * TAIL_CHUNKS), 256, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ram_fill_tail"));
+      SYNTH_LAUNCH(k_ram_fill_D, "k_ram_fill_D", dim3(nj * (d_tiles + 1)), 256, nj, d_tiles, capacity, n_rows); }
+    ctx->synth_hist_dirty = false;  // row D's boundary blocks leave the histograms zero
+    if (!all_clean) { Prof _p(ctx, "k_ram_fill_tail"); SYNTH_LAUNCH(k_ram_fill_tail, "k_ram_fill_tail", dim3(nj * ((RC_G + RC_L + 1) * TAIL_CHUNKS)), 256, capacity, n_rows); }
+#undef SYNTH_LAUNCH
     return claims.commit_if(ctx->sync_if_host());
 }
 

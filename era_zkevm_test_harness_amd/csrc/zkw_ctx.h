@@ -143,10 +143,13 @@ struct zkw_ctx {
     int chain_form = 0;  // lanes per Poseidon2 state in the queue-chain kernel: 4 (quad), 16 (row), 0 = auto
     int netlist_fill_form = 0;  // 0: a wave per cycle (k_nl_fill), 1: a lane per cycle (k_nl_walk + k_nl_expand)
     std::map<std::string, DevBuf> pool;  // named grow-only scratch
+    // "synth_hist" (the lookup histograms of zkw_ram_synthesize) is ZERO between calls: zeroed when it is allocated or grown, cleared by
+    // the kernel that reads it, and zeroed again by the next call when one failed between its first and its last launch (this flag)
+    bool synth_hist_dirty = false;
     std::map<std::string, HostStage> stages;
     // optional per-kernel timing with HIP events on the context's stream (zkw_profile_*)
     bool profiling = false;
-    struct ProfSpan { const char* name; hipEvent_t a, b; };
+    struct ProfSpan { const char* name; hipEvent_t a, b; unsigned weight; };  // weight: the launches the span counts as (a merged launch of two keeps the per-launch averages comparable)
     std::vector<ProfSpan> spans;
     std::vector<hipEvent_t> free_events;
     std::map<std::string, std::pair<double, uint64_t>> prof_totals;  // name -> (ms, launches)
@@ -165,7 +168,7 @@ struct zkw_ctx {
             if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
                 auto& t = prof_totals[sp.name];
                 t.first += ms;
-                t.second += 1;
+                t.second += sp.weight;
             }
             free_events.push_back(sp.a);
             free_events.push_back(sp.b);
@@ -290,12 +293,12 @@ struct zkw_ctx {
 struct Prof {
     zkw_ctx* c;
     hipEvent_t b = nullptr;
-    Prof(zkw_ctx* ctx, const char* name) : c(ctx) {
+    Prof(zkw_ctx* ctx, const char* name, unsigned weight = 1) : c(ctx) {
         if (!c->profiling || c->batched()) return;
         hipEvent_t a = c->prof_event();
         b = c->prof_event();
         (void)hipEventRecord(a, c->stream);
-        c->spans.push_back(zkw_ctx::ProfSpan{name, a, b});
+        c->spans.push_back(zkw_ctx::ProfSpan{name, a, b, weight});
     }
     ~Prof() {
         if (b) (void)hipEventRecord(b, c->stream);

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("ZKW_LIB", os.path.join(_HERE, "libzkw.so"))  # ZKW_LI
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_CHECK_FAILED = 0, -1, -2, -3, -4, -5
 PTR_HOST, PTR_DEVICE = 0, 1
 (RAM_SORTED_QUERIES, RAM_UNSORTED_ENC, RAM_SORTED_ENC, RAM_UNSORTED_TAILS, RAM_SORTED_TAILS, RAM_CHALLENGES,
- RAM_LHS_Z, RAM_RHS_Z, RAM_INSTANCES, RAM_COMPACT_FORMS, RAM_PUBLIC_INPUTS, RAM_GP_CKPT) = range(12)
+ RAM_LHS_Z, RAM_RHS_Z, RAM_INSTANCES, RAM_COMPACT_FORMS, RAM_PUBLIC_INPUTS, RAM_GP_CKPT, RAM_ND_PREFIX) = range(13)
 
 # every symbol include/zkw.h declares: (name, restype, argtypes)
 _vp, _sz, _u32, _u64p, _int = C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_int
@@ -1077,7 +1077,7 @@ class DecommitWitness:
 class RamWitness:
     """Owner of a zkw_ram_witness handle (block-wide arrays + per-instance records, all in HBM)."""
 
-    _DTYPES = {RAM_SORTED_QUERIES: MEM_QUERY, RAM_INSTANCES: RAM_INSTANCE}
+    _DTYPES = {RAM_SORTED_QUERIES: MEM_QUERY, RAM_INSTANCES: RAM_INSTANCE, RAM_ND_PREFIX: np.dtype("<u4")}
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -1112,7 +1112,8 @@ class RamWitness:
         t = self.num_items
         shape = {RAM_UNSORTED_ENC: (t, 8), RAM_SORTED_ENC: (t, 8), RAM_UNSORTED_TAILS: (t, 12),
                  RAM_SORTED_TAILS: (t, 12), RAM_CHALLENGES: (-1, 2, 9), RAM_COMPACT_FORMS: (-1, 18),
-                 RAM_PUBLIC_INPUTS: (-1, 4), RAM_GP_CKPT: (self.num_instances, -1, 4)}.get(what)
+                 RAM_PUBLIC_INPUTS: (-1, 4), RAM_GP_CKPT: (self.num_instances, -1, 4),
+                 RAM_ND_PREFIX: (self.num_instances, -1)}.get(what)
         return out.reshape(shape) if shape else out
 
     def free(self):

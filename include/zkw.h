@@ -311,7 +311,10 @@ enum {
     /* grand-product checkpoints: the accumulators {lhs rep 0, lhs rep 1, rhs rep 0, rhs rep 1} entering cycle 64 g of every
        instance (its FSM input for g = 0, else the chain value at its last item popped before that cycle); what the
        synthesis reads instead of the chains */
-    ZKW_RAM_GP_CKPT = 11        /* uint64_t[n_instances][ceil(capacity/64)][4] */
+    ZKW_RAM_GP_CKPT = 11,       /* uint64_t[n_instances][ceil(capacity/64)][4] */
+    /* nondeterministic writes of the instance before each tile of 256 cycles (exclusive, without the FSM input's
+       num_nondeterministic_writes): what row C of the synthesis adds its in-tile count to */
+    ZKW_RAM_ND_PREFIX = 12      /* uint32_t[n_instances][ceil(capacity/256)] */
 };
 size_t zkw_ram_witness_num_instances(const zkw_ram_witness *w);
 size_t zkw_ram_witness_num_items(const zkw_ram_witness *w);
