@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <vector>
 #include "../../era_zkevm_test_harness_amd/csrc/gl64.cuh"
+#include "gl_mul_flags.h"
 using gl::u32;
 using gl::u64;
 
@@ -30,14 +31,8 @@ static u64 sm(u64& s) {
     return z ^ (z >> 31);
 }
 
-// cm * 4 + c1 * 2 + b1 of mul_vcc(a, b)
-static int flags(u64 a, u64 b) {
-    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
-    const unsigned __int128 q = (unsigned __int128)((u64)a0 * b1) + (u64)a1 * b0, pr = (unsigned __int128)a * b;
-    const u32 w0 = (u32)pr, w1 = (u32)(pr >> 32), w2 = (u32)(pr >> 64), w3 = (u32)(pr >> 96);
-    const unsigned __int128 x = (unsigned __int128)w2 * 0xFFFFFFFFu + (((u64)w1 << 32) | w0);
-    return (int)(q >> 64) * 4 + (int)(x >> 64) * 2 + ((u64)x < w3 ? 1 : 0);
-}
+// cm * 4 + c1 * 2 + b1 of mul_vcc(a, b): the host word model shared with gl_field_test.hip
+static int flags(u64 a, u64 b) { return gl_mul_flags(a, b); }
 
 int main() {
     const std::vector<u64> edge = {0, 1, 0xFFFFFFFFull, 0x100000000ull, 0x100000001ull, 0x8000000000000000ull, gl::P - 1, gl::P, gl::P + 1,
@@ -47,11 +42,7 @@ int main() {
         for (u64 y : edge) { a.push_back(x); b.push_back(y); }
 
     // flag combinations: seeded candidates of a few shapes, then the built pairs; up to 32 kept per combination
-    static const u64 built[][2] = {
-        {0xe6eb8c9efd69fe29ull, 0xe7bd541e6870ff79ull}, {0xcd464138e6233255ull, 0xcbda28c7fd7a54caull}, {0xde527100f814e8a3ull, 0xe074284f872cabbdull},
-        {0xe87c966cf77b9aa3ull, 0xd8a27c493fb105baull}, {0xe1da8978e06f5c67ull, 0xf426792c4ee52fccull}, {0xd8921396c0ddb74dull, 0xe1082b5b6fc7281eull},
-        {0xc021c246e148b905ull, 0xc0ac1741fe4b8282ull}, {0xd65ca199c1c5f494ull, 0xed5dd83dd7ec64a2ull}, {0xe76c9686cff99085ull, 0xc5494e5ac62cdf56ull},
-        {0xf1fefe17c04e698dull, 0xe3e33286e39402bbull}, {0xe0d3707dde9dbc8full, 0xdf6aec11ce98637full}, {0xfc0f574ccdb8abc9ull, 0xc41a5667f81c1196ull}};
+    const auto& built = GL_MUL_BUILT_PAIRS;
     int kept[8] = {0};
     auto keep = [&](u64 x, u64 y) {
         const int f = flags(x, y);
