@@ -1,10 +1,12 @@
 // zkw_kzg.hip — the EIP-4844 blob witness behind include/zkw.h: zkw_kzg_settings (the monomial trusted setup as a fixed-base table in
 // HBM), zkw_kzg_commit and zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:119-231 of the reference), and the KZG proofs
-// zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs). Kernels and the decomposition: kzg_kernels.cuh,
-// kzg_open_kernels.cuh; field and group arithmetic: bls12_381.cuh.
+// zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs), and their check, zkw_kzg_verifier with
+// zkw_kzg_verify and zkw_eip4844_verify (verify_kzg_proof). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh,
+// kzg_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
 #include "kzg_open_kernels.cuh"
+#include "kzg_verify_kernels.cuh"
 
 #include <cstddef>
 
@@ -255,5 +257,125 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
     { Prof _p(ctx, "k_kzg_proofs_out"); ZKW_LAUNCH(ctx, k_kzg_proofs_out, blocks_for(n_blobs * 96, 256), 256, (const uint8_t*)d_proofs, (u32)nb, prf); }
     ZKW_TRY(ctx->finish_out(out, d_out, n_blobs));
     if (blob_evaluations) ZKW_TRY(ctx->finish_out(blob_evaluations, d_ev, n_blobs * KZG_EVAL_BYTES));
+    return ctx->sync_if_host();
+}
+
+// ---- the check: a verifier is the prepared lines of -G2 and [tau] G2; a call is two kernels and reads nothing back ----------------------
+static_assert(sizeof(bls::G2Line) == 192, "a line is two elements of Fq2");
+
+struct zkw_kzg_verifier {
+    zkw_ctx* ctx = nullptr;
+    size_t bytes = 0;
+    bls::G2Line* lines = nullptr;  // [2][68]: -G2, [tau] G2
+};
+
+static const char* kzg_g2_reason(u32 status) {
+    switch (status) {
+        case bls::G1_NOT_COMPRESSED: return "bit 7 of its first byte is clear (not a compressed point)";
+        case bls::G1_BAD_INFINITY: return "the infinity flag is set with other bits";
+        case bls::G1_X_TOO_LARGE: return "a coordinate of x is not below p";
+        case bls::G1_NOT_ON_CURVE: return "x has no y on y^2 = x^3 + 4 (1 + u)";
+        case KZG_G2_INFINITY: return "it is the point at infinity";
+        default: return "the point is outside the order-r subgroup";
+    }
+}
+
+extern "C" int zkw_kzg_verifier_create(zkw_ctx* ctx, const uint8_t* tau_g2, zkw_kzg_verifier** out) {
+    if (!ctx || !out || !tau_g2) return fail(ZKW_ERR_INVALID, "zkw_kzg_verifier_create: null argument");
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_kzg_verifier_create: the context belongs to a batch of blocks");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    const uint8_t* d_in = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_points", tau_g2, 96, &d_in));
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_status", 2, &d_status));
+    zkw_kzg_verifier* v = new zkw_kzg_verifier();
+    v->ctx = ctx;
+    v->bytes = 2 * (size_t)bls::G2_LINES * sizeof(bls::G2Line);
+    auto drop = [&](int rc) {
+        (void)ctx->sync_stream();  // nothing queued may still write the lines
+        if (v->lines) dev_free(v->lines);
+        delete v;
+        return rc;
+    };
+    const hipError_t e = dev_malloc(&v->lines, v->bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return drop(fail(ZKW_ERR_OOM, "zkw_kzg_verifier_create: %zu bytes of device memory: %s", v->bytes, hipGetErrorString(e)));
+    }
+    u32 status[2] = {0, 0};
+    const int rc = [&]() -> int {
+        { Prof _p(ctx, "k_kzg_g2_prepare"); ZKW_LAUNCH(ctx, k_kzg_g2_prepare, 1, 64, d_in, v->lines, d_status); }
+        return ctx->read_small(status, d_status, sizeof status);  // (synchronises: other contexts read the lines without any ordering with this stream)
+    }();
+    if (rc != ZKW_OK) return drop(rc);
+    if (status[0] != bls::G1_OK) return drop(fail(ZKW_ERR_CHECK_FAILED, "zkw_kzg_verifier_create: the generator of G2 is refused: %s", kzg_g2_reason(status[0])));
+    if (status[1] != bls::G1_OK) return drop(fail(ZKW_ERR_INVALID, "zkw_kzg_verifier_create: the point is refused: %s", kzg_g2_reason(status[1])));
+    ctx_retain(ctx);
+    *out = v;
+    return ZKW_OK;
+}
+
+extern "C" void zkw_kzg_verifier_free(zkw_kzg_verifier* v) {
+    if (!v) return;
+    (void)hipSetDevice(v->ctx->device);
+    (void)v->ctx->sync_stream();
+    dev_free(v->lines);
+    zkw_ctx* owner = v->ctx;
+    delete v;
+    ctx_release(owner);
+}
+extern "C" size_t zkw_kzg_verifier_bytes(const zkw_kzg_verifier* v) { return v ? v->bytes : 0; }
+
+// the two kernels over n >= 1 claims; d_verdicts: n bytes on the device
+static int kzg_verify_device(const zkw_kzg_verifier* v, zkw_ctx* ctx, const KzgClaims& claims, size_t n, uint8_t* d_verdicts) {
+    bls::G1Aff* d_pts = nullptr;
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_verify_points", 2 * n, &d_pts));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_verify_status", n, &d_status));
+    { Prof _p(ctx, "k_kzg_verify_points"); ZKW_LAUNCH(ctx, k_kzg_verify_points, blocks_for(n, 64), 64, claims, (u32)n, d_pts, d_status); }
+    { Prof _p(ctx, "k_kzg_verify_pairing"); ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v->lines, (u32)n, d_verdicts); }
+    return ZKW_OK;
+}
+
+static int kzg_verify_check_call(const char* who, const zkw_kzg_verifier* v, zkw_ctx* ctx, size_t n_claims) {
+    if (ctx->device != v->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the verifier lives on device %d, the context on device %d", who, v->ctx->device, ctx->device);
+    if (n_claims > (1u << 24)) return fail(ZKW_ERR_INVALID, "%s: at most %u claims per call, not %zu", who, 1u << 24, n_claims);
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_verify(const zkw_kzg_verifier* v, zkw_ctx* ctx, const uint8_t* commitments, const uint8_t* points, const uint8_t* values,
+                              const uint8_t* proofs, size_t n, uint8_t* verdicts) {
+    if (!v || !ctx || (n && (!commitments || !points || !values || !proofs || !verdicts))) return fail(ZKW_ERR_INVALID, "zkw_kzg_verify: null argument");
+    ZKW_TRY(kzg_verify_check_call("zkw_kzg_verify", v, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    KzgClaims cl{nullptr, nullptr, nullptr, nullptr, 0};
+    ZKW_TRY(ctx->in("kzg_in_commitments", commitments, n * 48, &cl.commitments));
+    ZKW_TRY(ctx->in("kzg_in_points", points, n * 32, &cl.points));
+    ZKW_TRY(ctx->in("kzg_in_values", values, n * 32, &cl.values));
+    ZKW_TRY(ctx->in("kzg_in_proofs", proofs, n * 48, &cl.proofs));
+    uint8_t* d_verdicts = nullptr;
+    ZKW_TRY(ctx->out("kzg_verdicts", verdicts, n, &d_verdicts));
+    ZKW_TRY(kzg_verify_device(v, ctx, cl, n, d_verdicts));
+    ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, n));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_eip4844_verify(const zkw_kzg_verifier* v, zkw_ctx* ctx, const zkw_eip4844_record* records, const zkw_eip4844_proof_record* proofs,
+                                  size_t n, uint8_t* verdicts) {
+    if (!v || !ctx || (n && (!records || !proofs || !verdicts))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_verify: null argument");
+    ZKW_TRY(kzg_verify_check_call("zkw_eip4844_verify", v, ctx, 2 * n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const zkw_eip4844_record* d_rec = nullptr;
+    const zkw_eip4844_proof_record* d_prf = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_records", records, n, &d_rec));
+    ZKW_TRY(ctx->in("kzg_in_proof_records", proofs, n, &d_prf));
+    uint8_t* d_verdicts = nullptr;
+    ZKW_TRY(ctx->out("kzg_verdicts", verdicts, 2 * n, &d_verdicts));
+    const KzgClaims cl{reinterpret_cast<const uint8_t*>(d_rec), nullptr, nullptr, reinterpret_cast<const uint8_t*>(d_prf), 1};
+    ZKW_TRY(kzg_verify_device(v, ctx, cl, 2 * n, d_verdicts));
+    ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, 2 * n));
     return ctx->sync_if_host();
 }

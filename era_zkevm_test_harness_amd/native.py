@@ -187,6 +187,11 @@ SYMBOLS = [
     ("zkw_eip4844_witness", _int, [_vp, _vp, _vp, _sz, _vp]),
     ("zkw_kzg_open", _int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     ("zkw_eip4844_prove", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("zkw_kzg_verifier_create", _int, [_vp, _vp, C.POINTER(_vp)]),
+    ("zkw_kzg_verifier_free", None, [_vp]),
+    ("zkw_kzg_verifier_bytes", _sz, [_vp]),
+    ("zkw_kzg_verify", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zkw_eip4844_verify", _int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -945,6 +950,84 @@ class KzgSettings:
     def free(self):
         if self.handle:
             load().zkw_kzg_settings_free(self.handle)
+            self.handle = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+KZG_VERDICT_FAILS, KZG_VERDICT_HOLDS, KZG_VERDICT_BAD_COMMITMENT, KZG_VERDICT_BAD_PROOF, KZG_VERDICT_BAD_SCALAR = range(5)
+
+
+class KzgVerifier:
+    """zkw_kzg_verifier: verify_kzg_proof (kzg/src/lib.rs:259-282) on the device, the pairing check
+    e(C - [y] G1 + [z] proof, -G2) e(proof, [tau] G2) = 1. `tau_g2` is the setup's [tau] G2 as 96 compressed bytes; it is checked on the
+    device (a bad one raises ZkwError(ERR_INVALID) with the reason) and prepared once as the line functions of the Miller loop. Immutable
+    afterwards: `verify` and `eip4844_verify` may run on any context of the same device (`ctx=`), several at once. A verifier reports, it
+    does not refuse: malformed data is a verdict code (KZG_VERDICT_*), never an exception. Arrays are numpy uint8 on a context in host
+    pointer mode, torch uint8 tensors on the context's device in device pointer mode (verdicts then come back as a tensor, and the call
+    only enqueues)."""
+
+    def __init__(self, ctx, tau_g2):
+        self.ctx = ctx
+        self.handle = C.c_void_p(None)
+        ptr, n, _keep = KzgSettings._bytes(ctx, tau_g2, 96)
+        assert n == 1
+        _check(load().zkw_kzg_verifier_create(ctx.handle, ptr, C.byref(self.handle)))
+
+    @property
+    def nbytes(self) -> int:
+        """device memory held by the prepared lines"""
+        return load().zkw_kzg_verifier_bytes(self.handle)
+
+    def verify(self, commitments, points, values, proofs, ctx=None):
+        """zkw_kzg_verify: `commitments` and `proofs` = [n, 48] bytes, `points` and `values` = [n, 32] bytes (little-endian, as
+        `KzgSettings.open` takes and returns them); returns [n] verdict bytes."""
+        ctx = ctx or self.ctx
+        cptr, n, _kc = KzgSettings._bytes(ctx, commitments, 48)
+        zptr, nz, _kz = KzgSettings._bytes(ctx, points, 32)
+        yptr, ny, _ky = KzgSettings._bytes(ctx, values, 32)
+        pptr, np_, _kp = KzgSettings._bytes(ctx, proofs, 48)
+        assert n == nz == ny == np_
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty((n,), dtype=torch.uint8, device=_kc.device)
+            _check(load().zkw_kzg_verify(self.handle, ctx.handle, cptr, zptr, yptr, pptr, n, C.c_void_p(out.data_ptr() if n else None)))
+            return out
+        out = np.zeros(n, np.uint8)
+        _check(load().zkw_kzg_verify(self.handle, ctx.handle, cptr, zptr, yptr, pptr, n, _np_ptr(out) if n else None))
+        return out
+
+    def eip4844_verify(self, records, proof_records, ctx=None):
+        """zkw_eip4844_verify: `records` = what `KzgSettings.eip4844_witness` returned for n blobs, `proof_records` = what
+        `eip4844_prove` returned for them; returns [n, 2] verdict bytes: the opening proof, the blob proof."""
+        ctx = ctx or self.ctx
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            rec, prf = records.contiguous(), proof_records.contiguous()
+            assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % EIP4844_RECORD.itemsize == 0
+            n = rec.numel() // EIP4844_RECORD.itemsize
+            assert prf.is_cuda and prf.element_size() == 1 and prf.numel() == n * EIP4844_PROOF_RECORD.itemsize
+            out = torch.empty((n, 2), dtype=torch.uint8, device=rec.device)
+            _check(load().zkw_eip4844_verify(self.handle, ctx.handle, C.c_void_p(rec.data_ptr() if n else None), C.c_void_p(prf.data_ptr() if n else None), n,
+                                             C.c_void_p(out.data_ptr() if n else None)))
+            return out
+        rec = np.ascontiguousarray(records, dtype=EIP4844_RECORD).reshape(-1)
+        prf = np.ascontiguousarray(proof_records, dtype=EIP4844_PROOF_RECORD).reshape(-1)
+        n = rec.size
+        assert prf.size == n
+        out = np.zeros((n, 2), np.uint8)
+        _check(load().zkw_eip4844_verify(self.handle, ctx.handle, _np_ptr(rec) if n else None, _np_ptr(prf) if n else None, n, _np_ptr(out) if n else None))
+        return out
+
+    def free(self):
+        if self.handle:
+            load().zkw_kzg_verifier_free(self.handle)
             self.handle = C.c_void_p(None)
 
     def __del__(self):

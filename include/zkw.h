@@ -770,6 +770,31 @@ typedef struct zkw_eip4844_proof_record {      /* 160 bytes */
 int zkw_eip4844_prove(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n_blobs,
                       const zkw_eip4844_record *records /*[n]*/, zkw_eip4844_proof_record *out /*[n]*/,
                       uint8_t *blob_evaluations /*[n][131072] or NULL*/);
+/* verify_kzg_proof (kzg/src/lib.rs:259-282) on the device: the BLS12-381 pairing check
+       e(C - [y] G1 + [z] proof, -G2) e(proof, [tau] G2) = 1
+   for G1, G2 the standard generators.  A verifier is a handle of its own (no G1 table; zkw_kzg_settings is not involved):
+   zkw_kzg_verifier_create takes the setup's [tau] G2 as 96 compressed bytes (x.c1 then x.c0, big-endian, the flags of the
+   G1 form in byte 0), checks it on the device and prepares the line functions of the Miller loop for -G2 and [tau] G2
+   (26 KB of HBM).  ZKW_ERR_INVALID with the reason in zkw_last_error for a cleared compression bit, a bad infinity encoding, a
+   coordinate >= p, an x with no y on the twist, a point outside the order-r subgroup, and infinity itself.  The call ends
+   synchronised; the handle retains ctx, is immutable and may be used from any context of the same device, several at once. */
+typedef struct zkw_kzg_verifier zkw_kzg_verifier;
+int zkw_kzg_verifier_create(zkw_ctx *ctx, const uint8_t tau_g2[96], zkw_kzg_verifier **out);
+void zkw_kzg_verifier_free(zkw_kzg_verifier *v);
+size_t zkw_kzg_verifier_bytes(const zkw_kzg_verifier *v); /* HBM held */
+/* Per claim i: does proofs[i] prove p(points[i]) = values[i] for the polynomial committed to by commitments[i]?  Points and
+   values are 32 little-endian bytes (zkw_kzg_open's form).  A verifier reports, it does not refuse: bad data is a verdict,
+   never an error return.  verdicts[i]: 0 the equation fails, 1 it holds, 2 malformed commitment (not a compressed point, bad
+   infinity, x >= p, not on the curve, outside the subgroup), 3 malformed proof, 4 point or value not below r; the lowest
+   applicable code above 1 wins.  Nothing is read back: in device pointer mode the call only enqueues.  n = 0 is a no-op; at
+   most 2^24 claims per call. */
+int zkw_kzg_verify(const zkw_kzg_verifier *v, zkw_ctx *ctx, const uint8_t *commitments /*[n][48]*/, const uint8_t *points /*[n][32]*/,
+                   const uint8_t *values /*[n][32]*/, const uint8_t *proofs /*[n][48]*/, size_t n, uint8_t *verdicts /*[n]*/);
+/* The two proofs of n blobs from their records: verdicts[j][0] is opening_proof at the record's evaluation_point and
+   opening_value, verdicts[j][1] is blob_proof at blob_challenge and blob_value, both against the record's commitment; the codes
+   of zkw_kzg_verify.  The challenge and the values are taken from the records, not recomputed from the blob. */
+int zkw_eip4844_verify(const zkw_kzg_verifier *v, zkw_ctx *ctx, const zkw_eip4844_record *records /*[n]*/,
+                       const zkw_eip4844_proof_record *proofs /*[n]*/, size_t n, uint8_t *verdicts /*[n][2]*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
