@@ -6,6 +6,7 @@
 //                       (unsorted queue: src/witness/oracle.rs:894-903; sorted: W/ram_permutation.rs:61-71)
 //   k_fs_challenges     produce_fs_challenges                   src/witness/utils.rs:498-550
 //   k_gp_local/_tiles/_apply  compute_grand_product_chains      src/witness/utils.rs:554-697
+//   k_ram_gp_groups / _scan   the same at every 64th cycle of an instance only (all the RAM builder and the synthesis read of them)
 //   k_ram_sort_keys / k_gather_queries   par_sort_by            W/ram_permutation.rs:48-53
 //   k_ram_instances     per-instance FSM snapshots              W/ram_permutation.rs:239-453
 #pragma once
@@ -535,13 +536,14 @@ static __device__ __forceinline__ void k_gather_encode(const VB& vb, const zkw_m
 struct RamBlock {
     const zkw_mem_query* sorted_q;  // the BATCH's queries; sorted item i of this block is sorted_q[sorted_perm[i]]
     const u32* sorted_perm;         // [n]
+    const zkw_mem_query* unsorted_q;  // [n] the block's queries in their original order
+    const u64* chal;                // [2][9] the block's challenges
     const u64* u_marks;             // [n_instances][12] unsorted queue tail after the last item of each instance
     const u64* s_marks;             // [n_instances][12] the same for the sorted queue
-    const u64* lhs_z;               // [2][n]
-    const u64* rhs_z;               // [2][n]
     zkw_ram_instance* instances;    // [ceil(n/capacity)]
-    u32* nondet_prefix;             // [n_instances] scratch: nondeterministic writes per chunk
+    u32* nondet_prefix;             // [n_instances] nondeterministic writes per instance (the FSM's count)
     u64* gp_ckpt;                   // [n_instances][ceil(capacity/64)][4] grand-product checkpoints of the block's instances
+    u64* gp_total;                  // [4] the four grand products over the whole block
     u32* nd_prefix;                 // [n_instances][ceil(capacity/256)] the circuit's nondeterministic writes of the instance before each tile of 256 cycles
     u64 n;
     u32 capacity;
@@ -552,43 +554,161 @@ __device__ __forceinline__ void copy12(u64* dst, const u64* src) {
     for (int k = 0; k < 12; k++) dst[k] = src[k];
 }
 
-// pass 1: count nondeterministic writes per chunk (rw && ts == 0 && page == BOOTLOADER_HEAP_PAGE). The walk is tile by tile (256
-// cycles of the instance at a time), so it leaves the synthesis its row-C counter on the way: nd_prefix[inst][t] = the writes that the
-// CIRCUIT counts (the same flag and not a pointer: nd_flag of ram_circuit_kernels.cuh) in the instance's cycles before tile t. Every tile
-// of the capacity gets its entry, also those past a short last instance.
-static __device__ __forceinline__ void k_ram_count_nondet(const VB& vb, const RamBlock* __restrict__ blocks) {
+// pass 1 (group pass): one workgroup per tile of 256 cycles of one instance, a wave per group of 64 cycles. A lane reads the unsorted
+// and the sorted query of its cycle (the sorted one through the permutation: the pass's only gather) and forms the cycle's four
+// grand-product factors as k_gp_local does for W = 8 (lhs r0, lhs r1, rhs r0, rhs r1; 1 in a cycle that pops nothing); the wave
+// multiplies them up — a reduction, six shuffle steps — into gp_ckpt[inst][group], where pass 2 turns the products into the running
+// ones. Nothing keeps a whole chain: the instance records and the synthesis read the chains at group starts only. Groups and tiles are
+// the INSTANCE's (first_item + 64 g is no multiple of 64 in a continuation), not the block's.
+// From the sorted query the lane also has the two nondeterministic-write flags (rw && ts == 0 && page == BOOTLOADER_HEAP_PAGE: the
+// FSM's; the same and not a pointer: the circuit's, nd_flag of ram_circuit_kernels.cuh). The tile's two counts (<= 256 each) leave
+// packed in nd_prefix[inst][tile] = FSM count | circuit count << 16, for pass 2. Every tile of the capacity gets its entry, also
+// those past a short last instance.
+static __device__ __forceinline__ void k_ram_gp_groups(const VB& vb, const RamBlock* __restrict__ blocks) {
     const RamBlock b = blocks[vb.y];
     const u64 n_inst = (b.n + b.capacity - 1) / b.capacity;
+    const u32 n_tiles = (b.capacity + 255) / 256, groups = (b.capacity + 63) / 64;
+    const u64 inst = vb.x / n_tiles;
+    const u32 t = vb.x % n_tiles;
+    if (inst >= n_inst) return;
+    __shared__ u32 sh[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 lo = inst * b.capacity, hi = lo + b.capacity < b.n ? lo + b.capacity : b.n;
+    const u64 i = lo + 256 * (u64)t + threadIdx.x;
+    const bool live = i < hi;
+    zkw_mem_query qs;
+    memset(&qs, 0, sizeof qs);
+    u64 eu[8], es[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) eu[k] = 0;
+    if (live) {
+        const RawQuery ru = load_raw_query(b.unsorted_q + i), rs = load_raw_query(b.sorted_q + b.sorted_perm[i]);
+        encode_raw_query(ru, eu);
+        uint4* d = reinterpret_cast<uint4*>(&qs);
+        d[0] = rs.a; d[1] = rs.b; d[2] = rs.c;
+    }
+    encode_mem_query(qs, es);
+    const bool f = live && qs.rw_flag && qs.timestamp == 0 && qs.page == ZKW_BOOTLOADER_HEAP_PAGE, fc = f && !qs.value_is_pointer;
+    u64 p[4];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const u64* ch = b.chal + 9 * r;
+        u64 lc = ch[8], rc = ch[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            lc = gl::add(lc, gl::mul(eu[k], ch[k]));
+            rc = gl::add(rc, gl::mul(es[k], ch[k]));
+            __builtin_amdgcn_sched_barrier(0);  // two products in flight: their carries live in SGPR pairs (as row A of the synthesis)
+        }
+        p[r] = live ? lc : 1;
+        p[2 + r] = live ? rc : 1;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+            const u64 o0 = __shfl_xor(p[k], d, 64), o1 = __shfl_xor(p[k + 1], d, 64);
+            p[k] = gl::mul(p[k], o0);
+            p[k + 1] = gl::mul(p[k + 1], o1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const u32 g = 4 * t + wave;
+    if (lane == 0 && g < groups) {
+        u64* out = b.gp_ckpt + 4 * (inst * groups + g);
+#pragma unroll
+        for (int k = 0; k < 4; k++) out[k] = gl::canon(p[k]);
+    }
+    const u32 c = (u32)__popcll(__ballot(f)) | (u32)__popcll(__ballot(fc)) << 16;
+    if (lane == 0) sh[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) b.nd_prefix[inst * n_tiles + t] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// pass 2 (scan pass): one workgroup per block.
+//   * The group products of the block's instances, in order, become in place the exclusive running products starting from 1: the four
+//     accumulators entering each group's first cycle, which is what row A of the synthesis starts its in-wave scan from
+//     (ram_circuit_kernels.cuh). Group 0 of instance k holds the FSM input accumulators of instance k; the block's total stays in
+//     gp_total for the last instance's output. Field products are exact, so the canonical values are those of the chains whatever the
+//     order of association. A workgroup-wide scan over chunks of 256 groups: a block of many instances has tens of thousands of groups.
+//   * Then a wave per instance: the packed tile counts become nd_prefix (exclusive prefix of the circuit's count inside the instance)
+//     and nondet_prefix[inst] (the FSM's count of the instance). The packed word is scanned as it is: 64 tiles hold at most 16 384
+//     writes, so the low half cannot carry into the high one within a chunk.
+static __device__ __forceinline__ void k_ram_gp_scan(const VB& vb, const RamBlock* __restrict__ blocks) {
+    const RamBlock b = blocks[vb.y];
+    const u64 n_inst = (b.n + b.capacity - 1) / b.capacity, groups = (b.capacity + 63) / 64, total = n_inst * groups;
     const u32 n_tiles = (b.capacity + 255) / 256;
-    __shared__ u32 sh[2][2][4];  // [tile parity][FSM count, circuit count][wave]: one barrier per tile
-    for (u64 inst = vb.x; inst < n_inst; inst += vb.nx) {
-        const u64 lo = inst * b.capacity, hi = lo + b.capacity < b.n ? lo + b.capacity : b.n;
-        u32 cnt = 0, before = 0;  // (thread 0's running sums)
-        for (u32 t = 0; t < n_tiles; t++) {
-            const u64 i = lo + 256 * (u64)t + threadIdx.x;
-            bool f = false, fc = false;
-            if (i < hi) {
-                const zkw_mem_query* q = b.sorted_q + b.sorted_perm[i];
-                f = q->rw_flag && q->timestamp == 0 && q->page == ZKW_BOOTLOADER_HEAP_PAGE;
-                fc = f && !q->value_is_pointer;
-            }
-            const u32 c = __popcll(__ballot(f)), cc = __popcll(__ballot(fc));
-            if ((threadIdx.x & 63) == 0) { sh[t & 1][0][threadIdx.x >> 6] = c; sh[t & 1][1][threadIdx.x >> 6] = cc; }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const u32* s0 = sh[t & 1][0];
-                const u32* s1 = sh[t & 1][1];
-                b.nd_prefix[inst * n_tiles + t] = before;
-                cnt += s0[0] + s0[1] + s0[2] + s0[3];
-                before += s1[0] + s1[1] + s1[2] + s1[3];
+    __shared__ u64 sh_w[4][4];  // [wave][product]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 carry[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) carry[k] = 1;
+    for (u64 base = 0; base < total; base += 256) {
+        const u64 j = base + threadIdx.x;
+        const bool ok = j < total;
+        u64* at = b.gp_ckpt + 4 * j;
+        u64 s[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) s[k] = ok ? at[k] : 1;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {
+                const u64 o0 = __shfl_up(s[k], d, 64), o1 = __shfl_up(s[k + 1], d, 64);
+                if (lane >= d) { s[k] = gl::mul(s[k], o0); s[k + 1] = gl::mul(s[k + 1], o1); }
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (threadIdx.x == 0) b.nondet_prefix[inst] = cnt;
+        if (lane == 63) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) sh_w[wave][k] = s[k];
+        }
         __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+            const u64 e0 = __shfl_up(s[k], 1, 64), e1 = __shfl_up(s[k + 1], 1, 64);
+            u64 pre0 = carry[k], pre1 = carry[k + 1], tot0 = carry[k], tot1 = carry[k + 1];
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                tot0 = gl::mul(tot0, sh_w[w][k]);
+                tot1 = gl::mul(tot1, sh_w[w][k + 1]);
+                if (w + 1 == wave) { pre0 = tot0; pre1 = tot1; }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            carry[k] = tot0;
+            carry[k + 1] = tot1;
+            const u64 x0 = lane == 0 ? pre0 : gl::mul(pre0, e0), x1 = lane == 0 ? pre1 : gl::mul(pre1, e1);
+            if (ok) { at[k] = gl::canon(x0); at[k + 1] = gl::canon(x1); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) b.gp_total[k] = gl::canon(carry[k]);
+    }
+    for (u64 inst = wave; inst < n_inst; inst += 4) {
+        u32* tiles = b.nd_prefix + inst * n_tiles;
+        u32 fsm = 0, before = 0;
+        for (u32 t0 = 0; t0 < n_tiles; t0 += 64) {
+            const u32 t = t0 + lane;
+            const u32 v = t < n_tiles ? tiles[t] : 0;
+            u32 incl = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const u32 y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (t < n_tiles) tiles[t] = before + ((incl - v) >> 16);
+            const u32 sum = __shfl(incl, 63, 64);
+            fsm += sum & 0xFFFFu;
+            before += sum >> 16;
+        }
+        if (lane == 0) b.nondet_prefix[inst] = fsm;
     }
 }
 
-// pass 2: one lane per instance
+// pass 3: one lane per instance
 static __device__ __forceinline__ void k_ram_instances(const VB& vb, const RamBlock* __restrict__ blocks) {
     const RamBlock b = blocks[vb.y];
     const u64 n_inst = (b.n + b.capacity - 1) / b.capacity;
@@ -613,9 +733,11 @@ static __device__ __forceinline__ void k_ram_instances(const VB& vb, const RamBl
     for (u64 k = 0; k < idx; k++) nondet_before += b.nondet_prefix[k];
 
     // FSM output of chunk j (without the padding reset) is a function of item `end_j - 1`
-    auto fill = [&](zkw_ram_fsm& f, u64 end /* items consumed so far, > 0 */, u32 nondet) {
+    // acc: the four grand products over the items consumed so far = the checkpoint entering the next instance's group 0 (k_ram_gp_scan)
+    const u64 groups = (b.capacity + 63) / 64;
+    auto fill = [&](zkw_ram_fsm& f, u64 end /* items consumed so far, > 0 */, u32 nondet, const u64* acc) {
         const u64 l = end - 1;
-        for (int r = 0; r < 2; r++) { f.lhs_accumulator[r] = b.lhs_z[r * n + l]; f.rhs_accumulator[r] = b.rhs_z[r * n + l]; }
+        for (int r = 0; r < 2; r++) { f.lhs_accumulator[r] = acc[r]; f.rhs_accumulator[r] = acc[2 + r]; }
         copy12(f.current_unsorted_queue_state.head, b.u_marks + 12 * (l / b.capacity));
         copy12(f.current_unsorted_queue_state.tail, u_final);
         f.current_unsorted_queue_state.length = (u32)(n - end);
@@ -632,35 +754,15 @@ static __device__ __forceinline__ void k_ram_instances(const VB& vb, const RamBl
     if (idx == 0) {
         for (int r = 0; r < 2; r++) { w.hidden_fsm_input.lhs_accumulator[r] = 1; w.hidden_fsm_input.rhs_accumulator[r] = 1; }
     } else {
-        fill(w.hidden_fsm_input, lo, nondet_before);
+        fill(w.hidden_fsm_input, lo, nondet_before, b.gp_ckpt + 4 * groups * idx);
     }
-    fill(w.hidden_fsm_output, hi, nondet_before + b.nondet_prefix[idx]);
+    fill(w.hidden_fsm_output, hi, nondet_before + b.nondet_prefix[idx], idx + 1 < n_inst ? b.gp_ckpt + 4 * groups * (idx + 1) : b.gp_total);
     if ((hi - lo) % b.capacity != 0) {  // padding reset, W/ram_permutation.rs:414-432
         zkw_ram_fsm& f = w.hidden_fsm_output;
         for (int k = 0; k < 3; k++) f.previous_sorting_key[k] = 0;
         for (int k = 0; k < 2; k++) f.previous_full_key[k] = 0;
         for (int k = 0; k < 8; k++) f.previous_value[k] = 0;
         f.previous_is_ptr = 0;
-    }
-}
-
-// pass 3: grand-product checkpoints, one lane per (instance, group of 64 cycles): the four accumulators (lhs r0, lhs r1, rhs r0, rhs r1)
-// entering the group's first cycle = the FSM input for group 0, else the chain value at the instance's last item popped before that
-// cycle. Row A of the synthesis finishes the scan inside its wave from these (ram_circuit_kernels.cuh), so that no synthesis call
-// needs the chains. first_item is no multiple of 64 for an instance's continuations: the groups are the INSTANCE's, not the chain tiles'.
-static __device__ __forceinline__ void k_ram_gp_ckpt(const VB& vb, const RamBlock* __restrict__ blocks) {
-    const RamBlock b = blocks[vb.y];
-    const u64 n_inst = (b.n + b.capacity - 1) / b.capacity, groups = (b.capacity + 63) / 64;
-    const u64 j = (u64)vb.x * blockDim.x + threadIdx.x;
-    if (j >= n_inst * groups) return;
-    const u64 idx = j / groups, g = j % groups;
-    const zkw_ram_instance& in = b.instances[idx];
-    const u64 first = in.first_item, m = in.num_items;
-    u64* out = b.gp_ckpt + 4 * j;
-    for (int r = 0; r < 2; r++) {
-        const u64 at = (u64)r * b.n + first + (64 * g - 1 < m ? 64 * g - 1 : m - 1);  // (unused for g = 0)
-        out[r] = g == 0 ? in.hidden_fsm_input.lhs_accumulator[r] : b.lhs_z[at];
-        out[2 + r] = g == 0 ? in.hidden_fsm_input.rhs_accumulator[r] : b.rhs_z[at];
     }
 }
 

@@ -1069,20 +1069,19 @@ struct zkw_ram_witness {
     u64 *unsorted_caps = nullptr, *sorted_caps = nullptr, *unsorted_marks = nullptr, *sorted_marks = nullptr;
     u64 *unsorted_tails = nullptr, *sorted_tails = nullptr;
     bool tails_valid = false;
-    // grand-product chains: the builder only needs them at instance boundaries, so they live in a window (zbuf_*, zcap items)
-    // that it computes per group of blocks (16 B per query and side instead of 32 B resident); the [total] arrays of the C ABI
-    // are computed on first access. What the synthesis needs of them stays behind as gp_ckpt: the four accumulators entering
-    // every group of 64 cycles of every instance ([n_instances][ceil(capacity/64)][4], written group by group while the chains
-    // are in the window); row A scans the 64 cycles in between itself
+    // grand-product chains: the builder never materialises them. It multiplies the factors of every group of 64 cycles of every
+    // instance up and scans those products (k_ram_gp_groups, k_ram_gp_scan): gp_ckpt = the four accumulators entering every group
+    // ([n_instances][ceil(capacity/64)][4]), gp_total = the four products over each whole block ([n_blocks][4]). The instance records
+    // take their accumulators from them, row A of the synthesis scans the 64 cycles in between itself; the [total] arrays of the C
+    // ABI are computed on first access
     u64 *challenges = nullptr, *lhs_z = nullptr, *rhs_z = nullptr;
     bool z_valid = false;
-    u64 *zbuf_l = nullptr, *zbuf_r = nullptr;
-    u64* gp_ckpt = nullptr;
+    u64 *gp_ckpt = nullptr, *gp_total = nullptr;
     // the circuit's nondeterministic writes of an instance before each of its tiles of 256 cycles ([n_instances][ceil(capacity/256)],
     // left by the builder's counting pass): row C of the synthesis adds its in-tile count, no synthesis call counts again
     u32* nd_prefix = nullptr;
     zkw_mem_query* sq_win = nullptr;  // the sorted queries of the blocks being synthesized, gathered per synthesis call
-    size_t zcap = 0, sqcap = 0;       // capacity of the chain windows / of the sorted window, in queue items
+    size_t sqcap = 0;                 // capacity of the sorted window, in queue items
     zkw_ram_instance* instances = nullptr;
     u32* nondet_counts = nullptr;
     u64 *compact_forms = nullptr, *public_inputs = nullptr;  // [n_instances][18], [n_instances][4]
@@ -1090,7 +1089,7 @@ struct zkw_ram_witness {
     void release() {
         void* ptrs[] = {sorted_q, perm, owned_q, unsorted_enc, sorted_enc, unsorted_caps, sorted_caps, unsorted_marks, sorted_marks,
                         unsorted_tails, sorted_tails, challenges,
-                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, zbuf_l, zbuf_r, sq_win, gp_ckpt, nd_prefix};
+                        lhs_z,    rhs_z,        instances,  nondet_counts, compact_forms, public_inputs, sq_win, gp_ckpt, gp_total, nd_prefix};
         for (void* p : ptrs)
             if (p) dev_free(p);
         sorted_q = nullptr;
@@ -1103,11 +1102,10 @@ struct zkw_ram_witness {
         unsorted_caps = sorted_caps = unsorted_marks = sorted_marks = nullptr;
         tails_valid = false;
         z_valid = false;
-        zbuf_l = zbuf_r = nullptr;
-        gp_ckpt = nullptr;
+        gp_ckpt = gp_total = nullptr;
         nd_prefix = nullptr;
         sq_win = nullptr;
-        zcap = sqcap = 0;
+        sqcap = 0;
         instances = nullptr;
         nondet_counts = nullptr;
         compact_forms = public_inputs = nullptr;
@@ -1125,34 +1123,22 @@ static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
     HIP_TRY(dev_malloc((void**)&w->unsorted_marks, (ni + 1) * 12 * sizeof(u64)));
     HIP_TRY(dev_malloc((void**)&w->sorted_marks, (ni + 1) * 12 * sizeof(u64)));
     HIP_TRY(dev_malloc((void**)&w->challenges, (n_blocks + 1) * 18 * sizeof(u64)));
-    {   // window of the grand-product chains: whole blocks, about 1 GB per side, at least the largest block
+    {   // window of the sorted queries: whole blocks, 192 MB, at least the largest block
         size_t max_block = 0;
         for (size_t b = 0; b + 1 < w->offsets.size(); b++) max_block = std::max(max_block, (size_t)(w->offsets[b + 1] - w->offsets[b]));
-        size_t window = (size_t)1 << 26, sq_window = (size_t)1 << 22;  // 2 x 1 GB of chains (few builder groups), 192 MB of sorted queries
-        if (const char* e = getenv("ZKW_Z_WINDOW_ITEMS")) window = sq_window = (size_t)strtoull(e, nullptr, 10);  // tests: force small groups
-        w->zcap = std::max(max_block, std::min(t, window));
+        size_t sq_window = (size_t)1 << 22;
+        if (const char* e = getenv("ZKW_Z_WINDOW_ITEMS")) sq_window = (size_t)strtoull(e, nullptr, 10);  // tests: force small groups
         w->sqcap = std::max(max_block, std::min(t, sq_window));
-        HIP_TRY(dev_malloc((void**)&w->zbuf_l, (w->zcap + 1) * 2 * sizeof(u64)));
-        HIP_TRY(dev_malloc((void**)&w->zbuf_r, (w->zcap + 1) * 2 * sizeof(u64)));
         HIP_TRY(dev_malloc((void**)&w->sq_win, (w->sqcap + 1) * sizeof(zkw_mem_query)));
     }
     HIP_TRY(dev_malloc((void**)&w->gp_ckpt, (ni * ram_gp_groups(w->capacity) + 1) * 4 * sizeof(u64)));
+    HIP_TRY(dev_malloc((void**)&w->gp_total, (n_blocks + 1) * 4 * sizeof(u64)));
     HIP_TRY(dev_malloc((void**)&w->nd_prefix, (ni * ram_nd_tiles(w->capacity) + 1) * sizeof(u32)));
     HIP_TRY(dev_malloc((void**)&w->instances, (ni + 1) * sizeof(zkw_ram_instance)));
     HIP_TRY(dev_malloc((void**)&w->nondet_counts, (ni + 1) * sizeof(u32)));
     HIP_TRY(dev_malloc((void**)&w->compact_forms, (ni + 1) * COMPACT_FORM_LEN * sizeof(u64)));
     HIP_TRY(dev_malloc((void**)&w->public_inputs, (ni + 1) * 4 * sizeof(u64)));
     return ZKW_OK;
-}
-
-// the block a query position belongs to: largest b with offsets[b] <= i
-__device__ __forceinline__ u32 block_of_position(const u64* __restrict__ offsets, int n_blocks, size_t i) {
-    int lo = 0, hi = n_blocks;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return (u32)lo;
 }
 
 // Widths of the sort key's fields in this batch: max timestamp / page / index, so that the radix sort only walks
@@ -1176,53 +1162,44 @@ static __device__ __forceinline__ void k_ram_key_ranges(const VB& vb, const zkw_
     }
 }
 
-// (block, page, index, timestamp) packed into one word, most significant first
-static __device__ __forceinline__ void k_ram_packed_keys(const VB& vb, const zkw_mem_query* __restrict__ q, size_t n, const u64* __restrict__ offsets,
-                                  int n_blocks, unsigned bits_p, unsigned bits_i, unsigned bits_t,
+// (page, index, timestamp) packed into one word, most significant first
+static __device__ __forceinline__ void k_ram_packed_keys(const VB& vb, const zkw_mem_query* __restrict__ q, size_t n, unsigned bits_i, unsigned bits_t,
                                   u64* __restrict__ key, u32* __restrict__ iota) {
     size_t i = (size_t)vb.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    u64 k = n_blocks > 1 ? block_of_position(offsets, n_blocks, i) : 0;
-    k = (k << bits_p) | q[i].page;
+    u64 k = q[i].page;
     k = (k << bits_i) | q[i].index;
     k = (k << bits_t) | q[i].timestamp;
     key[i] = k;
     iota[i] = (u32)i;
 }
 
-// (block, page, index) of the items in their current order `perm`, packed into one word
-static __device__ __forceinline__ void k_ram_packed_cells(const VB& vb, const u64* __restrict__ cell, const u32* __restrict__ perm, size_t n,
-                                   const u64* __restrict__ offsets, int n_blocks, unsigned bits_p, unsigned bits_i,
+// (page, index) of the items in their current order `perm`, packed into one word
+static __device__ __forceinline__ void k_ram_packed_cells(const VB& vb, const u64* __restrict__ cell, const u32* __restrict__ perm, size_t n, unsigned bits_i,
                                    u64* __restrict__ key) {
     size_t i = (size_t)vb.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const u32 src = perm[i];
-    const u64 c = cell[src];
-    u64 k = n_blocks > 1 ? block_of_position(offsets, n_blocks, src) : 0;
-    k = (k << bits_p) | (c >> 32);
-    k = (k << bits_i) | (c & 0xFFFFFFFFu);
-    key[i] = k;
-}
-
-static __device__ __forceinline__ void k_block_ids(const VB& vb, const u64* __restrict__ offsets, int n_blocks, size_t n, u32* __restrict__ ids) {
-    size_t i = (size_t)vb.x * blockDim.x + threadIdx.x;
-    if (i < n) ids[i] = block_of_position(offsets, n_blocks, i);
+    const u64 c = cell[perm[i]];
+    key[i] = ((c >> 32) << bits_i) | (c & 0xFFFFFFFFu);
 }
 
 static unsigned bits_in_use(u32 x) { return x ? 32u - (unsigned)__builtin_clz(x) : 0u; }
 
-// The sorting permutation for all blocks at once: order (block, page, index, timestamp), W/ram_permutation.rs:48-53
-// per block. The key is as wide as this batch makes it, and the sort takes the cheapest of three routes:
-//   one   - all four fields fit 64 bits: one radix sort of the packed word over the bits in use;
-//   two   - they do not, but (block, page, index) do: timestamps first, then the packed cell word (stable);
-//   three - full-width pages and indices in a multi-block batch: timestamp, cell, block id, each stable.
+// The sorting permutation for all blocks at once: order (page, index, timestamp) inside every block, W/ram_permutation.rs:48-53.
+// The batch arrives block by block, and every sort is segmented by the blocks (radix_sort.cuh): no pair leaves its block, so no
+// key carries a block id and no lane looks its block up. The key is as wide as this batch makes it, and the sort takes the
+// cheapest of three routes:
+//   one   - the three fields fit 64 bits: one radix sort of the packed word over the bits in use;
+//   two   - they do not: timestamps first, then (page, index) packed into one word narrower than 64 bits (stable);
+//   three - full-width pages and indices: timestamps first, then the 64-bit cell word as it is.
+// One block is one segment through the same code.
 // `work_a` / `work_b`: two device areas of 32 bytes per query that nothing else uses until the sort is over (the
 // builder passes the capacity-word arrays, which the chains fill afterwards); the radix temporary falls back to
 // the context scratch when it does not fit (tiny batches: its histograms dominate).
 static int ram_sort(zkw_ctx* ctx, const zkw_mem_query* d_q, size_t total, const std::vector<uint64_t>& offsets,
                     void* work_a, void* work_b, u32** perm_out) {
     const size_t n_blocks = offsets.size() - 1;
-    size_t tmp_bytes = radix_temp_bytes(total);
+    size_t tmp_bytes = radix_temp_bytes(total, n_blocks);
     // work_a: ts | k32 | v0 | v1 (4 x u32) | cell | k64a (2 x u64) = 32 bytes per query
     u32* ts = static_cast<u32*>(work_a);
     u32 *k32 = ts + total, *v0 = k32 + total, *v1 = v0 + total;
@@ -1247,17 +1224,16 @@ static int ram_sort(zkw_ctx* ctx, const zkw_mem_query* d_q, size_t total, const 
     u32 maxima[4];
     ZKW_TRY(ctx->read_small(maxima, d_max, 16));
     const unsigned bits_t = bits_in_use(maxima[0]), bits_p = bits_in_use(maxima[1]), bits_i = bits_in_use(maxima[2]);
-    unsigned bits_b = 0;
-    while ((1ull << bits_b) < n_blocks) bits_b++;
-    u64* d_off = nullptr;
-    if (n_blocks > 1) ZKW_TRY(ctx->upload("sort_off", offsets, &d_off));
+    std::vector<RsSeg> seg_table;
+    const u32 n_tiles = rs_seg_table(offsets.data(), n_blocks, seg_table), n_segs = (u32)n_blocks;
+    RsSeg* d_segs = nullptr;
+    ZKW_TRY(ctx->upload("sort_segs", seg_table, &d_segs));
 
-    if (bits_b + bits_p + bits_i + bits_t <= 64) {
-        const unsigned bits = bits_b + bits_p + bits_i + bits_t;
-        { Prof _p(ctx, "k_ram_packed_keys");
-          ZKW_LAUNCH(ctx, k_ram_packed_keys, grid, 256, d_q, total, d_off, (int)n_blocks, bits_p, bits_i, bits_t, k64a, v0); }
+    if (bits_p + bits_i + bits_t <= 64) {
+        const unsigned bits = bits_p + bits_i + bits_t;
+        { Prof _p(ctx, "k_ram_packed_keys"); ZKW_LAUNCH(ctx, k_ram_packed_keys, grid, 256, d_q, total, bits_i, bits_t, k64a, v0); }
         ZKW_TRY(launch_check("k_ram_packed_keys"));
-        { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v0, v1, total, bits ? bits : 1)); }
+        { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v0, v1, total, d_segs, n_segs, n_tiles, bits)); }
         *perm_out = v1;
         return ZKW_OK;
     }
@@ -1265,29 +1241,18 @@ static int ram_sort(zkw_ctx* ctx, const zkw_mem_query* d_q, size_t total, const 
     { Prof _p(ctx, "k_ram_sort_keys"); ZKW_LAUNCH(ctx, k_ram_sort_keys, grid, 256, d_q, total, ts, cell, v0, (const u64*)nullptr, 0); }
     ZKW_TRY(launch_check("k_ram_sort_keys"));
     // pass 1: timestamp
-    { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u32>(ctx, tmp, tmp_bytes, ts, k32, v0, v1, total, bits_t ? bits_t : 1)); }
-    if (bits_b + bits_p + bits_i <= 64) {
-        // pass 2: (block, page, index) of the ts-sorted items
-        const unsigned bits = bits_b + bits_p + bits_i;
-        { Prof _p(ctx, "k_ram_packed_cells");
-          ZKW_LAUNCH(ctx, k_ram_packed_cells, grid, 256, cell, v1, total, d_off, (int)n_blocks, bits_p, bits_i, k64a); }
+    { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u32>(ctx, tmp, tmp_bytes, ts, k32, v0, v1, total, d_segs, n_segs, n_tiles, bits_t)); }
+    // pass 2: the cell of the ts-sorted items, packed where that saves a digit
+    const unsigned bits = bits_p + bits_i;
+    if (bits < 64) {
+        { Prof _p(ctx, "k_ram_packed_cells"); ZKW_LAUNCH(ctx, k_ram_packed_cells, grid, 256, cell, v1, total, bits_i, k64a); }
         ZKW_TRY(launch_check("k_ram_packed_cells"));
-        { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v1, v0, total, bits ? bits : 1)); }
-        *perm_out = v0;
-        return ZKW_OK;
+    } else {
+        { Prof _p(ctx, "k_gather_u64_by_u32"); ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, cell, v1, total, k64a); }
+        ZKW_TRY(launch_check("k_gather_u64_by_u32"));
     }
-    // pass 2: cell of the ts-sorted items
-    { Prof _p(ctx, "k_gather_u64_by_u32"); ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, cell, v1, total, k64a); }
-    ZKW_TRY(launch_check("k_gather_u64_by_u32"));
-    { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v1, v0, total, 64)); }
-    // pass 3: block id, so that each block's items end up contiguous again (only multi-block batches get here)
-    { Prof _p(ctx, "k_block_ids"); ZKW_LAUNCH(ctx, k_block_ids, grid, 256, d_off, (int)n_blocks, total, ts); }
-    ZKW_TRY(launch_check("k_block_ids"));
-    // ts[] now holds block ids in ORIGINAL order; gather them through the current permutation
-    { Prof _p(ctx, "k_gather_u32_by_u32"); ZKW_LAUNCH(ctx, k_gather_u32_by_u32, grid, 256, ts, v0, total, k32); }
-    ZKW_TRY(launch_check("k_gather_u32_by_u32"));
-    { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u32>(ctx, tmp, tmp_bytes, k32, ts, v0, v1, total, bits_b)); }
-    *perm_out = v1;
+    { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v1, v0, total, d_segs, n_segs, n_tiles, bits)); }
+    *perm_out = v0;
     return ZKW_OK;
 }
 
@@ -1341,44 +1306,44 @@ static int ram_run(zkw_ctx* ctx, zkw_ram_witness* w, const zkw_mem_query* d_q, c
                       w->challenges + 18 * b};
     }
     ZKW_TRY(dev_fs(ctx, fs, 12, 9));
-    // K6 + a10 in groups of whole blocks that fit the chain window: both repetitions and both sides of a group in one
-    // launch set (W/ram_permutation.rs:115-138), then the per-instance records that read the chains at instance ends
+    // K6 + a10 (W/ram_permutation.rs:115-138, 239-453): the products of both repetitions and both sides per group of 64 cycles and
+    // the tile counts of nondeterministic writes in one pass over the queries, their scans per block, then the per-instance records,
+    // which take the chains' values at instance ends from the scanned checkpoints. No chain is written anywhere.
     w->z_valid = false;
-    for (size_t b0 = 0; b0 < n_blocks;) {
-        size_t b1 = b0 + 1;
-        while (b1 < n_blocks && w->offsets[b1 + 1] - w->offsets[b0] <= w->zcap) b1++;
-        ZKW_TRY(ram_gp_blocks(ctx, w, b0, b1, w->zbuf_l, w->zbuf_r));
-        const size_t base = w->offsets[b0];
+    const size_t groups = ram_gp_groups(w->capacity), nd_tiles = ram_nd_tiles(w->capacity);
+    for (size_t b0 = 0; b0 < n_blocks;) {  // (a grid's y extent is 16 bits)
+        const size_t b1 = std::min(n_blocks, b0 + 32768);
         std::vector<RamBlock> blocks(b1 - b0);
         size_t max_inst = 0;
         for (size_t b = b0; b < b1; b++) {
             const size_t lo = w->offsets[b], n = w->offsets[b + 1] - lo;
-            const size_t n_inst = w->inst_offsets[b + 1] - w->inst_offsets[b];
+            const size_t io = w->inst_offsets[b], n_inst = w->inst_offsets[b + 1] - io;
             if (n_inst > max_inst) max_inst = n_inst;
             blocks[b - b0] = RamBlock{w->unsorted_q,
                                       w->perm + lo,
-                                      w->unsorted_marks + 12 * w->inst_offsets[b],
-                                      w->sorted_marks + 12 * w->inst_offsets[b],
-                                      w->zbuf_l + 2 * (lo - base),
-                                      w->zbuf_r + 2 * (lo - base),
-                                      w->instances + w->inst_offsets[b],
-                                      w->nondet_counts + w->inst_offsets[b],
-                                      w->gp_ckpt + 4 * ram_gp_groups(w->capacity) * w->inst_offsets[b],
-                                      w->nd_prefix + ram_nd_tiles(w->capacity) * w->inst_offsets[b],
+                                      w->unsorted_q + lo,
+                                      w->challenges + 18 * b,
+                                      w->unsorted_marks + 12 * io,
+                                      w->sorted_marks + 12 * io,
+                                      w->instances + io,
+                                      w->nondet_counts + io,
+                                      w->gp_ckpt + 4 * groups * io,
+                                      w->gp_total + 4 * b,
+                                      w->nd_prefix + nd_tiles * io,
                                       n,
                                       w->capacity,
                                       n_nondet ? n_nondet[b] : 0u};
         }
         RamBlock* d_blocks = nullptr;
         ZKW_TRY(ctx->upload("ram_blocks", blocks, &d_blocks));
-        const unsigned gx = (unsigned)(max_inst < 64 ? max_inst : 64), gy = (unsigned)(b1 - b0);
-        { Prof _p(ctx, "k_ram_count_nondet"); ZKW_LAUNCH_2D(ctx, k_ram_count_nondet, gx, gy, 256, d_blocks); }
-        ZKW_TRY(launch_check("k_ram_count_nondet"));
+        const unsigned gy = (unsigned)(b1 - b0);
+        if (max_inst * nd_tiles >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "ram_run: more than 2^31 - 1 tiles of 256 cycles in one block");
+        { Prof _p(ctx, "k_ram_gp_groups"); ZKW_LAUNCH_2D(ctx, k_ram_gp_groups, max_inst * nd_tiles, gy, 256, d_blocks); }
+        ZKW_TRY(launch_check("k_ram_gp_groups"));
+        { Prof _p(ctx, "k_ram_gp_scan"); ZKW_LAUNCH_2D(ctx, k_ram_gp_scan, 1, gy, 256, d_blocks); }
+        ZKW_TRY(launch_check("k_ram_gp_scan"));
         { Prof _p(ctx, "k_ram_instances"); ZKW_LAUNCH_2D(ctx, k_ram_instances, blocks_for(max_inst, 64), gy, 64, d_blocks); }
         ZKW_TRY(launch_check("k_ram_instances"));
-        // the group's chains are still in the window: leave the synthesis its checkpoints (it never recomputes the chains)
-        { Prof _p(ctx, "k_ram_gp_ckpt"); ZKW_LAUNCH_2D(ctx, k_ram_gp_ckpt, blocks_for(max_inst * ram_gp_groups(w->capacity), 256), gy, 256, d_blocks); }
-        ZKW_TRY(launch_check("k_ram_gp_ckpt"));
         b0 = b1;
     }
     // a20: compact forms and public inputs of every instance (postprocessing/mod.rs:353-369)
