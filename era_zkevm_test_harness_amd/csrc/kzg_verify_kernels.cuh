@@ -53,10 +53,14 @@ static __device__ __forceinline__ void k_kzg_g2_prepare(const VB& vb, const uint
 // where the claims of a call are. records == 0: four arrays, claim i at commitments + 48 i, points + 32 i and values + 32 i (32
 // little-endian bytes), proofs + 48 i. records == 1: `commitments` is n / 2 zkw_eip4844_record and `proofs` n / 2
 // zkw_eip4844_proof_record; claim 2 j is blob j's opening at the record's evaluation_point and opening_value, claim 2 j + 1 its blob
-// proof at blob_challenge and blob_value, both against the record's commitment
+// proof at blob_challenge and blob_value, both against the record's commitment. records == 2 (zkw_eip4844_verify_blobs): commitments and
+// proofs as in form 0, `points` and `values` inside rows of 64 bytes (the openings: challenge, value; 32 big-endian bytes each), and
+// pre[i] != 0 (k_kzg_blob_eval's status: an element of blob i is not below r) makes claim i KZG_VERDICT_BAD_SCALAR when neither of its
+// points is malformed
 struct KzgClaims {
     const uint8_t *commitments, *points, *values, *proofs;
     u32 records;
+    const u32* pre;
 };
 
 static __device__ __forceinline__ bls::Fr kzg_scalar(const uint8_t* b, u32 form) {  // KZG_Z_LE32, KZG_Z_BE16 or KZG_Z_BE32
@@ -94,11 +98,13 @@ static __device__ __forceinline__ void k_kzg_verify_points(const VB& vb, KzgClai
     if (i >= n) return;
     const uint8_t *cb, *pb, *zb, *yb;
     u32 z_form = KZG_Z_LE32, y_form = KZG_Z_LE32;
-    if (!cl.records) {
+    if (cl.records != 1) {
+        const u32 row = cl.records ? 64u : 32u;
         cb = cl.commitments + 48 * (size_t)i;
         pb = cl.proofs + 48 * (size_t)i;
-        zb = cl.points + 32 * (size_t)i;
-        yb = cl.values + 32 * (size_t)i;
+        zb = cl.points + row * (size_t)i;
+        yb = cl.values + row * (size_t)i;
+        if (cl.records) z_form = y_form = KZG_Z_BE32;
     } else {
         const uint8_t* rec = cl.commitments + (size_t)(i >> 1) * KZG_REC_BYTES;
         const uint8_t* prf = cl.proofs + (size_t)(i >> 1) * KZG_PRF_BYTES;
@@ -115,6 +121,7 @@ static __device__ __forceinline__ void k_kzg_verify_points(const VB& vb, KzgClai
     if (!kzg_point_in(cb, &c)) st = KZG_VERDICT_BAD_COMMITMENT;
     else if (!kzg_point_in(pb, &pi)) st = KZG_VERDICT_BAD_PROOF;
     else if (!bls::below_modulus<bls::FrT>(z.w) || !bls::below_modulus<bls::FrT>(y.w)) st = KZG_VERDICT_BAD_SCALAR;
+    else if (cl.records == 2 && cl.pre[i]) st = KZG_VERDICT_BAD_SCALAR;
     status[i] = st;
     const bls::G1Aff none{bls::zero<bls::FqT>(), bls::zero<bls::FqT>()};
     if (st) {

@@ -1,11 +1,13 @@
 // zkw_kzg.hip — the EIP-4844 blob witness behind include/zkw.h: zkw_kzg_settings (the monomial trusted setup as a fixed-base table in
 // HBM), zkw_kzg_commit and zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:119-231 of the reference), and the KZG proofs
 // zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs), and their check, zkw_kzg_verifier with
-// zkw_kzg_verify and zkw_eip4844_verify (verify_kzg_proof). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh,
+// zkw_kzg_verify and zkw_eip4844_verify (verify_kzg_proof), zkw_kzg_evaluate_blobs (eval_poly) and zkw_eip4844_verify_blobs
+// (verify_proof_poly). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh,
 // kzg_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
 #include "kzg_open_kernels.cuh"
+#include "kzg_eval_kernels.cuh"
 #include "kzg_verify_kernels.cuh"
 
 #include <cstddef>
@@ -350,7 +352,7 @@ extern "C" int zkw_kzg_verify(const zkw_kzg_verifier* v, zkw_ctx* ctx, const uin
     ZKW_TRY(kzg_verify_check_call("zkw_kzg_verify", v, ctx, n));
     if (n == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    KzgClaims cl{nullptr, nullptr, nullptr, nullptr, 0};
+    KzgClaims cl{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     ZKW_TRY(ctx->in("kzg_in_commitments", commitments, n * 48, &cl.commitments));
     ZKW_TRY(ctx->in("kzg_in_points", points, n * 32, &cl.points));
     ZKW_TRY(ctx->in("kzg_in_values", values, n * 32, &cl.values));
@@ -374,8 +376,68 @@ extern "C" int zkw_eip4844_verify(const zkw_kzg_verifier* v, zkw_ctx* ctx, const
     ZKW_TRY(ctx->in("kzg_in_proof_records", proofs, n, &d_prf));
     uint8_t* d_verdicts = nullptr;
     ZKW_TRY(ctx->out("kzg_verdicts", verdicts, 2 * n, &d_verdicts));
-    const KzgClaims cl{reinterpret_cast<const uint8_t*>(d_rec), nullptr, nullptr, reinterpret_cast<const uint8_t*>(d_prf), 1};
+    const KzgClaims cl{reinterpret_cast<const uint8_t*>(d_rec), nullptr, nullptr, reinterpret_cast<const uint8_t*>(d_prf), 1, nullptr};
     ZKW_TRY(kzg_verify_device(v, ctx, cl, 2 * n, d_verdicts));
     ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, 2 * n));
+    return ctx->sync_if_host();
+}
+
+// ---- the check from the blob itself: challenge and value are recomputed, nothing the prover wrote down is taken on trust ----------------
+extern "C" int zkw_kzg_evaluate_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* points, size_t n, uint8_t* values) {
+    if (!ctx || (n && (!blob_evaluations || !points || !values))) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: null argument");
+    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: at most 32767 blobs per call, not %zu", n);
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_z = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(ctx->in("kzg_in_points", points, n * 32, &d_z));
+    bls::Fr* d_tw = nullptr;
+    uint8_t* d_y = nullptr;  // (scratch in both pointer modes: a refused call leaves `values` untouched)
+    u32* d_st = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_eval_values", n * 32, &d_y));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
+    { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
+    { Prof _p(ctx, "k_kzg_blob_eval"); ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, d_z, 32u, (const bls::Fr*)d_tw, d_y, 32u, d_st); }
+    std::vector<u32> st(n);
+    ZKW_TRY(ctx->read_small(st.data(), d_st, n * sizeof(u32)));
+    for (size_t j = 0; j < n; j++) {
+        if (st[j] == KZG_EVAL_BAD_POINT) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: the point of blob %zu is not below r", j);
+        if (st[j] != KZG_EVAL_OK) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: element %u of blob %zu is not below r", (unsigned)(st[j] - 1), j);
+    }
+    HIP_TRY(ctx->copy_async(values, d_y, n * 32, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* commitments,
+                                        const uint8_t* proofs, size_t n, uint8_t* verdicts, uint8_t* openings) {
+    if (!v || !ctx || (n && (!blob_evaluations || !commitments || !proofs || !verdicts))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_verify_blobs: null argument");
+    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_eip4844_verify_blobs: at most 32767 blobs per call, not %zu", n);
+    ZKW_TRY(kzg_verify_check_call("zkw_eip4844_verify_blobs", v, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t* d_ev = nullptr;
+    KzgClaims cl{nullptr, nullptr, nullptr, nullptr, 2, nullptr};
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(ctx->in("kzg_in_commitments", commitments, n * 48, &cl.commitments));
+    ZKW_TRY(ctx->in("kzg_in_proofs", proofs, n * 48, &cl.proofs));
+    uint8_t *d_verdicts = nullptr, *d_open = nullptr;  // a row of d_open: the blob's challenge, then its value there
+    ZKW_TRY(ctx->out("kzg_verdicts", verdicts, n, &d_verdicts));
+    if (openings) ZKW_TRY(ctx->out("kzg_openings", openings, n * 64, &d_open));
+    else ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_openings", n * 64, &d_open));  // the check reads them either way
+    bls::Fr* d_tw = nullptr;
+    u32* d_st = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
+    // one after another on the context's stream: the evaluation needs the challenge, the points kernel needs both
+    { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
+    { Prof _p(ctx, "k_kzg_blob_challenge"); ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, cl.commitments, 48u, d_open, 64u); }
+    { Prof _p(ctx, "k_kzg_blob_eval"); ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, (const uint8_t*)d_open, 64u, (const bls::Fr*)d_tw, d_open + 32, 64u, d_st); }
+    cl.points = d_open;
+    cl.values = d_open + 32;
+    cl.pre = d_st;
+    ZKW_TRY(kzg_verify_device(v, ctx, cl, n, d_verdicts));
+    ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, n));
+    if (openings) ZKW_TRY(ctx->finish_out(openings, d_open, n * 64));
     return ctx->sync_if_host();
 }

@@ -192,6 +192,8 @@ SYMBOLS = [
     ("zkw_kzg_verifier_bytes", _sz, [_vp]),
     ("zkw_kzg_verify", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("zkw_eip4844_verify", _int, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zkw_kzg_evaluate_blobs", _int, [_vp, _vp, _vp, _sz, _vp]),
+    ("zkw_eip4844_verify_blobs", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -959,6 +961,25 @@ class KzgSettings:
             pass
 
 
+def kzg_evaluate_blobs(ctx, evaluations, points):
+    """zkw_kzg_evaluate_blobs (eval_poly, kzg/src/lib.rs:327-358): `evaluations` = [n, 131072] bytes, blobs in evaluation form as
+    `KzgSettings.eip4844_prove(evaluations=True)` returns them, `points` = [n, 32] bytes, a point as 32 big-endian bytes below r
+    (blob_challenge's form); returns [n, 32]: p_j(points[j]) in the same form. An element or a point that is not below r raises
+    ZkwError(ERR_INVALID) naming it. Arrays as for `KzgSettings`."""
+    eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+    zptr, nz, _kz = KzgSettings._bytes(ctx, points, 32)
+    assert n == nz
+    if ctx.pointer_mode == PTR_DEVICE:
+        import torch
+
+        out = torch.empty((n, 32), dtype=torch.uint8, device=_kz.device)
+        _check(load().zkw_kzg_evaluate_blobs(ctx.handle, eptr, zptr, n, C.c_void_p(out.data_ptr() if n else None)))
+        return out
+    out = np.zeros((n, 32), np.uint8)
+    _check(load().zkw_kzg_evaluate_blobs(ctx.handle, eptr, zptr, n, _np_ptr(out) if n else None))
+    return out
+
+
 KZG_VERDICT_FAILS, KZG_VERDICT_HOLDS, KZG_VERDICT_BAD_COMMITMENT, KZG_VERDICT_BAD_PROOF, KZG_VERDICT_BAD_SCALAR = range(5)
 
 
@@ -1024,6 +1045,30 @@ class KzgVerifier:
         out = np.zeros((n, 2), np.uint8)
         _check(load().zkw_eip4844_verify(self.handle, ctx.handle, _np_ptr(rec) if n else None, _np_ptr(prf) if n else None, n, _np_ptr(out) if n else None))
         return out
+
+    def eip4844_verify_blobs(self, evaluations, commitments, proofs, ctx=None, openings=False):
+        """zkw_eip4844_verify_blobs (verify_proof_poly, kzg/src/lib.rs:292-301): `evaluations` = [n, 131072] bytes, the blobs in
+        evaluation form as a sidecar carries them, `commitments` and `proofs` = [n, 48] bytes; the challenge and the blob's value there
+        are recomputed from the blob. Returns [n] verdict bytes (4: a blob element is not below r); with `openings=True` returns
+        (verdicts, [n, 64] bytes): per blob the challenge and the value, 32 big-endian bytes each."""
+        ctx = ctx or self.ctx
+        eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+        cptr, nc, _kc = KzgSettings._bytes(ctx, commitments, 48)
+        pptr, np_, _kp = KzgSettings._bytes(ctx, proofs, 48)
+        assert n == nc == np_
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty((n,), dtype=torch.uint8, device=_kc.device)
+            op = torch.empty((n, 64), dtype=torch.uint8, device=_kc.device) if openings else None
+            _check(load().zkw_eip4844_verify_blobs(self.handle, ctx.handle, eptr, cptr, pptr, n, C.c_void_p(out.data_ptr() if n else None),
+                                                   C.c_void_p(op.data_ptr() if openings and n else None)))
+            return (out, op) if openings else out
+        out = np.zeros(n, np.uint8)
+        op = np.zeros((n, 64), np.uint8) if openings else None
+        _check(load().zkw_eip4844_verify_blobs(self.handle, ctx.handle, eptr, cptr, pptr, n, _np_ptr(out) if n else None,
+                                               _np_ptr(op) if openings and n else None))
+        return (out, op) if openings else out
 
     def free(self):
         if self.handle:

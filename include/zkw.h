@@ -792,9 +792,25 @@ int zkw_kzg_verify(const zkw_kzg_verifier *v, zkw_ctx *ctx, const uint8_t *commi
                    const uint8_t *values /*[n][32]*/, const uint8_t *proofs /*[n][48]*/, size_t n, uint8_t *verdicts /*[n]*/);
 /* The two proofs of n blobs from their records: verdicts[j][0] is opening_proof at the record's evaluation_point and
    opening_value, verdicts[j][1] is blob_proof at blob_challenge and blob_value, both against the record's commitment; the codes
-   of zkw_kzg_verify.  The challenge and the values are taken from the records, not recomputed from the blob. */
+   of zkw_kzg_verify.  The challenge and the values are taken from the records, not recomputed from the blob: that check is
+   zkw_eip4844_verify_blobs.  (The random-linear-combination batch form of the reference is not offered: the call is bound by the
+   latency of one wave per 8 claims and measured flat from 1 to 1 024 claims, so two pairings instead of 2 n would buy nothing.) */
 int zkw_eip4844_verify(const zkw_kzg_verifier *v, zkw_ctx *ctx, const zkw_eip4844_record *records /*[n]*/,
                        const zkw_eip4844_proof_record *proofs /*[n]*/, size_t n, uint8_t *verdicts /*[n][2]*/);
+/* eval_poly (kzg/src/lib.rs:327-358): values[j] = p_j(points[j]) for blob j in evaluation form. Points and values are 32
+   big-endian bytes (blob_challenge's form). ZKW_ERR_INVALID, naming blob and element (or the point) in zkw_last_error, when
+   something is not below r; the outputs are then untouched. One readback per call (the n status words). n = 0 is a no-op;
+   at most 32 767 blobs per call. */
+int zkw_kzg_evaluate_blobs(zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/, const uint8_t *points /*[n][32]*/,
+                           size_t n, uint8_t *values /*[n][32]*/);
+/* verify_proof_poly (lib.rs:292-301): per blob, challenge = compute_challenge(blob, commitment), y = eval_poly(blob, challenge),
+   verdict = the check of zkw_kzg_verify on (commitment, challenge, y, proof). Codes of zkw_kzg_verify; 4 here means a blob
+   element not below r; the lowest applicable code above 1 wins. openings (may be NULL): per blob the challenge and y, 32
+   big-endian bytes each (zeros for y under verdict 4). Nothing is read back: in device pointer mode the call only enqueues.
+   n = 0 is a no-op; at most 32 767 blobs per call. */
+int zkw_eip4844_verify_blobs(const zkw_kzg_verifier *v, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
+                             const uint8_t *commitments /*[n][48]*/, const uint8_t *proofs /*[n][48]*/, size_t n,
+                             uint8_t *verdicts /*[n]*/, uint8_t *openings /*[n][64] or NULL*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
