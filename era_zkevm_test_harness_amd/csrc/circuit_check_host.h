@@ -31,3 +31,12 @@ static int check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32
     if (first_bad) *first_bad = res.violations ? res.first_bad : 0;
     return ZKW_OK;
 }
+
+// an extern "C" zkw_<circuit>_check_satisfied: the argument check, whether the capacity fits the trace, then the check
+template <class S>
+static int check_satisfied_entry(const char* name, uint64_t min_rows, zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
+                                 uint64_t* n_violations, uint64_t* first_bad) {
+    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations) return fail(ZKW_ERR_INVALID, "%s: bad argument", name);
+    if (min_rows > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
+    return check_satisfied<S>(ctx, t, slot, capacity, n_violations, first_bad);
+}

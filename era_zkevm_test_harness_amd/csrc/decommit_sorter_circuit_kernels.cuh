@@ -15,6 +15,7 @@
 #include "scan_kernels.cuh"
 #include "decommit_kernels.cuh"
 #include "ram_circuit_kernels.cuh"
+#include "sorter_circuit_common.cuh"
 
 namespace zkw {
 
@@ -360,43 +361,9 @@ static __device__ __forceinline__ void k_ds_fill_row(const VB& vb, const DsSynth
     hist_flush(sh_hist, job.hist);
 }
 
-// the zero padding below the boundary rows and the multiplicity column (see k_ram_fill_tail)
+// (the boundary rows, the zero padding below them and the multiplicity column: k_sorter_fill_tail<DsCircuit>, sorter_circuit_common.cuh)
 constexpr int DS_BOUNDARY_ROWS = (DS_NUM_ROW_TYPES - DS_ROWS_PER_CYCLE + 1) & ~1;  // register rows, PI, flush rows, the closed-form section (rounded up to even: 16-byte stores below)
 __device__ __forceinline__ void ds_boundary_block(const DsSynthJob& job, u32 capacity, size_t n_rows);
-static __device__ __forceinline__ void k_ds_fill_tail(const VB& vb, const DsSynthJob* __restrict__ jobs, u32 n_jobs, u32 capacity, size_t n_rows) {
-    // 1-D grid: the first n_jobs blocks fill the boundary rows of one trace each (dispatched first and at raised priority: a chain of a dozen
-    // dependent permutations that the other blocks' stores hide), then (DS_G + DS_L + 1) * TAIL_CHUNKS blocks per trace
-    if (vb.x < n_jobs) {
-        __builtin_amdgcn_s_setprio(3);
-        ds_boundary_block(jobs[vb.x], capacity, n_rows);
-        return;
-    }
-    constexpr u32 PER_JOB = (DS_G + DS_L + 1) * TAIL_CHUNKS;
-    const u32 bid = (vb.x - n_jobs) % PER_JOB;
-    const DsSynthJob& job = jobs[(vb.x - n_jobs) / PER_JOB];
-    u64* trace = job.trace;
-    const int col = bid / TAIL_CHUNKS, ch = bid % TAIL_CHUNKS;
-    if (col < DS_G + DS_L) {
-        if (job.tail_clean) return;
-        const size_t bnd = (size_t)DS_BOUNDARY_ROW(capacity) + DS_BOUNDARY_ROWS;
-        const size_t n_pairs = (n_rows - bnd) / 2;
-        const size_t per = (n_pairs + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_pairs ? lo + per : n_pairs;
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(trace + (size_t)col * n_rows + bnd);
-        const ulonglong2 z = make_ulonglong2(0, 0);
-        for (size_t k = lo + threadIdx.x; k < hi; k += 256) c2[k] = z;
-        return;
-    }
-    u64* mlt = trace + (size_t)DS_MULT_COL * n_rows;
-    const size_t per = (n_rows + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_rows ? lo + per : n_rows;
-    for (size_t r = lo + threadIdx.x; r < (job.tail_clean && hi > 256 ? (lo < 256 ? 256 : lo) : hi); r += 256) {  // (a clean slot: rows >= 256 of the column are still zero)
-        u64 v = 0;
-        if (r < 256) {
-            v = job.hist[r];
-            if (r == 0) v += (u64)DS_L * n_rows - (u64)DS_LOOKUPS_PER_CYCLE * capacity - 8 - 4 * DS_CF_NUM_BYTES;  // (GIN's 8 byte cells and GOUT's, counted in job.hist by k_ds_fill_poseidon<1>)
-        }
-        mlt[r] = v;
-    }
-}
 
 // runs after everything else (same stream): BND_IN, BND_OUT, the flush permutation PF, PI
 __device__ __forceinline__ void ds_fill_register_rows(const DsSynthJob& job, u32 capacity, size_t n_rows) {
@@ -472,13 +439,9 @@ __device__ __forceinline__ void ds_fill_register_rows(const DsSynthJob& job, u32
 
 // runs after everything else (same stream): BND_IN, BND_OUT, the flush permutation PF (one lane), then the closed-form section
 // (closed_form_kernels.cuh) down to the PI row
-// (the extra block of k_ds_fill_tail, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
+// (the extra block of k_sorter_fill_tail<DsCircuit>, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
 __device__ __forceinline__ void ds_boundary_block(const DsSynthJob& job, u32 capacity, size_t n_rows) {
-    {
-        u64* trace = job.trace;
-        const size_t bnd = (size_t)DS_BOUNDARY_ROW(capacity);
-        for (int k = threadIdx.x; k < (DS_G + DS_L) * DS_BOUNDARY_ROWS; k += CF_THREADS) TR(k / DS_BOUNDARY_ROWS, bnd + k % DS_BOUNDARY_ROWS) = 0;
-    }
+    zero_boundary_rows<DS_G + DS_L, DS_BOUNDARY_ROWS>(job.trace, n_rows, (size_t)DS_BOUNDARY_ROW(capacity));
     __syncthreads();
     __shared__ u64 sh_oi[50], sh_oo[25], sh_fi[DS_FSM_ENC_LEN], sh_fo[DS_FSM_ENC_LEN], sh_flags[2];
     if (threadIdx.x == 0) ds_fill_register_rows(job, capacity, n_rows);
@@ -519,6 +482,17 @@ __device__ __forceinline__ void ds_boundary_block(const DsSynthJob& job, u32 cap
 struct DsFreshFlag {
     const zkw_decommit_query* sorted_q;
     __device__ u32 operator()(size_t i) const { return sorted_q[i].is_fresh ? 1u : 0u; }
+};
+
+// the circuit as k_sorter_fill_tail (sorter_circuit_common.cuh) and the host's synthesis driver see it
+struct DsCircuit {
+    using Job = DsSynthJob;
+    static constexpr int G = DS_G, L = DS_L, MULT_COL = DS_MULT_COL, BOUNDARY_ROWS = DS_BOUNDARY_ROWS, LOOKUPS_PER_CYCLE = DS_LOOKUPS_PER_CYCLE;
+    static __host__ __device__ size_t boundary_row(u32 capacity) { return (size_t)DS_BOUNDARY_ROW(capacity); }
+    static __host__ __device__ size_t region_stride(u32 capacity) { return (size_t)DS_REGION_STRIDE(capacity); }
+    static __host__ __device__ size_t min_rows(u32 capacity) { return (size_t)DS_MIN_ROWS(capacity); }
+    static __device__ u64 row0_extra() { return 8 + 4 * DS_CF_NUM_BYTES; }  // (GIN's 8 byte cells and GOUT's, counted in job.hist by k_ds_fill_poseidon<1>)
+    static __device__ __forceinline__ void boundary_block(const Job& job, u32 capacity, size_t n_rows) { ds_boundary_block(job, capacity, n_rows); }
 };
 
 #undef TR

@@ -327,40 +327,6 @@ static __device__ __forceinline__ void k_es_fill_row(const VB& vb, const EsSynth
 
 constexpr int ES_BOUNDARY_ROWS = (ES_NUM_ROW_TYPES - ES_ROWS_PER_CYCLE + 1) & ~1;  // register rows, PI, flush rows, the closed-form section (rounded up to even: 16-byte stores below)
 __device__ __forceinline__ void es_boundary_block(const EsSynthJob& job, u32 capacity, size_t n_rows);
-static __device__ __forceinline__ void k_es_fill_tail(const VB& vb, const EsSynthJob* __restrict__ jobs, u32 n_jobs, u32 capacity, size_t n_rows) {
-    // 1-D grid: the first n_jobs blocks fill the boundary rows of one trace each (dispatched first and at raised priority: a chain of a dozen
-    // dependent permutations that the other blocks' stores hide), then (ES_G + ES_L + 1) * TAIL_CHUNKS blocks per trace
-    if (vb.x < n_jobs) {
-        __builtin_amdgcn_s_setprio(3);
-        es_boundary_block(jobs[vb.x], capacity, n_rows);
-        return;
-    }
-    constexpr u32 PER_JOB = (ES_G + ES_L + 1) * TAIL_CHUNKS;
-    const u32 bid = (vb.x - n_jobs) % PER_JOB;
-    const EsSynthJob& job = jobs[(vb.x - n_jobs) / PER_JOB];
-    u64* trace = job.trace;
-    const int col = bid / TAIL_CHUNKS, ch = bid % TAIL_CHUNKS;
-    if (col < ES_G + ES_L) {
-        if (job.tail_clean) return;
-        const size_t bnd = (size_t)ES_BOUNDARY_ROW(capacity) + ES_BOUNDARY_ROWS;
-        const size_t n_pairs = (n_rows - bnd) / 2;
-        const size_t per = (n_pairs + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_pairs ? lo + per : n_pairs;
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(trace + (size_t)col * n_rows + bnd);
-        const ulonglong2 z = make_ulonglong2(0, 0);
-        for (size_t k = lo + threadIdx.x; k < hi; k += 256) c2[k] = z;
-        return;
-    }
-    u64* mlt = trace + (size_t)ES_MULT_COL * n_rows;
-    const size_t per = (n_rows + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_rows ? lo + per : n_rows;
-    for (size_t r = lo + threadIdx.x; r < (job.tail_clean && hi > 256 ? (lo < 256 ? 256 : lo) : hi); r += 256) {  // (a clean slot: rows >= 256 of the column are still zero)
-        u64 v = 0;
-        if (r < 256) {
-            v = job.hist[r];
-            if (r == 0) v += (u64)ES_L * n_rows - (u64)ES_LOOKUPS_PER_CYCLE * capacity - 4 * ES_CF_NUM_BYTES;  // (the section's byte cells: counted in job.hist by k_es_fill_row<A>)
-        }
-        mlt[r] = v;
-    }
-}
 
 // BND_IN, BND_OUT, the flush permutations F1..F3, PI (runs last on the stream: reads the last cycle's rows)
 __device__ __forceinline__ void es_fill_register_rows(const EsSynthJob& job, u32 capacity, size_t n_rows) {
@@ -425,13 +391,9 @@ __device__ __forceinline__ void es_fill_register_rows(const EsSynthJob& job, u32
 
 // BND_IN, BND_OUT, the flush permutations F1..F3 (one lane), then the closed-form section down to the PI row (runs last on the stream: reads
 // the last cycle's rows)
-// (the extra block of k_es_fill_tail, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
+// (the extra block of k_sorter_fill_tail<EsCircuit>, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
 __device__ __forceinline__ void es_boundary_block(const EsSynthJob& job, u32 capacity, size_t n_rows) {
-    {
-        u64* trace = job.trace;
-        const size_t bnd = (size_t)ES_BOUNDARY_ROW(capacity);
-        for (int k = threadIdx.x; k < (ES_G + ES_L) * ES_BOUNDARY_ROWS; k += CF_THREADS) TR(k / ES_BOUNDARY_ROWS, bnd + k % ES_BOUNDARY_ROWS) = 0;
-    }
+    zero_boundary_rows<ES_G + ES_L, ES_BOUNDARY_ROWS>(job.trace, n_rows, (size_t)ES_BOUNDARY_ROW(capacity));
     __syncthreads();
     if (threadIdx.x == 0) es_fill_register_rows(job, capacity, n_rows);
     cf_section_from_records<CfEventsSorter, SpecEventsSorter>(job.first_inst, job.inst, job.trace, n_rows, (size_t)ES_BOUNDARY_ROW(capacity), [](int, size_t) {});
@@ -443,6 +405,17 @@ struct EsKeptFlag {
     const zkw_log_query* sorted_q;
     size_t n;
     __device__ u32 operator()(size_t j) const { return (j + 1 < n && !sorted_q[j].rollback && sorted_q[j + 1].timestamp != sorted_q[j].timestamp) ? 1u : 0u; }
+};
+
+// the circuit as k_sorter_fill_tail (sorter_circuit_common.cuh) and the host's synthesis driver see it
+struct EsCircuit {
+    using Job = EsSynthJob;
+    static constexpr int G = ES_G, L = ES_L, MULT_COL = ES_MULT_COL, BOUNDARY_ROWS = ES_BOUNDARY_ROWS, LOOKUPS_PER_CYCLE = ES_LOOKUPS_PER_CYCLE;
+    static __host__ __device__ size_t boundary_row(u32 capacity) { return (size_t)ES_BOUNDARY_ROW(capacity); }
+    static __host__ __device__ size_t region_stride(u32 capacity) { return (size_t)ES_REGION_STRIDE(capacity); }
+    static __host__ __device__ size_t min_rows(u32 capacity) { return (size_t)ES_MIN_ROWS(capacity); }
+    static __device__ u64 row0_extra() { return 4 * ES_CF_NUM_BYTES; }  // (the section's byte cells: counted in job.hist by k_es_fill_row<A>)
+    static __device__ __forceinline__ void boundary_block(const Job& job, u32 capacity, size_t n_rows) { es_boundary_block(job, capacity, n_rows); }
 };
 
 #undef TR

@@ -229,40 +229,6 @@ static __device__ __forceinline__ void k_ld_fill_row(const VB& vb, const LdSynth
 
 constexpr int LD_BOUNDARY_ROWS = (LD_NUM_ROW_TYPES - LD_ROWS_PER_CYCLE + 1) & ~1;  // register rows, PI, flush rows, the closed-form section (rounded up to even: 16-byte stores below)
 __device__ __forceinline__ void ld_boundary_block(const LdSynthJob& job, u32 capacity, size_t n_rows);
-static __device__ __forceinline__ void k_ld_fill_tail(const VB& vb, const LdSynthJob* __restrict__ jobs, u32 n_jobs, u32 capacity, size_t n_rows) {
-    // 1-D grid: the first n_jobs blocks fill the boundary rows of one trace each (dispatched first and at raised priority: a chain of a dozen
-    // dependent permutations that the other blocks' stores hide), then (LD_G + LD_L + 1) * TAIL_CHUNKS blocks per trace
-    if (vb.x < n_jobs) {
-        __builtin_amdgcn_s_setprio(3);
-        ld_boundary_block(jobs[vb.x], capacity, n_rows);
-        return;
-    }
-    constexpr u32 PER_JOB = (LD_G + LD_L + 1) * TAIL_CHUNKS;
-    const u32 bid = (vb.x - n_jobs) % PER_JOB;
-    const LdSynthJob& job = jobs[(vb.x - n_jobs) / PER_JOB];
-    u64* trace = job.trace;
-    const int col = bid / TAIL_CHUNKS, ch = bid % TAIL_CHUNKS;
-    if (col < LD_G + LD_L) {
-        if (job.tail_clean) return;
-        const size_t bnd = (size_t)LD_BOUNDARY_ROW(capacity) + LD_BOUNDARY_ROWS;
-        const size_t n_pairs = (n_rows - bnd) / 2;
-        const size_t per = (n_pairs + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_pairs ? lo + per : n_pairs;
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(trace + (size_t)col * n_rows + bnd);
-        const ulonglong2 z = make_ulonglong2(0, 0);
-        for (size_t k = lo + threadIdx.x; k < hi; k += 256) c2[k] = z;
-        return;
-    }
-    u64* mlt = trace + (size_t)LD_MULT_COL * n_rows;
-    const size_t per = (n_rows + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_rows ? lo + per : n_rows;
-    for (size_t r = lo + threadIdx.x; r < (job.tail_clean && hi > 256 ? (lo < 256 ? 256 : lo) : hi); r += 256) {  // (a clean slot: rows >= 256 of the column are still zero)
-        u64 v = 0;
-        if (r < 256) {
-            v = job.hist[r];
-            if (r == 0) v += (u64)LD_L * n_rows - (u64)LD_LOOKUPS_PER_CYCLE * capacity;
-        }
-        mlt[r] = v;
-    }
-}
 
 // BND_IN, BND_OUT, PI (runs last on the stream: reads the last cycle's row Q)
 __device__ __forceinline__ void ld_fill_register_rows(const LdSynthJob& job, u32 capacity, size_t n_rows) {
@@ -305,17 +271,24 @@ __device__ __forceinline__ void ld_fill_register_rows(const LdSynthJob& job, u32
 }
 
 // the register rows (one lane), then the closed-form section down to the PI row (runs last on the stream: reads the last cycle's rows)
-// (the extra block of k_ld_fill_tail, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
+// (the extra block of k_sorter_fill_tail<LdCircuit>, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
 __device__ __forceinline__ void ld_boundary_block(const LdSynthJob& job, u32 capacity, size_t n_rows) {
-    {
-        u64* trace = job.trace;
-        const size_t bnd = (size_t)LD_BOUNDARY_ROW(capacity);
-        for (int k = threadIdx.x; k < (LD_G + LD_L) * LD_BOUNDARY_ROWS; k += CF_THREADS) TR(k / LD_BOUNDARY_ROWS, bnd + k % LD_BOUNDARY_ROWS) = 0;
-    }
+    zero_boundary_rows<LD_G + LD_L, LD_BOUNDARY_ROWS>(job.trace, n_rows, (size_t)LD_BOUNDARY_ROW(capacity));
     __syncthreads();
     if (threadIdx.x == 0) ld_fill_register_rows(job, capacity, n_rows);
     cf_section_from_records<CfLogDemux, SpecLogDemux>(job.first_inst, job.inst, job.trace, n_rows, (size_t)LD_BOUNDARY_ROW(capacity), [](int, size_t) {});
 }
+
+// the circuit as k_sorter_fill_tail (sorter_circuit_common.cuh) and the host's synthesis driver see it
+struct LdCircuit {
+    using Job = LdSynthJob;
+    static constexpr int G = LD_G, L = LD_L, MULT_COL = LD_MULT_COL, BOUNDARY_ROWS = LD_BOUNDARY_ROWS, LOOKUPS_PER_CYCLE = LD_LOOKUPS_PER_CYCLE;
+    static __host__ __device__ size_t boundary_row(u32 capacity) { return (size_t)LD_BOUNDARY_ROW(capacity); }
+    static __host__ __device__ size_t region_stride(u32 capacity) { return (size_t)LD_REGION_STRIDE(capacity); }
+    static __host__ __device__ size_t min_rows(u32 capacity) { return (size_t)LD_MIN_ROWS(capacity); }
+    static __device__ u64 row0_extra() { return 0; }
+    static __device__ __forceinline__ void boundary_block(const Job& job, u32 capacity, size_t n_rows) { ld_boundary_block(job, capacity, n_rows); }
+};
 
 #undef TR
 }  // namespace zkw

@@ -414,40 +414,6 @@ static __device__ __forceinline__ void k_ss_fill_row(const VB& vb, const SsSynth
 
 constexpr int SS_BOUNDARY_ROWS = (SS_NUM_ROW_TYPES - SS_ROWS_PER_CYCLE + 1) & ~1;  // register rows, PI, flush rows, the closed-form section (rounded up to even: 16-byte stores below)
 __device__ __forceinline__ void ss_boundary_block(const SsSynthJob& job, u32 capacity, size_t n_rows);
-static __device__ __forceinline__ void k_ss_fill_tail(const VB& vb, const SsSynthJob* __restrict__ jobs, u32 n_jobs, u32 capacity, size_t n_rows) {
-    // 1-D grid: the first n_jobs blocks fill the boundary rows of one trace each (dispatched first and at raised priority: a chain of a dozen
-    // dependent permutations that the other blocks' stores hide), then (SS_G + SS_L + 1) * TAIL_CHUNKS blocks per trace
-    if (vb.x < n_jobs) {
-        __builtin_amdgcn_s_setprio(3);
-        ss_boundary_block(jobs[vb.x], capacity, n_rows);
-        return;
-    }
-    constexpr u32 PER_JOB = (SS_G + SS_L + 1) * TAIL_CHUNKS;
-    const u32 bid = (vb.x - n_jobs) % PER_JOB;
-    const SsSynthJob& job = jobs[(vb.x - n_jobs) / PER_JOB];
-    u64* trace = job.trace;
-    const int col = bid / TAIL_CHUNKS, ch = bid % TAIL_CHUNKS;
-    if (col < SS_G + SS_L) {
-        if (job.tail_clean) return;
-        const size_t bnd = (size_t)SS_BOUNDARY_ROW(capacity) + SS_BOUNDARY_ROWS;
-        const size_t n_pairs = (n_rows - bnd) / 2;
-        const size_t per = (n_pairs + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_pairs ? lo + per : n_pairs;
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(trace + (size_t)col * n_rows + bnd);
-        const ulonglong2 z = make_ulonglong2(0, 0);
-        for (size_t k = lo + threadIdx.x; k < hi; k += 256) c2[k] = z;
-        return;
-    }
-    u64* mlt = trace + (size_t)SS_MULT_COL * n_rows;
-    const size_t per = (n_rows + TAIL_CHUNKS - 1) / TAIL_CHUNKS, lo = ch * per, hi = lo + per < n_rows ? lo + per : n_rows;
-    for (size_t r = lo + threadIdx.x; r < (job.tail_clean && hi > 256 ? (lo < 256 ? 256 : lo) : hi); r += 256) {  // (a clean slot: rows >= 256 of the column are still zero)
-        u64 v = 0;
-        if (r < 256) {
-            v = job.hist[r];
-            if (r == 0) v += (u64)SS_L * n_rows - (u64)SS_LOOKUPS_PER_CYCLE * capacity - 4 * SS_CF_NUM_BYTES;  // (the section's byte cells: counted in job.hist by k_ss_fill_row<A>)
-        }
-        mlt[r] = v;
-    }
-}
 
 // BND_IN, BND_OUT, the flush permutations F1..F3, PI (runs last on the stream: reads the last cycle's rows)
 __device__ __forceinline__ void ss_fill_register_rows(const SsSynthJob& job, u32 capacity, size_t n_rows) {
@@ -532,17 +498,24 @@ __device__ __forceinline__ void ss_fill_register_rows(const SsSynthJob& job, u32
 }
 
 // the register rows (one lane), then the closed-form section down to the PI row (runs last on the stream: reads the last cycle's rows)
-// (the extra block of k_ss_fill_tail, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
+// (the extra block of k_sorter_fill_tail<SsCircuit>, whose other blocks zero the rows BELOW the boundary rows: the boundary rows' cells are zeroed here first)
 __device__ __forceinline__ void ss_boundary_block(const SsSynthJob& job, u32 capacity, size_t n_rows) {
-    {
-        u64* trace = job.trace;
-        const size_t bnd = (size_t)SS_BOUNDARY_ROW(capacity);
-        for (int k = threadIdx.x; k < (SS_G + SS_L) * SS_BOUNDARY_ROWS; k += CF_THREADS) TR(k / SS_BOUNDARY_ROWS, bnd + k % SS_BOUNDARY_ROWS) = 0;
-    }
+    zero_boundary_rows<SS_G + SS_L, SS_BOUNDARY_ROWS>(job.trace, n_rows, (size_t)SS_BOUNDARY_ROW(capacity));
     __syncthreads();
     if (threadIdx.x == 0) ss_fill_register_rows(job, capacity, n_rows);
     cf_section_from_records<CfStorageSorter, SpecStorageSorter>(job.first_inst, job.inst, job.trace, n_rows, (size_t)SS_BOUNDARY_ROW(capacity), [](int, size_t) {});
 }
+
+// the circuit as k_sorter_fill_tail (sorter_circuit_common.cuh) and the host's synthesis driver see it
+struct SsCircuit {
+    using Job = SsSynthJob;
+    static constexpr int G = SS_G, L = SS_L, MULT_COL = SS_MULT_COL, BOUNDARY_ROWS = SS_BOUNDARY_ROWS, LOOKUPS_PER_CYCLE = SS_LOOKUPS_PER_CYCLE;
+    static __host__ __device__ size_t boundary_row(u32 capacity) { return (size_t)SS_BOUNDARY_ROW(capacity); }
+    static __host__ __device__ size_t region_stride(u32 capacity) { return (size_t)SS_REGION_STRIDE(capacity); }
+    static __host__ __device__ size_t min_rows(u32 capacity) { return (size_t)SS_MIN_ROWS(capacity); }
+    static __device__ u64 row0_extra() { return 4 * SS_CF_NUM_BYTES; }  // (the section's byte cells: counted in job.hist by k_ss_fill_row<A>)
+    static __device__ __forceinline__ void boundary_block(const Job& job, u32 capacity, size_t n_rows) { ss_boundary_block(job, capacity, n_rows); }
+};
 
 #undef TR
 }  // namespace zkw

@@ -1675,7 +1675,7 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
         j.challenges = w->challenges + 18 * b;
         j.gp_ckpt = w->gp_ckpt + 4 * ram_gp_groups(capacity) * idx;
         {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
-            const uint64_t tag = ((uint64_t)ZKW_CIRCUIT_RAM_PERMUTATION << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
+            const uint64_t tag = slot_layout_tag(ZKW_CIRCUIT_RAM_PERMUTATION, capacity, n_rows);
             const size_t slot = (first_slot + k) % t->n_slots;
             bool clean = false;
             j.trace = claims.claim(slot, tag, &clean);
@@ -1722,18 +1722,12 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
 
 extern "C" int zkw_ram_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
                                        uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations)
-        return fail(ZKW_ERR_INVALID, "zkw_ram_check_satisfied: bad argument");
-    if (RC_MIN_ROWS(capacity) > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-    return check_satisfied<SpecRam>(ctx, t, slot, capacity, n_violations, first_bad);
+    return check_satisfied_entry<SpecRam>("zkw_ram_check_satisfied", RC_MIN_ROWS(capacity), ctx, t, slot, capacity, n_violations, first_bad);
 }
 
 extern "C" int zkw_decommit_sorter_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
                                                    uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations)
-        return fail(ZKW_ERR_INVALID, "zkw_decommit_sorter_check_satisfied: bad argument");
-    if (DS_MIN_ROWS(capacity) > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-    return check_satisfied<SpecDecommitSorter>(ctx, t, slot, capacity, n_violations, first_bad);
+    return check_satisfied_entry<SpecDecommitSorter>("zkw_decommit_sorter_check_satisfied", DS_MIN_ROWS(capacity), ctx, t, slot, capacity, n_violations, first_bad);
 }
 
 // ------------------------------------------------------------------------------------------------ closed forms from records (a20)

@@ -411,6 +411,49 @@ struct SlotClaims {
         return rc;
     }
 };
+// the tag of a slot that holds a trace of this circuit type, capacity and length (never 0 = unknown)
+inline uint64_t slot_layout_tag(int circuit_type, u32 capacity, size_t n_rows) {
+    return ((uint64_t)circuit_type << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
+}
+
+// The accessor quartet of a witness type W (zkw_<name>_witness_bytes / _device_ptr / _get / _free) over its
+// `const void* Array(const W*, int what, size_t* bytes)`, which answers (nullptr, 0) to a `what` it does not know.
+// (zkw_ram_witness_* stays apart: lazy materialisation, its own status codes and messages.)
+template <auto Array, class W>
+static size_t witness_bytes(const W* w, int what) {
+    size_t b = 0;
+    if (w) (void)Array(w, what, &b);
+    return b;
+}
+template <auto Array, class W>
+static const void* witness_device_ptr(const W* w, int what) {
+    size_t b = 0;
+    return w ? Array(w, what, &b) : nullptr;
+}
+// negative_is_empty: the decommit sorter's get has always looked the array up before judging `what`, so a negative one is an empty array there
+template <auto Array, class W>
+static int witness_get(const W* w, int what, void* dst, size_t dst_bytes, const char* name, int last_what, bool negative_is_empty = false) {
+    if (!w || !dst) return fail(ZKW_ERR_INVALID, "%s: null argument", name);
+    if (what > last_what || (what < 0 && !negative_is_empty)) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
+    size_t bytes = 0;
+    const void* src = Array(w, what, &bytes);
+    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
+    if (bytes == 0) return ZKW_OK;
+    zkw_ctx* ctx = w->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return ctx->sync_if_host();
+}
+template <class W>
+static void witness_free(W* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->ctx->device);
+    (void)w->ctx->sync_stream();
+    w->release();
+    zkw_ctx* owner = w->ctx;
+    delete w;
+    ctx_release(owner);
+}
 
 
 // device-level steps (zkw_api.hip): every builder's queue chains, challenges and grand products go through these

@@ -169,36 +169,12 @@ static const void* dcm_array(const zkw_decommitter_witness* w, int what, size_t*
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_decommitter_witness_bytes(const zkw_decommitter_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)dcm_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_decommitter_witness_device_ptr(const zkw_decommitter_witness* w, int what) {
-    size_t b = 0;
-    return w ? dcm_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_decommitter_witness_bytes(const zkw_decommitter_witness* w, int what) { return witness_bytes<dcm_array>(w, what); }
+extern "C" const void* zkw_decommitter_witness_device_ptr(const zkw_decommitter_witness* w, int what) { return witness_device_ptr<dcm_array>(w, what); }
 extern "C" int zkw_decommitter_witness_get(const zkw_decommitter_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_decommitter_witness_get: null argument");
-    if (what < 0 || what > ZKW_DCM_SHA256_ROUNDS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = dcm_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<dcm_array>(w, what, dst, dst_bytes, "zkw_decommitter_witness_get", ZKW_DCM_SHA256_ROUNDS);
 }
-extern "C" void zkw_decommitter_witness_free(zkw_decommitter_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_decommitter_witness_free(zkw_decommitter_witness* w) { witness_free(w); }
 
 // ------------------------------------------------------------------------------------------------ L1 messages hasher
 extern "C" int zkw_linear_keccak256(zkw_ctx* ctx, const zkw_log_query* messages, size_t n, uint8_t* hash_out) {
@@ -383,36 +359,12 @@ static const void* pc_array(const zkw_precompile_witness* w, int what, size_t* b
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_precompile_witness_bytes(const zkw_precompile_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)pc_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_precompile_witness_device_ptr(const zkw_precompile_witness* w, int what) {
-    size_t b = 0;
-    return w ? pc_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_precompile_witness_bytes(const zkw_precompile_witness* w, int what) { return witness_bytes<pc_array>(w, what); }
+extern "C" const void* zkw_precompile_witness_device_ptr(const zkw_precompile_witness* w, int what) { return witness_device_ptr<pc_array>(w, what); }
 extern "C" int zkw_precompile_witness_get(const zkw_precompile_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_precompile_witness_get: null argument");
-    if (what < 0 || what > ZKW_PRC_SHA256_ROUNDS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = pc_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<pc_array>(w, what, dst, dst_bytes, "zkw_precompile_witness_get", ZKW_PRC_SHA256_ROUNDS);
 }
-extern "C" void zkw_precompile_witness_free(zkw_precompile_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_precompile_witness_free(zkw_precompile_witness* w) { witness_free(w); }
 
 // ------------------------------------------------------------------------------------------------ storage application (a17)
 struct zkw_storage_application_witness {
@@ -567,36 +519,12 @@ static const void* sap_array(const zkw_storage_application_witness* w, int what,
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_storage_application_witness_bytes(const zkw_storage_application_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)sap_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_storage_application_witness_device_ptr(const zkw_storage_application_witness* w, int what) {
-    size_t b = 0;
-    return w ? sap_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_storage_application_witness_bytes(const zkw_storage_application_witness* w, int what) { return witness_bytes<sap_array>(w, what); }
+extern "C" const void* zkw_storage_application_witness_device_ptr(const zkw_storage_application_witness* w, int what) { return witness_device_ptr<sap_array>(w, what); }
 extern "C" int zkw_storage_application_witness_get(const zkw_storage_application_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_storage_application_witness_get: null argument");
-    if (what < 0 || what > ZKW_SAP_INSTANCES) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = sap_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<sap_array>(w, what, dst, dst_bytes, "zkw_storage_application_witness_get", ZKW_SAP_INSTANCES);
 }
-extern "C" void zkw_storage_application_witness_free(zkw_storage_application_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_storage_application_witness_free(zkw_storage_application_witness* w) { witness_free(w); }
 
 // (work_ctx: whose stream and scratch do the work — the witness's own context, or the private one of a joint call over many witnesses)
 static int precompile_closed_forms_with(zkw_ctx* ctx, zkw_precompile_witness* w, const uint64_t** compact, const uint64_t** public_inputs);
@@ -1060,7 +988,7 @@ int nl_synthesize_with(zkw_ctx* ctx, int circuit_type, const NlPrepare& prepare,
         // The fill writes the lookup cells of every row above the boundary and the general-purpose cells of the header / gate rows;
         // everything else is zero. A slot whose previous tenant was the same layout (circuit, capacity, rows) already has those
         // zeros: nothing to clear (the multiplicity column is rewritten over the tables' rows). Otherwise: clear it.
-        const uint64_t tag = ((uint64_t)circuit_type << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
+        const uint64_t tag = slot_layout_tag(circuit_type, capacity, n_rows);
         bool clean = false;
         u64* tr = claims.claim(inst[k].t, inst[k].slot, tag, &clean);
         jobs[k] = NlJob{prep[k].hdr_bits, prep[k].free_elems, prep[k].state_before, inst[k].public_input, tr, d_keys + k * keys_n, d_hist + k * hist_n};

@@ -230,36 +230,12 @@ static const void* dec_array(const zkw_decommit_witness* w, int what, size_t* by
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_decommit_witness_bytes(const zkw_decommit_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)dec_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_decommit_witness_device_ptr(const zkw_decommit_witness* w, int what) {
-    size_t b = 0;
-    return w ? dec_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_decommit_witness_bytes(const zkw_decommit_witness* w, int what) { return witness_bytes<dec_array>(w, what); }
+extern "C" const void* zkw_decommit_witness_device_ptr(const zkw_decommit_witness* w, int what) { return witness_device_ptr<dec_array>(w, what); }
 extern "C" int zkw_decommit_witness_get(const zkw_decommit_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_decommit_witness_get: null argument");
-    size_t bytes = 0;
-    const void* src = dec_array(w, what, &bytes);
-    if (!src && bytes == 0 && what > ZKW_DEC_PUBLIC_INPUTS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<dec_array>(w, what, dst, dst_bytes, "zkw_decommit_witness_get", ZKW_DEC_PUBLIC_INPUTS, true);
 }
-extern "C" void zkw_decommit_witness_free(zkw_decommit_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_decommit_witness_free(zkw_decommit_witness* w) { witness_free(w); }
 
 // ------------------------------------------------------------------------------------------------ events sorter
 struct zkw_events_witness {
@@ -429,36 +405,12 @@ static const void* evt_array(const zkw_events_witness* w, int what, size_t* byte
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_events_witness_bytes(const zkw_events_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)evt_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_events_witness_device_ptr(const zkw_events_witness* w, int what) {
-    size_t b = 0;
-    return w ? evt_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_events_witness_bytes(const zkw_events_witness* w, int what) { return witness_bytes<evt_array>(w, what); }
+extern "C" const void* zkw_events_witness_device_ptr(const zkw_events_witness* w, int what) { return witness_device_ptr<evt_array>(w, what); }
 extern "C" int zkw_events_witness_get(const zkw_events_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_events_witness_get: null argument");
-    if (what < 0 || what > ZKW_EVT_PUBLIC_INPUTS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = evt_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<evt_array>(w, what, dst, dst_bytes, "zkw_events_witness_get", ZKW_EVT_PUBLIC_INPUTS);
 }
-extern "C" void zkw_events_witness_free(zkw_events_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_events_witness_free(zkw_events_witness* w) { witness_free(w); }
 
 // ------------------------------------------------------------------------------------------------ log demuxer
 struct zkw_demux_witness {
@@ -594,36 +546,12 @@ static const void* dmx_array(const zkw_demux_witness* w, int what, size_t* bytes
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_demux_witness_bytes(const zkw_demux_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)dmx_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_demux_witness_device_ptr(const zkw_demux_witness* w, int what) {
-    size_t b = 0;
-    return w ? dmx_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_demux_witness_bytes(const zkw_demux_witness* w, int what) { return witness_bytes<dmx_array>(w, what); }
+extern "C" const void* zkw_demux_witness_device_ptr(const zkw_demux_witness* w, int what) { return witness_device_ptr<dmx_array>(w, what); }
 extern "C" int zkw_demux_witness_get(const zkw_demux_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_demux_witness_get: null argument");
-    if (what < 0 || what > ZKW_DMX_PUBLIC_INPUTS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = dmx_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<dmx_array>(w, what, dst, dst_bytes, "zkw_demux_witness_get", ZKW_DMX_PUBLIC_INPUTS);
 }
-extern "C" void zkw_demux_witness_free(zkw_demux_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_demux_witness_free(zkw_demux_witness* w) { witness_free(w); }
 
 // ------------------------------------------------------------------------------------------------ storage sorter
 struct zkw_storage_witness {
@@ -831,63 +759,88 @@ static const void* sto_array(const zkw_storage_witness* w, int what, size_t* byt
         default: *bytes = 0; return nullptr;
     }
 }
-extern "C" size_t zkw_storage_witness_bytes(const zkw_storage_witness* w, int what) {
-    size_t b = 0;
-    if (w) (void)sto_array(w, what, &b);
-    return b;
-}
-extern "C" const void* zkw_storage_witness_device_ptr(const zkw_storage_witness* w, int what) {
-    size_t b = 0;
-    return w ? sto_array(w, what, &b) : nullptr;
-}
+extern "C" size_t zkw_storage_witness_bytes(const zkw_storage_witness* w, int what) { return witness_bytes<sto_array>(w, what); }
+extern "C" const void* zkw_storage_witness_device_ptr(const zkw_storage_witness* w, int what) { return witness_device_ptr<sto_array>(w, what); }
 extern "C" int zkw_storage_witness_get(const zkw_storage_witness* w, int what, void* dst, size_t dst_bytes) {
-    if (!w || !dst) return fail(ZKW_ERR_INVALID, "zkw_storage_witness_get: null argument");
-    if (what < 0 || what > ZKW_STO_PUBLIC_INPUTS) return fail(ZKW_ERR_INVALID, "unknown array %d", what);
-    size_t bytes = 0;
-    const void* src = sto_array(w, what, &bytes);
-    if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "need %zu bytes, got %zu", bytes, dst_bytes);
-    if (bytes == 0) return ZKW_OK;
-    zkw_ctx* ctx = w->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return ctx->sync_if_host();
+    return witness_get<sto_array>(w, what, dst, dst_bytes, "zkw_storage_witness_get", ZKW_STO_PUBLIC_INPUTS);
 }
-extern "C" void zkw_storage_witness_free(zkw_storage_witness* w) {
-    if (!w) return;
-    (void)hipSetDevice(w->ctx->device);
-    (void)w->ctx->sync_stream();
-    w->release();
-    zkw_ctx* owner = w->ctx;
-    delete w;
-    ctx_release(owner);
-}
+extern "C" void zkw_storage_witness_free(zkw_storage_witness* w) { witness_free(w); }
 
-// ------------------------------------------------------------------------------------------------ decommit sorter synthesis (a21, type 2)
-extern "C" int zkw_decommit_sorter_synthesize(zkw_ctx* ctx, const zkw_decommit_witness* cw, size_t first_instance, size_t n_instances,
-                                              zkw_trace* t, size_t first_slot) {
-    zkw_decommit_witness* w = const_cast<zkw_decommit_witness*>(cw);
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_decommit_sorter_synthesize: bad argument");
+// ------------------------------------------------------------------------------------------------ synthesis (a21): types 2, 11 / 12, 4, 9
+// One driver for the four circuits. What a circuit adds to it (a struct S below):
+//   W, Circuit (the traits of its kernel header), TYPE (the circuit type of the slot tag), the names of the entry point, of its scratch and of
+//   its tail span; refuse(w, t): its own refusals, none for most; prepare(ctx, w): what its fills need and the builder did not leave (the lazy
+//   prefix); public_inputs(w); fill_job(w, job): the witness's pointers; launch_fills(..): its fill kernels in order.
+
+// one fill launch: its profile span, the launch's name, the text of its launch check
+template <auto Body, int BS, class J>
+static int launch_fill(zkw_ctx* ctx, const char* span, const char* name, const char* what, dim3 grid, const J* d_jobs, u32 capacity, size_t n_rows) {
+    { Prof _p(ctx, span); ZKW_TRY((Launcher<Body, BS>::go(ctx, name, grid, 0, d_jobs, capacity, n_rows))); }
+    return launch_check(what);
+}
+// (queue / Poseidon2 kernels: a lane per cycle in blocks of 64; row kernels: blocks of 256)
+#define FILL_Q(kernel, P) ZKW_TRY((launch_fill<&kernel<P>, 64>(ctx, #kernel, #kernel, #kernel "<" #P ">", g64, d_jobs, capacity, n_rows)));
+#define FILL_ROW(kernel, row, R, span) ZKW_TRY((launch_fill<&kernel<row>, 256>(ctx, span, #kernel, #kernel "<" #R ">", g256, d_jobs, capacity, n_rows)));
+
+template <class S>
+static int sorter_synthesize(zkw_ctx* ctx, typename S::W* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
+    using C = typename S::Circuit;
+    using Job = typename C::Job;
+    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "%s: bad argument", S::ENTRY);
     if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
     if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
+    ZKW_TRY(S::refuse(w, t));
     const u32 capacity = w->capacity;
     const size_t n_rows = t->n_rows;
-    if (DS_MIN_ROWS(capacity) > n_rows)
-        return fail(ZKW_ERR_INVALID, "capacity %u needs %llu rows, trace has %zu", capacity, (unsigned long long)DS_MIN_ROWS(capacity), n_rows);
+    if (C::min_rows(capacity) > n_rows)
+        return fail(ZKW_ERR_INVALID, "capacity %u needs %llu rows, trace has %zu", capacity, (unsigned long long)C::min_rows(capacity), n_rows);
     if (n_rows & 1) return fail(ZKW_ERR_INVALID, "trace length must be even (it is a power of two in every circuit)");
     if (n_instances == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!w->fresh_prefix) {
-        HIP_TRY(dev_malloc((void**)&w->fresh_prefix, (w->n + 2) * sizeof(u32)));
-        ZKW_TRY(flag_prefix(ctx, "k_ds_fresh_prefix", DsFreshFlag{w->sorted_q}, w->n, w->fresh_prefix));
-    }
+    ZKW_TRY(S::prepare(ctx, w));
     u32* d_hist = nullptr;
-    ZKW_TRY(ctx->scratch_t<u32>("ds_hist", n_instances * 256, &d_hist));
+    ZKW_TRY(ctx->scratch_t<u32>(S::HIST, n_instances * 256, &d_hist));
     HIP_TRY(ctx->memset_async(d_hist, 0, n_instances * 256 * sizeof(u32)));
     SlotClaims claims(t);
-    std::vector<DsSynthJob> jobs(n_instances);
+    std::vector<Job> jobs(n_instances);
+    // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
+    const uint64_t tag = slot_layout_tag(S::TYPE, capacity, n_rows);
     for (size_t k = 0; k < n_instances; k++) {
-        DsSynthJob& j = jobs[k];
+        Job& j = jobs[k];
+        S::fill_job(w, j);
         j.inst = w->instances + first_instance + k;
+        j.first_inst = w->instances;  // one block per witness
+        j.n_block = w->n;
+        j.public_input = S::public_inputs(w) + 4 * (first_instance + k);
+        bool clean = false;
+        j.trace = claims.claim((first_slot + k) % t->n_slots, tag, &clean);
+        j.tail_clean = clean;
+        j.hist = d_hist + 256 * k;
+    }
+    Job* d_jobs = nullptr;
+    ZKW_TRY(ctx->upload(S::JOBS, jobs, &d_jobs));
+    const unsigned nj = (unsigned)n_instances;
+    const u32 rstride = (u32)C::region_stride(capacity);
+    const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
+    ZKW_TRY(S::launch_fills(ctx, d_jobs, capacity, n_rows, g64, g256));
+    { Prof _p(ctx, S::TAIL); ZKW_LAUNCH_T(ctx, k_sorter_fill_tail<C>, S::TAIL, nj * ((C::G + C::L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
+    ZKW_TRY(launch_check(S::TAIL));
+    return claims.commit_if(ctx->sync_if_host());
+}
+
+struct DsSynth {
+    using W = zkw_decommit_witness;
+    using Circuit = DsCircuit;
+    static constexpr int TYPE = 2;
+    static constexpr const char *ENTRY = "zkw_decommit_sorter_synthesize", *HIST = "ds_hist", *JOBS = "ds_jobs", *TAIL = "k_ds_fill_tail";
+    static int refuse(const W*, const zkw_trace*) { return ZKW_OK; }
+    static int prepare(zkw_ctx* ctx, W* w) {
+        if (w->fresh_prefix) return ZKW_OK;
+        HIP_TRY(dev_malloc((void**)&w->fresh_prefix, (w->n + 2) * sizeof(u32)));
+        return flag_prefix(ctx, "k_ds_fresh_prefix", DsFreshFlag{w->sorted_q}, w->n, w->fresh_prefix);
+    }
+    static const u64* public_inputs(const W* w) { return w->public_inputs; }
+    static void fill_job(const W* w, DsSynthJob& j) {
         j.sorted_q = w->sorted_q;
         j.unsorted_enc = w->unsorted_enc; j.sorted_enc = w->sorted_enc;
         j.unsorted_tails = w->unsorted_tails; j.sorted_tails = w->sorted_tails;
@@ -895,254 +848,136 @@ extern "C" int zkw_decommit_sorter_synthesize(zkw_ctx* ctx, const zkw_decommit_w
         j.fresh_prefix = w->fresh_prefix;
         j.challenges = w->challenges;
         j.lhs_z = w->lhs_z; j.rhs_z = w->rhs_z;
-        j.n_block = w->n;
         memcpy(j.rq_tail_in, w->dedup_in.tail, 96);
         j.rq_len_in = w->dedup_in.length;
-        {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
-            const uint64_t tag = ((uint64_t)2 << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
-            const size_t slot = (first_slot + k) % t->n_slots;
-            bool clean = false;
-            j.trace = claims.claim(slot, tag, &clean);
-            j.tail_clean = clean;
-        }
-        j.hist = d_hist + 256 * k;
-        j.public_input = w->public_inputs + 4 * (first_instance + k);
-        j.first_inst = w->instances;  // one block per witness
     }
-    DsSynthJob* d_jobs = nullptr;
-    ZKW_TRY(ctx->upload("ds_jobs", jobs, &d_jobs));
-    const unsigned nj = (unsigned)n_instances;
-    const u32 rstride = (u32)DS_REGION_STRIDE(capacity);
-    const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
-    { Prof _p(ctx, "k_ds_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ds_fill_poseidon<0>), "k_ds_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_poseidon<0>"));
-    { Prof _p(ctx, "k_ds_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ds_fill_poseidon<1>), "k_ds_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_poseidon<1>"));
-    { Prof _p(ctx, "k_ds_fill_poseidon"); ZKW_LAUNCH_D(ctx, (k_ds_fill_poseidon<2>), "k_ds_fill_poseidon", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_poseidon<2>"));
-    { Prof _p(ctx, "k_ds_fill_row_A"); ZKW_LAUNCH_D(ctx, (k_ds_fill_row<DS_ROW_A>), "k_ds_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_row<A>"));
-    { Prof _p(ctx, "k_ds_fill_row_B"); ZKW_LAUNCH_D(ctx, (k_ds_fill_row<DS_ROW_B>), "k_ds_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_row<B>"));
-    { Prof _p(ctx, "k_ds_fill_row_C"); ZKW_LAUNCH_D(ctx, (k_ds_fill_row<DS_ROW_C>), "k_ds_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_row<C>"));
-    { Prof _p(ctx, "k_ds_fill_row_D"); ZKW_LAUNCH_D(ctx, (k_ds_fill_row<DS_ROW_D>), "k_ds_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_row<D>"));
-    { Prof _p(ctx, "k_ds_fill_tail"); ZKW_LAUNCH(ctx, k_ds_fill_tail, nj * ((DS_G + DS_L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ds_fill_tail"));
-    return claims.commit_if(ctx->sync_if_host());
-}
+    static int launch_fills(zkw_ctx* ctx, const DsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
+#define ROW(R) FILL_ROW(k_ds_fill_row, DS_ROW_##R, R, "k_ds_fill_row_" #R)
+        FILL_Q(k_ds_fill_poseidon, 0) FILL_Q(k_ds_fill_poseidon, 1) FILL_Q(k_ds_fill_poseidon, 2) ROW(A) ROW(B) ROW(C) ROW(D)
+#undef ROW
+        return ZKW_OK;
+    }
+};
 
-// ------------------------------------------------------------------------------------------------ events / L1 messages sorter synthesis (a21, types 11 / 12)
-extern "C" int zkw_events_sorter_synthesize(zkw_ctx* ctx, const zkw_events_witness* cw, size_t first_instance, size_t n_instances,
-                                            zkw_trace* t, size_t first_slot) {
-    zkw_events_witness* w = const_cast<zkw_events_witness*>(cw);
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_events_sorter_synthesize: bad argument");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    const u32 capacity = w->capacity;
-    const size_t n_rows = t->n_rows, n = w->n;
-    if (ES_MIN_ROWS(capacity) > n_rows)
-        return fail(ZKW_ERR_INVALID, "capacity %u needs %llu rows, trace has %zu", capacity, (unsigned long long)ES_MIN_ROWS(capacity), n_rows);
-    if (n_rows & 1) return fail(ZKW_ERR_INVALID, "trace length must be even (it is a power of two in every circuit)");
-    if (n_instances == 0) return ZKW_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!w->kept_prefix) {
-        HIP_TRY(dev_malloc((void**)&w->kept_prefix, (n + 2) * sizeof(u32)));
-        ZKW_TRY(flag_prefix(ctx, "k_es_kept_prefix", EsKeptFlag{w->sorted_q, n}, n, w->kept_prefix));
+struct EsSynth {  // events and L1 messages sorters (types 11 / 12): one layout, tagged 11
+    using W = zkw_events_witness;
+    using Circuit = EsCircuit;
+    static constexpr int TYPE = 11;
+    static constexpr const char *ENTRY = "zkw_events_sorter_synthesize", *HIST = "es_hist", *JOBS = "es_jobs", *TAIL = "k_es_fill_tail";
+    static int refuse(const W*, const zkw_trace*) { return ZKW_OK; }
+    static int prepare(zkw_ctx* ctx, W* w) {
+        if (w->kept_prefix) return ZKW_OK;
+        HIP_TRY(dev_malloc((void**)&w->kept_prefix, (w->n + 2) * sizeof(u32)));
+        return flag_prefix(ctx, "k_es_kept_prefix", EsKeptFlag{w->sorted_q, w->n}, w->n, w->kept_prefix);
     }
-    u32* d_hist = nullptr;
-    ZKW_TRY(ctx->scratch_t<u32>("es_hist", n_instances * 256, &d_hist));
-    HIP_TRY(ctx->memset_async(d_hist, 0, n_instances * 256 * sizeof(u32)));
-    const size_t m = n ? n : 1;
-    u64 *u_enc = w->enc_all, *s_enc = w->enc_all + 20 * m;
-    u64 *u_new = w->tails_all + 4 * m, *s_new = w->tails_all + 12 * m, *r_new = w->tails_all + 16 * m;
-    SlotClaims claims(t);
-    std::vector<EsSynthJob> jobs(n_instances);
-    for (size_t k = 0; k < n_instances; k++) {
-        EsSynthJob& j = jobs[k];
-        j.inst = w->instances + first_instance + k;
+    static const u64* public_inputs(const W* w) { return w->cf_pi + COMPACT_FORM_LEN * w->n_instances; }
+    static void fill_job(const W* w, EsSynthJob& j) {
+        const size_t m = w->n ? w->n : 1;  // (the builder's arrays of an empty queue have one element)
         j.sorted_q = w->sorted_q;
-        j.unsorted_enc = u_enc; j.sorted_enc = s_enc;
-        j.unsorted_new_tails = u_new; j.sorted_new_tails = s_new; j.result_new_tails = r_new;
+        j.unsorted_enc = w->enc_all; j.sorted_enc = w->enc_all + 20 * m;
+        j.unsorted_new_tails = w->tails_all + 4 * m; j.sorted_new_tails = w->tails_all + 12 * m; j.result_new_tails = w->tails_all + 16 * m;
         j.kept_prefix = w->kept_prefix;
         j.challenges = w->challenges;
         j.lhs_z = w->lhs_z; j.rhs_z = w->rhs_z;
-        j.n_block = n;
         memcpy(j.rq_tail_in, w->result_in.tail, 32);
         j.rq_len_in = w->result_in.length;
-        j.public_input = w->cf_pi + COMPACT_FORM_LEN * w->n_instances + 4 * (first_instance + k);
-        j.first_inst = w->instances;  // one block per witness
-        {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
-            const uint64_t tag = ((uint64_t)11 << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
-            const size_t slot = (first_slot + k) % t->n_slots;
-            bool clean = false;
-            j.trace = claims.claim(slot, tag, &clean);
-            j.tail_clean = clean;
-        }
-        j.hist = d_hist + 256 * k;
     }
-    EsSynthJob* d_jobs = nullptr;
-    ZKW_TRY(ctx->upload("es_jobs", jobs, &d_jobs));
-    const unsigned nj = (unsigned)n_instances;
-    const u32 rstride = (u32)ES_REGION_STRIDE(capacity);
-    const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
-    { Prof _p(ctx, "k_es_fill_queue"); ZKW_LAUNCH_D(ctx, (k_es_fill_queue<0>), "k_es_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_es_fill_queue<0>"));
-    { Prof _p(ctx, "k_es_fill_queue"); ZKW_LAUNCH_D(ctx, (k_es_fill_queue<1>), "k_es_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_es_fill_queue<1>"));
-    { Prof _p(ctx, "k_es_fill_queue"); ZKW_LAUNCH_D(ctx, (k_es_fill_queue<2>), "k_es_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_es_fill_queue<2>"));
-#define ES_LAUNCH_ROW(R) { Prof _p(ctx, "k_es_fill_row"); ZKW_LAUNCH_D(ctx, (k_es_fill_row<ES_ROW_##R>), "k_es_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); } \
-    ZKW_TRY(launch_check("k_es_fill_row<" #R ">"));
-    ES_LAUNCH_ROW(A) ES_LAUNCH_ROW(NTV) ES_LAUNCH_ROW(W) ES_LAUNCH_ROW(Q)  // NTV after the queue kernels: it writes the range checks into their rows' lookup columns
-#undef ES_LAUNCH_ROW
-    { Prof _p(ctx, "k_es_fill_tail"); ZKW_LAUNCH(ctx, k_es_fill_tail, nj * ((ES_G + ES_L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_es_fill_tail"));
-    return claims.commit_if(ctx->sync_if_host());
-}
+    static int launch_fills(zkw_ctx* ctx, const EsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
+#define ROW(R) FILL_ROW(k_es_fill_row, ES_ROW_##R, R, "k_es_fill_row")
+        FILL_Q(k_es_fill_queue, 0) FILL_Q(k_es_fill_queue, 1) FILL_Q(k_es_fill_queue, 2)
+        ROW(A) ROW(NTV) ROW(W) ROW(Q)  // NTV after the queue kernels: it writes the range checks into their rows' lookup columns
+#undef ROW
+        return ZKW_OK;
+    }
+};
 
-extern "C" int zkw_events_sorter_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
-                                                 uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations)
-        return fail(ZKW_ERR_INVALID, "zkw_events_sorter_check_satisfied: bad argument");
-    if (ES_MIN_ROWS(capacity) > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-    return check_satisfied<SpecEventsSorter>(ctx, t, slot, capacity, n_violations, first_bad);
-}
-
-// ------------------------------------------------------------------------------------------------ LogDemuxer synthesis
-extern "C" int zkw_log_demux_synthesize(zkw_ctx* ctx, const zkw_demux_witness* w, size_t first_instance, size_t n_instances,
-                                        zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_log_demux_synthesize: bad argument");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (!w->default_params)
-        return fail(ZKW_ERR_INVALID, "the LogDemuxer circuit hard-wires ZKW_DEMUX_PARAMS_DEFAULT; this witness was built with other routing constants");
-    if (t->n_cols < LD_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the LogDemuxer needs %d (zkw_trace_create_with_columns)", t->n_cols, LD_COLS);
-    const u32 capacity = w->capacity;
-    const size_t n_rows = t->n_rows, n = w->n;
-    if (LD_MIN_ROWS(capacity) > n_rows)
-        return fail(ZKW_ERR_INVALID, "capacity %u needs %llu rows, trace has %zu", capacity, (unsigned long long)LD_MIN_ROWS(capacity), n_rows);
-    if (n_rows & 1) return fail(ZKW_ERR_INVALID, "trace length must be even (it is a power of two in every circuit)");
-    if (n_instances == 0) return ZKW_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    u32* d_hist = nullptr;
-    ZKW_TRY(ctx->scratch_t<u32>("ld_hist", n_instances * 256, &d_hist));
-    HIP_TRY(ctx->memset_async(d_hist, 0, n_instances * 256 * sizeof(u32)));
-    SlotClaims claims(t);
-    std::vector<LdSynthJob> jobs(n_instances);
-    for (size_t k = 0; k < n_instances; k++) {
-        LdSynthJob& j = jobs[k];
-        j.inst = w->instances + first_instance + k;
+struct LdSynth {
+    using W = const zkw_demux_witness;
+    using Circuit = LdCircuit;
+    static constexpr int TYPE = 4;
+    static constexpr const char *ENTRY = "zkw_log_demux_synthesize", *HIST = "ld_hist", *JOBS = "ld_jobs", *TAIL = "k_ld_fill_tail";
+    static int refuse(const W* w, const zkw_trace* t) {
+        if (!w->default_params)
+            return fail(ZKW_ERR_INVALID, "the LogDemuxer circuit hard-wires ZKW_DEMUX_PARAMS_DEFAULT; this witness was built with other routing constants");
+        if (t->n_cols < LD_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the LogDemuxer needs %d (zkw_trace_create_with_columns)", t->n_cols, LD_COLS);
+        return ZKW_OK;
+    }
+    static int prepare(zkw_ctx*, W*) { return ZKW_OK; }
+    static const u64* public_inputs(const W* w) { return w->cf_pi + COMPACT_FORM_LEN * w->n_instances; }
+    static void fill_job(const W* w, LdSynthJob& j) {
+        const size_t n = w->n;
         j.in_enc = w->enc_all;
         j.in_new_tails = w->tails_all + 4 * n;
         j.out_new_tails = w->tails_all + 12 * n;
         j.route_count = w->route_count;
         for (int c = 0; c < 7; c++) j.offsets[c] = w->offsets[c];
-        j.n_block = n;
-        j.public_input = w->cf_pi + COMPACT_FORM_LEN * w->n_instances + 4 * (first_instance + k);
-        j.first_inst = w->instances;  // one block per witness
-        {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
-            const uint64_t tag = ((uint64_t)4 << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
-            const size_t slot = (first_slot + k) % t->n_slots;
-            bool clean = false;
-            j.trace = claims.claim(slot, tag, &clean);
-            j.tail_clean = clean;
-        }
-        j.hist = d_hist + 256 * k;
     }
-    LdSynthJob* d_jobs = nullptr;
-    ZKW_TRY(ctx->upload("ld_jobs", jobs, &d_jobs));
-    const unsigned nj = (unsigned)n_instances;
-    const u32 rstride = (u32)LD_REGION_STRIDE(capacity);
-    const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
-    { Prof _p(ctx, "k_ld_fill_queue"); ZKW_LAUNCH_D(ctx, (k_ld_fill_queue<0>), "k_ld_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ld_fill_queue<0>"));
-    { Prof _p(ctx, "k_ld_fill_queue"); ZKW_LAUNCH_D(ctx, (k_ld_fill_queue<1>), "k_ld_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ld_fill_queue<1>"));
-#define LD_LAUNCH_ROW(R) { Prof _p(ctx, "k_ld_fill_row"); ZKW_LAUNCH_D(ctx, (k_ld_fill_row<LD_ROW_##R>), "k_ld_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); } \
-    ZKW_TRY(launch_check("k_ld_fill_row<" #R ">"));
-    LD_LAUNCH_ROW(X0) LD_LAUNCH_ROW(X1) LD_LAUNCH_ROW(X2) LD_LAUNCH_ROW(X3) LD_LAUNCH_ROW(R) LD_LAUNCH_ROW(Q)
-#undef LD_LAUNCH_ROW
-    { Prof _p(ctx, "k_ld_fill_tail"); ZKW_LAUNCH(ctx, k_ld_fill_tail, nj * ((LD_G + LD_L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ld_fill_tail"));
-    return claims.commit_if(ctx->sync_if_host());
-}
+    static int launch_fills(zkw_ctx* ctx, const LdSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
+#define ROW(R) FILL_ROW(k_ld_fill_row, LD_ROW_##R, R, "k_ld_fill_row")
+        FILL_Q(k_ld_fill_queue, 0) FILL_Q(k_ld_fill_queue, 1) ROW(X0) ROW(X1) ROW(X2) ROW(X3) ROW(R) ROW(Q)
+#undef ROW
+        return ZKW_OK;
+    }
+};
 
-extern "C" int zkw_log_demux_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
-                                             uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations)
-        return fail(ZKW_ERR_INVALID, "zkw_log_demux_check_satisfied: bad argument");
-    if (LD_MIN_ROWS(capacity) > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-    return check_satisfied<SpecLogDemux>(ctx, t, slot, capacity, n_violations, first_bad);
-}
-
-// compact closed-form inputs and public inputs of a precompile witness's instances, computed once and kept with the witness
-// ------------------------------------------------------------------------------------------------ StorageSorter synthesis
-extern "C" int zkw_storage_sorter_synthesize(zkw_ctx* ctx, const zkw_storage_witness* w, size_t first_instance, size_t n_instances,
-                                             zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_storage_sorter_synthesize: bad argument");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (t->n_cols < SS_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the StorageSorter needs %d", t->n_cols, SS_COLS);
-    const u32 capacity = w->capacity;
-    const size_t n_rows = t->n_rows, n = w->n;
-    if (SS_MIN_ROWS(capacity) > n_rows)
-        return fail(ZKW_ERR_INVALID, "capacity %u needs %llu rows, trace has %zu", capacity, (unsigned long long)SS_MIN_ROWS(capacity), n_rows);
-    if (n_rows & 1) return fail(ZKW_ERR_INVALID, "trace length must be even (it is a power of two in every circuit)");
-    if (n_instances == 0) return ZKW_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    u32* d_hist = nullptr;
-    ZKW_TRY(ctx->scratch_t<u32>("ss_hist", n_instances * 256, &d_hist));
-    HIP_TRY(ctx->memset_async(d_hist, 0, n_instances * 256 * sizeof(u32)));
-    SlotClaims claims(t);
-    std::vector<SsSynthJob> jobs(n_instances);
-    for (size_t k = 0; k < n_instances; k++) {
-        SsSynthJob& j = jobs[k];
-        j.inst = w->instances + first_instance + k;
+struct SsSynth {
+    using W = const zkw_storage_witness;
+    using Circuit = SsCircuit;
+    static constexpr int TYPE = 9;
+    static constexpr const char *ENTRY = "zkw_storage_sorter_synthesize", *HIST = "ss_hist", *JOBS = "ss_jobs", *TAIL = "k_ss_fill_tail";
+    static int refuse(const W*, const zkw_trace* t) {
+        if (t->n_cols < SS_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the StorageSorter needs %d", t->n_cols, SS_COLS);
+        return ZKW_OK;
+    }
+    static int prepare(zkw_ctx*, W*) { return ZKW_OK; }
+    static const u64* public_inputs(const W* w) { return w->cf_pi + COMPACT_FORM_LEN * w->n_instances; }
+    static void fill_job(const W* w, SsSynthJob& j) {
+        const size_t n = w->n;
         j.unsorted_enc = w->enc_all; j.sorted_enc = w->enc_all + 20 * n;
         j.unsorted_new_tails = w->tails_all + 4 * n; j.sorted_new_tails = w->tails_all + 12 * n; j.result_new_tails = w->tails_all + 16 * n;
         j.challenges = w->challenges;
         j.lhs_z = w->lhs_z; j.rhs_z = w->rhs_z;
         j.sc.D = reinterpret_cast<int*>(w->scans); j.sc.S = w->scans + n; j.sc.R = w->scans + 2 * n; j.sc.E = w->scans + 3 * n;
-        j.n_block = n;
-        j.public_input = w->cf_pi + COMPACT_FORM_LEN * w->n_instances + 4 * (first_instance + k);
-        j.first_inst = w->instances;  // one block per witness
-        {   // a slot whose previous tenant was this layout keeps its zero padding rows (zkw_ctx.h slot_tag; every other writer resets the tag)
-            const uint64_t tag = ((uint64_t)9 << 56) ^ ((uint64_t)capacity << 24) ^ (uint64_t)n_rows ^ 0x5A00000000000000ull;
-            const size_t slot = (first_slot + k) % t->n_slots;
-            bool clean = false;
-            j.trace = claims.claim(slot, tag, &clean);
-            j.tail_clean = clean;
-        }
-        j.hist = d_hist + 256 * k;
     }
-    SsSynthJob* d_jobs = nullptr;
-    ZKW_TRY(ctx->upload("ss_jobs", jobs, &d_jobs));
-    const unsigned nj = (unsigned)n_instances;
-    const u32 rstride = (u32)SS_REGION_STRIDE(capacity);
-    const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
-    { Prof _p(ctx, "k_ss_fill_queue"); ZKW_LAUNCH_D(ctx, (k_ss_fill_queue<0>), "k_ss_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ss_fill_queue<0>"));
-    { Prof _p(ctx, "k_ss_fill_queue"); ZKW_LAUNCH_D(ctx, (k_ss_fill_queue<1>), "k_ss_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ss_fill_queue<1>"));
-    { Prof _p(ctx, "k_ss_fill_queue"); ZKW_LAUNCH_D(ctx, (k_ss_fill_queue<2>), "k_ss_fill_queue", g64, 64, 0, d_jobs, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ss_fill_queue<2>"));
-#define SS_LAUNCH_ROW(R) { Prof _p(ctx, "k_ss_fill_row"); ZKW_LAUNCH_D(ctx, (k_ss_fill_row<SS_ROW_##R>), "k_ss_fill_row", g256, 256, 0, d_jobs, capacity, n_rows); } \
-    ZKW_TRY(launch_check("k_ss_fill_row<" #R ">"));
-    SS_LAUNCH_ROW(A) SS_LAUNCH_ROW(X0) SS_LAUNCH_ROW(X1) SS_LAUNCH_ROW(X2) SS_LAUNCH_ROW(X3) SS_LAUNCH_ROW(X4) SS_LAUNCH_ROW(X5)
-    SS_LAUNCH_ROW(X6) SS_LAUNCH_ROW(X7) SS_LAUNCH_ROW(K) SS_LAUNCH_ROW(C1) SS_LAUNCH_ROW(C2) SS_LAUNCH_ROW(Q)
-#undef SS_LAUNCH_ROW
-    { Prof _p(ctx, "k_ss_fill_tail"); ZKW_LAUNCH(ctx, k_ss_fill_tail, nj * ((SS_G + SS_L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
-    ZKW_TRY(launch_check("k_ss_fill_tail"));
-    return claims.commit_if(ctx->sync_if_host());
+    static int launch_fills(zkw_ctx* ctx, const SsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
+#define ROW(R) FILL_ROW(k_ss_fill_row, SS_ROW_##R, R, "k_ss_fill_row")
+        FILL_Q(k_ss_fill_queue, 0) FILL_Q(k_ss_fill_queue, 1) FILL_Q(k_ss_fill_queue, 2)
+        ROW(A) ROW(X0) ROW(X1) ROW(X2) ROW(X3) ROW(X4) ROW(X5) ROW(X6) ROW(X7) ROW(K) ROW(C1) ROW(C2) ROW(Q)
+#undef ROW
+        return ZKW_OK;
+    }
+};
+#undef FILL_Q
+#undef FILL_ROW
+
+// (the decommit and events sorters' first synthesis call computes the lazy prefix the witness then keeps: hence the const_cast)
+extern "C" int zkw_decommit_sorter_synthesize(zkw_ctx* ctx, const zkw_decommit_witness* w, size_t first_instance, size_t n_instances,
+                                              zkw_trace* t, size_t first_slot) {
+    return sorter_synthesize<DsSynth>(ctx, const_cast<zkw_decommit_witness*>(w), first_instance, n_instances, t, first_slot);
+}
+extern "C" int zkw_events_sorter_synthesize(zkw_ctx* ctx, const zkw_events_witness* w, size_t first_instance, size_t n_instances,
+                                            zkw_trace* t, size_t first_slot) {
+    return sorter_synthesize<EsSynth>(ctx, const_cast<zkw_events_witness*>(w), first_instance, n_instances, t, first_slot);
+}
+extern "C" int zkw_log_demux_synthesize(zkw_ctx* ctx, const zkw_demux_witness* w, size_t first_instance, size_t n_instances,
+                                        zkw_trace* t, size_t first_slot) {
+    return sorter_synthesize<LdSynth>(ctx, w, first_instance, n_instances, t, first_slot);
+}
+extern "C" int zkw_storage_sorter_synthesize(zkw_ctx* ctx, const zkw_storage_witness* w, size_t first_instance, size_t n_instances,
+                                             zkw_trace* t, size_t first_slot) {
+    return sorter_synthesize<SsSynth>(ctx, w, first_instance, n_instances, t, first_slot);
 }
 
+// (zkw_decommit_sorter_check_satisfied: zkw_api.hip)
+extern "C" int zkw_events_sorter_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
+                                                 uint64_t* n_violations, uint64_t* first_bad) {
+    return check_satisfied_entry<SpecEventsSorter>("zkw_events_sorter_check_satisfied", ES_MIN_ROWS(capacity), ctx, t, slot, capacity, n_violations, first_bad);
+}
+extern "C" int zkw_log_demux_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
+                                             uint64_t* n_violations, uint64_t* first_bad) {
+    return check_satisfied_entry<SpecLogDemux>("zkw_log_demux_check_satisfied", LD_MIN_ROWS(capacity), ctx, t, slot, capacity, n_violations, first_bad);
+}
 extern "C" int zkw_storage_sorter_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity,
                                                   uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations)
-        return fail(ZKW_ERR_INVALID, "zkw_storage_sorter_check_satisfied: bad argument");
-    if (SS_MIN_ROWS(capacity) > t->n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-    return check_satisfied<SpecStorageSorter>(ctx, t, slot, capacity, n_violations, first_bad);
+    return check_satisfied_entry<SpecStorageSorter>("zkw_storage_sorter_check_satisfied", SS_MIN_ROWS(capacity), ctx, t, slot, capacity, n_violations, first_bad);
 }
-

@@ -358,18 +358,49 @@ EVENTS_INSTANCE = np.dtype(
  EVT_COMPACT_FORMS, EVT_PUBLIC_INPUTS) = range(15)
 
 
-class EventsWitness:
+class _Witness:
+    """Owner of a zkw_<_PREFIX>_witness handle: every witness type but the RAM one reads its arrays the same way.
+    A subclass names the C symbol prefix and the element types (_DTYPES, default u64) and shapes (_SHAPES) of its arrays."""
+
+    _PREFIX = None
+    _DTYPES = {}
+    _SHAPES = {}
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.handle = C.c_void_p(None)
+
+    def get(self, what):
+        lib = load()
+        nbytes = getattr(lib, f"zkw_{self._PREFIX}_witness_bytes")(self.handle, what)
+        dt = self._DTYPES.get(what, np.dtype("<u8"))
+        out = np.zeros(nbytes // dt.itemsize, dt)
+        if nbytes:
+            _check(getattr(lib, f"zkw_{self._PREFIX}_witness_get")(self.handle, what, _np_ptr(out), nbytes))
+        shape = self._SHAPES.get(what)
+        return out.reshape(shape) if shape else out
+
+    def free(self):
+        if self.handle:
+            getattr(load(), f"zkw_{self._PREFIX}_witness_free")(self.handle)
+            self.handle = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class EventsWitness(_Witness):
     """Owner of a zkw_events_witness handle."""
 
+    _PREFIX = "events"
     _DTYPES = {EVT_SORTED_QUERIES: LOG_QUERY, EVT_RESULT_QUERIES: LOG_QUERY, EVT_INSTANCES: EVENTS_INSTANCE}
     _SHAPES = {EVT_UNSORTED_ENC: (-1, 20), EVT_SORTED_ENC: (-1, 20), EVT_UNSORTED_OLD_TAILS: (-1, 4),
                EVT_UNSORTED_NEW_TAILS: (-1, 4), EVT_SORTED_OLD_TAILS: (-1, 4), EVT_SORTED_NEW_TAILS: (-1, 4),
                EVT_RESULT_NEW_TAILS: (-1, 4), EVT_CHALLENGES: (2, 21), EVT_LHS_Z: (2, -1), EVT_RHS_Z: (2, -1),
                EVT_COMPACT_FORMS: (-1, 18), EVT_PUBLIC_INPUTS: (-1, 4)}
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
 
     @property
     def num_instances(self):
@@ -378,27 +409,6 @@ class EventsWitness:
     @property
     def num_results(self):
         return load().zkw_events_witness_num_results(self.handle)
-
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_events_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_events_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
-
-    def free(self):
-        if self.handle:
-            load().zkw_events_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 DEMUX_FSM = np.dtype([("initial_log_queue_state", QUEUE_STATE4), ("queue_state", QUEUE_STATE4, (6,))])
@@ -410,41 +420,17 @@ DEMUX_INSTANCE = np.dtype(
  DMX_OUT_OFFSETS, DMX_INSTANCES, DMX_COMPACT_FORMS, DMX_PUBLIC_INPUTS) = range(11)
 
 
-class DemuxWitness:
+class DemuxWitness(_Witness):
     """Owner of a zkw_demux_witness handle."""
 
+    _PREFIX = "demux"
     _DTYPES = {DMX_OUT_QUERIES: LOG_QUERY, DMX_INSTANCES: DEMUX_INSTANCE}
     _SHAPES = {DMX_IN_ENC: (-1, 20), DMX_OUT_ENC: (-1, 20), DMX_IN_OLD_TAILS: (-1, 4), DMX_IN_NEW_TAILS: (-1, 4),
                DMX_OUT_OLD_TAILS: (-1, 4), DMX_OUT_NEW_TAILS: (-1, 4), DMX_COMPACT_FORMS: (-1, 18), DMX_PUBLIC_INPUTS: (-1, 4)}
 
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
-
     @property
     def num_instances(self):
         return load().zkw_demux_witness_num_instances(self.handle)
-
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_demux_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_demux_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
-
-    def free(self):
-        if self.handle:
-            load().zkw_demux_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 STORAGE_FSM = np.dtype(
@@ -464,19 +450,16 @@ STORAGE_INSTANCE = np.dtype(
  STO_LHS_Z, STO_RHS_Z, STO_INSTANCES, STO_COMPACT_FORMS, STO_PUBLIC_INPUTS) = range(17)
 
 
-class StorageWitness:
+class StorageWitness(_Witness):
     """Owner of a zkw_storage_witness handle."""
 
+    _PREFIX = "storage"
     _DTYPES = {STO_SORTED_QUERIES: LOG_QUERY, STO_RESULT_QUERIES: LOG_QUERY, STO_INSTANCES: STORAGE_INSTANCE,
                STO_SORTED_EXT_TS: np.dtype("<u4")}
     _SHAPES = {STO_UNSORTED_ENC: (-1, 20), STO_LHS_ENC: (-1, 20), STO_SORTED_ENC: (-1, 20), STO_UNSORTED_OLD_TAILS: (-1, 4),
                STO_UNSORTED_NEW_TAILS: (-1, 4), STO_SORTED_OLD_TAILS: (-1, 4), STO_SORTED_NEW_TAILS: (-1, 4),
                STO_RESULT_NEW_TAILS: (-1, 4), STO_CHALLENGES: (2, 21), STO_LHS_Z: (2, -1), STO_RHS_Z: (2, -1),
                STO_COMPACT_FORMS: (-1, 18), STO_PUBLIC_INPUTS: (-1, 4)}
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
 
     @property
     def num_instances(self):
@@ -485,27 +468,6 @@ class StorageWitness:
     @property
     def num_results(self):
         return load().zkw_storage_witness_num_results(self.handle)
-
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_storage_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_storage_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
-
-    def free(self):
-        if self.handle:
-            load().zkw_storage_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 DECOMMITTER_FSM = np.dtype(
@@ -557,42 +519,17 @@ assert KECCAK_ROUND_RECORD.itemsize == 344
 SAP_DERIVED_KEYS, SAP_MERKLE_PATHS, SAP_LEAF_INDEXES, SAP_ROOTS, SAP_INSTANCES = range(5)
 
 
-class StorageApplicationWitness:
+class StorageApplicationWitness(_Witness):
     """Owner of a zkw_storage_application_witness handle."""
 
+    _PREFIX = "storage_application"
     _DTYPES = {SAP_DERIVED_KEYS: np.dtype("u1"), SAP_MERKLE_PATHS: np.dtype("u1"), SAP_ROOTS: np.dtype("u1"),
                SAP_INSTANCES: STORAGE_APPLICATION_INSTANCE}
     _SHAPES = {SAP_DERIVED_KEYS: (-1, 32), SAP_MERKLE_PATHS: (-1, 256, 32), SAP_ROOTS: (-1, 32)}
 
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
-
     @property
     def num_instances(self):
         return load().zkw_storage_application_witness_num_instances(self.handle)
-
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_storage_application_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_storage_application_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
-
-    def free(self):
-        if self.handle:
-            load().zkw_storage_application_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 
 class StorageTreeDevice:
@@ -1082,15 +1019,12 @@ class KzgVerifier:
             pass
 
 
-class PrecompileWitness:
+class PrecompileWitness(_Witness):
     """Owner of a zkw_precompile_witness handle (keccak256 / sha256 / ecrecover round-function instances)."""
 
+    _PREFIX = "precompile"
     _DTYPES = {PRC_INSTANCES: PRECOMPILE_INSTANCE, PRC_KECCAK_ROUNDS: KECCAK_ROUND_RECORD, PRC_SHA256_ROUNDS: SHA256_ROUND_RECORD}
     _SHAPES = {PRC_MEM_ENC: (-1, 8), PRC_MEM_TAILS: (-1, 12)}
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
 
     @property
     def num_instances(self):
@@ -1100,77 +1034,28 @@ class PrecompileWitness:
     def num_rounds(self):
         return load().zkw_precompile_witness_num_rounds(self.handle)
 
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_precompile_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_precompile_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
 
-    def free(self):
-        if self.handle:
-            load().zkw_precompile_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-
-class DecommitterWitness:
+class DecommitterWitness(_Witness):
     """Owner of a zkw_decommitter_witness handle."""
 
+    _PREFIX = "decommitter"
     _DTYPES = {DCM_MEM_QUERIES: MEM_QUERY, DCM_INSTANCES: DECOMMITTER_INSTANCE, DCM_ROUND_STATES: np.dtype("<u4"),
                DCM_SHA256_ROUNDS: SHA256_ROUND_RECORD}
     _SHAPES = {DCM_MEM_ENC: (-1, 8), DCM_MEM_TAILS: (-1, 12), DCM_ROUND_STATES: (-1, 8)}
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
 
     @property
     def num_instances(self):
         return load().zkw_decommitter_witness_num_instances(self.handle)
 
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_decommitter_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_decommitter_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
 
-    def free(self):
-        if self.handle:
-            load().zkw_decommitter_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DecommitWitness:
+class DecommitWitness(_Witness):
     """Owner of a zkw_decommit_witness handle."""
 
+    _PREFIX = "decommit"
     _DTYPES = {DEC_SORTED_QUERIES: DECOMMIT_QUERY, DEC_DEDUP_QUERIES: DECOMMIT_QUERY, DEC_INSTANCES: DECOMMIT_INSTANCE}
     _SHAPES = {DEC_UNSORTED_ENC: (-1, 8), DEC_SORTED_ENC: (-1, 8), DEC_UNSORTED_TAILS: (-1, 12), DEC_SORTED_TAILS: (-1, 12),
                DEC_DEDUP_TAILS: (-1, 12), DEC_CHALLENGES: (2, 9), DEC_LHS_Z: (2, -1), DEC_RHS_Z: (2, -1),
                DEC_COMPACT_FORMS: (-1, 18), DEC_PUBLIC_INPUTS: (-1, 4)}
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.handle = C.c_void_p(None)
 
     @property
     def num_instances(self):
@@ -1179,27 +1064,6 @@ class DecommitWitness:
     @property
     def num_dedup(self):
         return load().zkw_decommit_witness_num_dedup(self.handle)
-
-    def get(self, what):
-        lib = load()
-        nbytes = lib.zkw_decommit_witness_bytes(self.handle, what)
-        dt = self._DTYPES.get(what, np.dtype("<u8"))
-        out = np.zeros(nbytes // dt.itemsize, dt)
-        if nbytes:
-            _check(lib.zkw_decommit_witness_get(self.handle, what, _np_ptr(out), nbytes))
-        shape = self._SHAPES.get(what)
-        return out.reshape(shape) if shape else out
-
-    def free(self):
-        if self.handle:
-            load().zkw_decommit_witness_free(self.handle)
-            self.handle = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 class RamWitness:
@@ -1928,7 +1792,6 @@ Context.synthesize_storage_sorter = _ctx_synthesize_storage_sorter
 Context.check_if_satisfied_storage_sorter = _ctx_check_if_satisfied_storage_sorter
 Context.check_if_satisfied_log_demux = _ctx_check_if_satisfied_log_demux
 Context.check_if_satisfied_events_sorter = _ctx_check_if_satisfied_events_sorter
-
 
 
 # ---- MainVM instance slicing (include/zkw_types.h: zkw_vm_instance & co) ------------------------------------------------

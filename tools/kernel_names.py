@@ -21,6 +21,9 @@ def short(name):
             break
     if not base:
         return n
+    c = re.match(r"INS_\d+([A-Z][a-z])CircuitEE", tail) if base == "k_sorter_fill_tail" else None
+    if c:  # the sorter circuits' shared tail (round 21), by the name each instantiation had as a kernel of its own: k_ds_fill_tail, ...
+        base = "k_" + c.group(1).lower() + "_fill_tail"
     t = re.match(r"I((?:Li\d+E)+)E", tail)
     targs = "<" + ", ".join(re.findall(r"Li(\d+)E", t.group(1))) + ">" if t else ""
     return "zkw::" + base + targs + (" [merged]" if m.group(1) == "multi" else "")
