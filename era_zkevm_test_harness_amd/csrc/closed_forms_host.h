@@ -9,10 +9,9 @@ template <class T>
 static int closed_form_public_inputs(zkw_ctx* ctx, const typename T::Inst* d_inst, size_t ni, u64** cf_pi) {
     if (!*cf_pi) HIP_TRY(dev_malloc((void**)cf_pi, ni * (COMPACT_FORM_LEN + 4) * sizeof(u64)));
     u64 *compact = *cf_pi, *pis = *cf_pi + COMPACT_FORM_LEN * ni;
-    { Prof _p(ctx, "k_closed_form_commitments"); ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<T>), "k_closed_form_commitments", (unsigned)ni, 64, d_inst, ni, compact); }
-    ZKW_TRY(launch_check("k_closed_form_commitments"));
-    { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, compact, ni, (u32)COMPACT_FORM_LEN, pis); }
-    return launch_check("k_commit_encodings");
+    ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<T>), "k_closed_form_commitments", (unsigned)ni, 64, d_inst, ni, compact);
+    ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, compact, ni, (u32)COMPACT_FORM_LEN, pis);
+    return ZKW_OK;
 }
 
 // a20 for the circuits whose builders keep no compact forms themselves (3, 5, 6, 7, 10, 13): commitments straight from
@@ -24,10 +23,8 @@ static int closed_form_from_records(zkw_ctx* ctx, const void* instances, size_t 
     u64 *d_cf = nullptr, *d_pi = nullptr;
     ZKW_TRY(ctx->out("cf_compact", reinterpret_cast<u64*>(compact), n * COMPACT_FORM_LEN, &d_cf));
     ZKW_TRY(ctx->out("cf_pi", reinterpret_cast<u64*>(public_inputs), n * 4, &d_pi));
-    { Prof _p(ctx, "k_closed_form_commitments"); ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<T>), "k_closed_form_commitments", (unsigned)n, 64, d_inst, n, d_cf); }
-    ZKW_TRY(launch_check("k_closed_form_commitments"));
-    { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n, 64), 64, d_cf, n, (u32)COMPACT_FORM_LEN, d_pi); }
-    ZKW_TRY(launch_check("k_commit_encodings"));
+    ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<T>), "k_closed_form_commitments", (unsigned)n, 64, d_inst, n, d_cf);
+    ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n, 64), 64, d_cf, n, (u32)COMPACT_FORM_LEN, d_pi);
     ZKW_TRY(ctx->finish_out(reinterpret_cast<u64*>(compact), d_cf, n * COMPACT_FORM_LEN));
     ZKW_TRY(ctx->finish_out(reinterpret_cast<u64*>(public_inputs), d_pi, n * 4));
     return ctx->sync_if_host();

@@ -270,16 +270,17 @@ static int radix_sort_pairs(zkw_ctx* ctx, void* tmp, size_t tmp_bytes, const K* 
     u32* chunk = hist + entries;
     const K* src_k = kin;
     const u32* src_v = vin;
+    const LaunchAt inner = no_span(ctx);  // the passes run under the caller's one "radix_sort" span
     for (unsigned pass = 0; pass < passes; pass++) {
         // the last pass must land in (kout, vout): passes alternate out, tmp, out, ... when their number is odd, tmp, out, ... when even
         const bool to_out = ((passes - pass) & 1) == 1;
         K* dst_k = to_out ? kout : tk;
         u32* dst_v = to_out ? vout : tv;
         const unsigned shift = 8 * pass, bits = std::min(8u, end_bit - shift), mask = (1u << bits) - 1;
-        ZKW_LAUNCH_T(ctx, (k_rs_hist<K>), "k_rs_hist", n_tiles, 256, src_k, n, shift, mask, hist, n_tiles);
-        ZKW_LAUNCH(ctx, k_rs_scan_a, n_chunks, 1024, hist, entries, chunk);
-        ZKW_LAUNCH(ctx, k_rs_scan_b, 1, 1024, chunk, n_chunks);
-        ZKW_LAUNCH_T(ctx, (k_rs_scatter<K>), "k_rs_scatter", n_tiles, 256, src_k, src_v, n, shift, mask, (const u32*)hist, (const u32*)chunk, n_tiles, dst_k, dst_v);
+        ZKW_LAUNCH_T(inner, (k_rs_hist<K>), "k_rs_hist", n_tiles, 256, src_k, n, shift, mask, hist, n_tiles);
+        ZKW_LAUNCH(inner, k_rs_scan_a, n_chunks, 1024, hist, entries, chunk);
+        ZKW_LAUNCH(inner, k_rs_scan_b, 1, 1024, chunk, n_chunks);
+        ZKW_LAUNCH_T(inner, (k_rs_scatter<K>), "k_rs_scatter", n_tiles, 256, src_k, src_v, n, shift, mask, (const u32*)hist, (const u32*)chunk, n_tiles, dst_k, dst_v);
         src_k = dst_k;
         src_v = dst_v;
     }
@@ -325,15 +326,16 @@ static int radix_sort_pairs_segmented(zkw_ctx* ctx, void* tmp, size_t tmp_bytes,
     u32* chunk = hist + entries;
     const K* src_k = kin;
     const u32* src_v = vin;
+    const LaunchAt inner = no_span(ctx);  // the passes run under the caller's one "radix_sort" span
     for (unsigned pass = 0; pass < passes; pass++) {
         const bool to_out = ((passes - pass) & 1) == 1;  // (as radix_sort_pairs)
         K* dst_k = to_out ? kout : tk;
         u32* dst_v = to_out ? vout : tv;
         const unsigned shift = 8 * pass, bits = std::min(8u, end_bit - shift), mask = (1u << bits) - 1;
-        ZKW_LAUNCH_T(ctx, (k_rs_hist_seg<K>), "k_rs_hist_seg", n_tiles, 256, src_k, d_segs, n_segs, shift, mask, hist);
-        ZKW_LAUNCH(ctx, k_rs_scan_a, n_chunks, 1024, hist, entries, chunk);
-        ZKW_LAUNCH(ctx, k_rs_scan_b, 1, 1024, chunk, n_chunks);
-        ZKW_LAUNCH_T(ctx, (k_rs_scatter_seg<K>), "k_rs_scatter_seg", n_tiles, 256, src_k, src_v, d_segs, n_segs, shift, mask, (const u32*)hist, (const u32*)chunk, dst_k, dst_v);
+        ZKW_LAUNCH_T(inner, (k_rs_hist_seg<K>), "k_rs_hist_seg", n_tiles, 256, src_k, d_segs, n_segs, shift, mask, hist);
+        ZKW_LAUNCH(inner, k_rs_scan_a, n_chunks, 1024, hist, entries, chunk);
+        ZKW_LAUNCH(inner, k_rs_scan_b, 1, 1024, chunk, n_chunks);
+        ZKW_LAUNCH_T(inner, (k_rs_scatter_seg<K>), "k_rs_scatter_seg", n_tiles, 256, src_k, src_v, d_segs, n_segs, shift, mask, (const u32*)hist, (const u32*)chunk, dst_k, dst_v);
         src_k = dst_k;
         src_v = dst_v;
     }

@@ -62,13 +62,10 @@ static int flag_prefix(zkw_ctx* ctx, const char* name, Flag flag, size_t n, u32*
     const unsigned n_tiles = (unsigned)((n + FLAG_PREFIX_TILE - 1) / FLAG_PREFIX_TILE);
     u32* d_tiles = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("flag_prefix_tiles", n_tiles, &d_tiles));
-    { Prof _p(ctx, name); ZKW_LAUNCH_T(ctx, (k_flag_prefix_tiles<Flag>), "k_flag_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, flag, n, d_prefix, d_tiles); }
-    ZKW_TRY(launch_check(name));
+    ZKW_LAUNCH_T(span_as(ctx, name), (k_flag_prefix_tiles<Flag>), "k_flag_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, flag, n, d_prefix, d_tiles);
     if (n_tiles > 1) {
-        ZKW_LAUNCH(ctx, k_flag_prefix_offsets, 1, 1024, d_tiles, n_tiles);
-        ZKW_TRY(launch_check("k_flag_prefix_offsets"));
-        ZKW_LAUNCH(ctx, k_flag_prefix_apply, (unsigned)((n + 255) / 256), 256, d_prefix, d_tiles, n);
-        ZKW_TRY(launch_check("k_flag_prefix_apply"));
+        ZKW_LAUNCH(no_span(ctx), k_flag_prefix_offsets, 1, 1024, d_tiles, n_tiles);
+        ZKW_LAUNCH(no_span(ctx), k_flag_prefix_apply, (unsigned)((n + 255) / 256), 256, d_prefix, d_tiles, n);
     }
     return ZKW_OK;
 }
@@ -110,13 +107,10 @@ static int route_prefix(zkw_ctx* ctx, const char* name, Route route, size_t n, u
     const unsigned n_tiles = (unsigned)((n + FLAG_PREFIX_TILE - 1) / FLAG_PREFIX_TILE);
     u32* d_tiles = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("route_prefix_tiles", (size_t)K * n_tiles, &d_tiles));
-    { Prof _p(ctx, name); ZKW_LAUNCH_T(ctx, (k_route_prefix_tiles<K, Route>), "k_route_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, route, n, d_count, d_tiles); }
-    ZKW_TRY(launch_check(name));
+    ZKW_LAUNCH_T(span_as(ctx, name), (k_route_prefix_tiles<K, Route>), "k_route_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, route, n, d_count, d_tiles);
     if (n_tiles > 1) {
-        for (int c = 0; c < K; c++) ZKW_LAUNCH(ctx, k_flag_prefix_offsets, 1, 1024, d_tiles + (size_t)c * n_tiles, n_tiles);
-        ZKW_TRY(launch_check("k_flag_prefix_offsets"));
-        ZKW_LAUNCH_T(ctx, (k_route_prefix_apply<K>), "k_route_prefix_apply", (unsigned)((n + 255) / 256), 256, d_count, d_tiles, n, n_tiles);
-        ZKW_TRY(launch_check("k_route_prefix_apply"));
+        for (int c = 0; c < K; c++) ZKW_LAUNCH(no_span(ctx), k_flag_prefix_offsets, 1, 1024, d_tiles + (size_t)c * n_tiles, n_tiles);
+        ZKW_LAUNCH_T(no_span(ctx), (k_route_prefix_apply<K>), "k_route_prefix_apply", (unsigned)((n + 255) / 256), 256, d_count, d_tiles, n, n_tiles);
     }
     return ZKW_OK;
 }
@@ -191,16 +185,9 @@ static int sum_prefix(zkw_ctx* ctx, const char* name, Val val, size_t n, u64* d_
     const unsigned n_tiles = (unsigned)((n + FLAG_PREFIX_TILE - 1) / FLAG_PREFIX_TILE);
     u64* d_tiles = nullptr;
     ZKW_TRY(ctx->scratch_t<u64>("sum_prefix_tiles", (size_t)K * (n_tiles ? n_tiles : 1), &d_tiles));
-    if (n) {
-        { Prof _p(ctx, name); ZKW_LAUNCH_T(ctx, (k_sum_prefix_tiles<K, Val>), "k_sum_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, val, n, d_out, d_tiles); }
-        ZKW_TRY(launch_check(name));
-    }
-    for (int c = 0; c < K; c++) ZKW_LAUNCH(ctx, k_sum_prefix_offsets, 1, 1024, d_tiles + (size_t)c * n_tiles, n_tiles, d_totals + c, d_out + (size_t)c * (n + 1) + n);
-    ZKW_TRY(launch_check("k_sum_prefix_offsets"));
-    if (n_tiles > 1) {
-        ZKW_LAUNCH_T(ctx, (k_sum_prefix_apply<K>), "k_sum_prefix_apply", (unsigned)((n + 255) / 256), 256, d_out, d_tiles, n, n_tiles);
-        ZKW_TRY(launch_check("k_sum_prefix_apply"));
-    }
+    if (n) ZKW_LAUNCH_T(span_as(ctx, name), (k_sum_prefix_tiles<K, Val>), "k_sum_prefix_tiles", n_tiles, FLAG_PREFIX_TILE, val, n, d_out, d_tiles);
+    for (int c = 0; c < K; c++) ZKW_LAUNCH(no_span(ctx), k_sum_prefix_offsets, 1, 1024, d_tiles + (size_t)c * n_tiles, n_tiles, d_totals + c, d_out + (size_t)c * (n + 1) + n);
+    if (n_tiles > 1) ZKW_LAUNCH_T(no_span(ctx), (k_sum_prefix_apply<K>), "k_sum_prefix_apply", (unsigned)((n + 255) / 256), 256, d_out, d_tiles, n, n_tiles);
     return ZKW_OK;
 }
 

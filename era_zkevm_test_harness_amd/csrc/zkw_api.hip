@@ -771,8 +771,8 @@ int dev_encode(zkw_ctx* ctx, const zkw_mem_query* q, size_t n, u64* enc) {
     if (n == 0) return ZKW_OK;
     unsigned grid = blocks_for(n, 256);
     if (grid > 256 * 16) grid = 256 * 16;
-    { Prof _p(ctx, "k_encode_mem"); ZKW_LAUNCH(ctx, k_encode_mem, grid, 256, q, n, enc); }
-    return launch_check("k_encode_mem");
+    ZKW_LAUNCH(ctx, k_encode_mem, grid, 256, q, n, enc);
+    return ZKW_OK;
 }
 
 // Chains: one chain per 16-lane DPP row, 4 chains per wave, one wave per block. A single wave already
@@ -828,19 +828,17 @@ int dev_fs(zkw_ctx* ctx, const std::vector<FsJob>& jobs, int state_w, int n_chal
     FsJob* d_jobs = nullptr;
     ZKW_TRY(ctx->upload("fs_jobs", jobs, &d_jobs));
     int n = (int)jobs.size();
-    { Prof _p(ctx, "k_fs_challenges"); ZKW_LAUNCH(ctx, k_fs_challenges, (n + 63) / 64, 64, d_jobs, n, state_w, n_chal); }
-    return launch_check("k_fs_challenges");
+    ZKW_LAUNCH(ctx, k_fs_challenges, (n + 63) / 64, 64, d_jobs, n, state_w, n_chal);
+    return ZKW_OK;
 }
 
 template <int W, int REPS>
 static int gp_launch(zkw_ctx* ctx, const GpSeg* d_segs, int n_segs, const GpTile* d_tiles, unsigned n_tiles,
                      u64* d_aggr) {
-    { Prof _p(ctx, "k_gp_local"); ZKW_LAUNCH_T(ctx, (k_gp_local<W, REPS>), "k_gp_local", n_tiles, GP_BLOCK, d_segs, d_tiles, d_aggr); }
-    ZKW_TRY(launch_check("k_gp_local"));
-    { Prof _p(ctx, "k_gp_tiles"); ZKW_LAUNCH_T(ctx, (k_gp_tiles<REPS>), "k_gp_tiles", (n_segs * REPS + 63) / 64, 64, d_segs, n_segs, d_aggr); }
-    ZKW_TRY(launch_check("k_gp_tiles"));
-    { Prof _p(ctx, "k_gp_apply"); ZKW_LAUNCH_T(ctx, (k_gp_apply<REPS>), "k_gp_apply", n_tiles, GP_BLOCK, d_segs, d_tiles, d_aggr); }
-    return launch_check("k_gp_apply");
+    ZKW_LAUNCH_T(ctx, (k_gp_local<W, REPS>), "k_gp_local", n_tiles, GP_BLOCK, d_segs, d_tiles, d_aggr);
+    ZKW_LAUNCH_T(ctx, (k_gp_tiles<REPS>), "k_gp_tiles", (n_segs * REPS + 63) / 64, 64, d_segs, n_segs, d_aggr);
+    ZKW_LAUNCH_T(ctx, (k_gp_apply<REPS>), "k_gp_apply", n_tiles, GP_BLOCK, d_segs, d_tiles, d_aggr);
+    return ZKW_OK;
 }
 
 // segs: rows/z/chal/n filled by the caller; first_tile/n_tiles filled here
@@ -972,8 +970,7 @@ extern "C" int zkw_encode_log_queries(zkw_ctx* ctx, const zkw_log_query* q, size
     ZKW_TRY(ctx->in("lenc_q", q, n, &d_q));
     if (ext_ts) ZKW_TRY(ctx->in("lenc_ts", ext_ts, n, &d_e));
     ZKW_TRY(ctx->out("lenc_out", enc, n * 20, &d_enc));
-    { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, blocks_for(n, 256), 256, d_q, n, d_e, d_enc); }
-    ZKW_TRY(launch_check("k_encode_log"));
+    ZKW_LAUNCH(ctx, k_encode_log, blocks_for(n, 256), 256, d_q, n, d_e, d_enc);
     ZKW_TRY(ctx->finish_out(enc, d_enc, n * 20));
     return ctx->sync_if_host();
 }
@@ -986,8 +983,7 @@ extern "C" int zkw_encode_decommit_queries(zkw_ctx* ctx, const zkw_decommit_quer
     u64* d_enc = nullptr;
     ZKW_TRY(ctx->in("denc_q", q, n, &d_q));
     ZKW_TRY(ctx->out("denc_out", enc, n * 8, &d_enc));
-    { Prof _p(ctx, "k_encode_decommit"); ZKW_LAUNCH(ctx, k_encode_decommit, blocks_for(n, 256), 256, d_q, n, d_enc); }
-    ZKW_TRY(launch_check("k_encode_decommit"));
+    ZKW_LAUNCH(ctx, k_encode_decommit, blocks_for(n, 256), 256, d_q, n, d_enc);
     ZKW_TRY(ctx->finish_out(enc, d_enc, n * 8));
     return ctx->sync_if_host();
 }
@@ -998,16 +994,15 @@ int dev_log_chains(zkw_ctx* ctx, const u64* d_enc, size_t total, std::vector<Log
     if (total == 0 || jobs.empty()) { if (ctx->chain_service && !ctx->batched()) chain_service_of(ctx->device)->skip(key); return ZKW_OK; }
     u64* d_pre = nullptr;
     ZKW_TRY(ctx->scratch_t<u64>("log_pre", total * 4, &d_pre));
-    { Prof _p(ctx, "k_log_prehash"); ZKW_LAUNCH(ctx, k_log_prehash, blocks_for(total, 128), 128, d_enc, total, d_pre); }
-    ZKW_TRY(launch_check("k_log_prehash"));
+    ZKW_LAUNCH(ctx, k_log_prehash, blocks_for(total, 128), 128, d_enc, total, d_pre);
     for (auto& j : jobs) j.pre = d_pre + (j.enc - d_enc) / 20 * 4;
     if (ctx->batched()) return zkw_batch_chains(ctx->batch, nullptr, 0, jobs.data(), jobs.size());
     if (ctx->chain_service) return chain_service_run(ctx, nullptr, &jobs, "k_chain_log", key);
     LogChainJob* d_jobs = nullptr;
     ZKW_TRY(ctx->upload("log_chain_jobs", jobs, &d_jobs));
     const int n_jobs = (int)jobs.size();
-    { Prof _p(ctx, "k_chain_log"); hipLaunchKernelGGL(k_chain_log, dim3((n_jobs + 3) / 4), dim3(64), 0, ctx->stream, d_jobs, n_jobs); }
-    return launch_check("k_chain_log");
+    ZKW_TRY(launch_direct(ctx, "k_chain_log", k_chain_log, dim3((n_jobs + 3) / 4), dim3(64), 0, d_jobs, n_jobs));
+    return ZKW_OK;
 }
 
 extern "C" int zkw_queue_push_chain_log_batch(zkw_ctx* ctx, const uint64_t* enc, const uint64_t* offsets,
@@ -1217,10 +1212,7 @@ static int ram_sort(zkw_ctx* ctx, const zkw_mem_query* d_q, size_t total, const 
     ZKW_TRY(ctx->scratch("sort_max", 256, &d_max_v));
     u32* d_max = static_cast<u32*>(d_max_v);
     HIP_TRY(ctx->memset_async(d_max, 0, 16));
-    { Prof _p(ctx, "k_ram_key_ranges");
-      const unsigned g = grid < 4096 ? grid : 4096;
-      ZKW_LAUNCH(ctx, k_ram_key_ranges, g, 256, d_q, total, d_max); }
-    ZKW_TRY(launch_check("k_ram_key_ranges"));
+    ZKW_LAUNCH(ctx, k_ram_key_ranges, grid < 4096 ? grid : 4096, 256, d_q, total, d_max);
     u32 maxima[4];
     ZKW_TRY(ctx->read_small(maxima, d_max, 16));
     const unsigned bits_t = bits_in_use(maxima[0]), bits_p = bits_in_use(maxima[1]), bits_i = bits_in_use(maxima[2]);
@@ -1231,25 +1223,21 @@ static int ram_sort(zkw_ctx* ctx, const zkw_mem_query* d_q, size_t total, const 
 
     if (bits_p + bits_i + bits_t <= 64) {
         const unsigned bits = bits_p + bits_i + bits_t;
-        { Prof _p(ctx, "k_ram_packed_keys"); ZKW_LAUNCH(ctx, k_ram_packed_keys, grid, 256, d_q, total, bits_i, bits_t, k64a, v0); }
-        ZKW_TRY(launch_check("k_ram_packed_keys"));
+        ZKW_LAUNCH(ctx, k_ram_packed_keys, grid, 256, d_q, total, bits_i, bits_t, k64a, v0);
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v0, v1, total, d_segs, n_segs, n_tiles, bits)); }
         *perm_out = v1;
         return ZKW_OK;
     }
 
-    { Prof _p(ctx, "k_ram_sort_keys"); ZKW_LAUNCH(ctx, k_ram_sort_keys, grid, 256, d_q, total, ts, cell, v0, (const u64*)nullptr, 0); }
-    ZKW_TRY(launch_check("k_ram_sort_keys"));
+    ZKW_LAUNCH(ctx, k_ram_sort_keys, grid, 256, d_q, total, ts, cell, v0, (const u64*)nullptr, 0);
     // pass 1: timestamp
     { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u32>(ctx, tmp, tmp_bytes, ts, k32, v0, v1, total, d_segs, n_segs, n_tiles, bits_t)); }
     // pass 2: the cell of the ts-sorted items, packed where that saves a digit
     const unsigned bits = bits_p + bits_i;
     if (bits < 64) {
-        { Prof _p(ctx, "k_ram_packed_cells"); ZKW_LAUNCH(ctx, k_ram_packed_cells, grid, 256, cell, v1, total, bits_i, k64a); }
-        ZKW_TRY(launch_check("k_ram_packed_cells"));
+        ZKW_LAUNCH(ctx, k_ram_packed_cells, grid, 256, cell, v1, total, bits_i, k64a);
     } else {
-        { Prof _p(ctx, "k_gather_u64_by_u32"); ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, cell, v1, total, k64a); }
-        ZKW_TRY(launch_check("k_gather_u64_by_u32"));
+        ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, cell, v1, total, k64a);
     }
     { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs_segmented<u64>(ctx, tmp, tmp_bytes, k64a, k64b, v1, v0, total, d_segs, n_segs, n_tiles, bits)); }
     *perm_out = v0;
@@ -1338,20 +1326,16 @@ static int ram_run(zkw_ctx* ctx, zkw_ram_witness* w, const zkw_mem_query* d_q, c
         ZKW_TRY(ctx->upload("ram_blocks", blocks, &d_blocks));
         const unsigned gy = (unsigned)(b1 - b0);
         if (max_inst * nd_tiles >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "ram_run: more than 2^31 - 1 tiles of 256 cycles in one block");
-        { Prof _p(ctx, "k_ram_gp_groups"); ZKW_LAUNCH_2D(ctx, k_ram_gp_groups, max_inst * nd_tiles, gy, 256, d_blocks); }
-        ZKW_TRY(launch_check("k_ram_gp_groups"));
-        { Prof _p(ctx, "k_ram_gp_scan"); ZKW_LAUNCH_2D(ctx, k_ram_gp_scan, 1, gy, 256, d_blocks); }
-        ZKW_TRY(launch_check("k_ram_gp_scan"));
-        { Prof _p(ctx, "k_ram_instances"); ZKW_LAUNCH_2D(ctx, k_ram_instances, blocks_for(max_inst, 64), gy, 64, d_blocks); }
-        ZKW_TRY(launch_check("k_ram_instances"));
+        ZKW_LAUNCH_2D(ctx, k_ram_gp_groups, max_inst * nd_tiles, gy, 256, d_blocks);
+        ZKW_LAUNCH_2D(ctx, k_ram_gp_scan, 1, gy, 256, d_blocks);
+        ZKW_LAUNCH_2D(ctx, k_ram_instances, blocks_for(max_inst, 64), gy, 64, d_blocks);
         b0 = b1;
     }
     // a20: compact forms and public inputs of every instance (postprocessing/mod.rs:353-369)
     const size_t ni = w->n_instances;
-    { Prof _p(ctx, "k_ram_commitments"); ZKW_LAUNCH(ctx, k_ram_commitments, blocks_for(4 * ni, 64), 64, w->instances, ni, w->compact_forms); }
-    ZKW_TRY(launch_check("k_ram_commitments"));
-    { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, w->compact_forms, ni, (u32)COMPACT_FORM_LEN, w->public_inputs); }
-    return launch_check("k_commit_encodings");
+    ZKW_LAUNCH(ctx, k_ram_commitments, blocks_for(4 * ni, 64), 64, w->instances, ni, w->compact_forms);
+    ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, w->compact_forms, ni, (u32)COMPACT_FORM_LEN, w->public_inputs);
+    return ZKW_OK;
 }
 
 extern "C" int zkw_ram_build_instances_batch(zkw_ctx* ctx, const zkw_mem_query* q, const uint64_t* block_offsets,
@@ -1426,8 +1410,7 @@ static int ram_sorted_queries(const zkw_ram_witness* cw) {
     const size_t t = w->total;
     if (!w->sorted_q && dev_malloc((void**)&w->sorted_q, (t + 1) * sizeof(zkw_mem_query)) != hipSuccess)
         return fail(ZKW_ERR_OOM, "no room for the sorted queries (%zu bytes): read ZKW_RAM_SORTED_QUERIES from a smaller batch", t * sizeof(zkw_mem_query));
-    { Prof _p(ctx, "k_gather_encode"); ZKW_LAUNCH(ctx, k_gather_encode, blocks_for(t, 256), 256, w->unsorted_q, w->perm, t, w->sorted_q, (u64*)nullptr); }
-    ZKW_TRY(launch_check("k_gather_encode"));
+    ZKW_LAUNCH(ctx, k_gather_encode, blocks_for(t, 256), 256, w->unsorted_q, w->perm, t, w->sorted_q, (u64*)nullptr);
     w->sorted_valid = true;
     return ZKW_OK;
 }
@@ -1482,10 +1465,8 @@ static int ram_full_tails(const zkw_ram_witness* cw) {
     u64* d_off = nullptr;
     ZKW_TRY(ctx->upload("tails_off", w->offsets, &d_off));
     const int nq = (int)(w->offsets.size() - 1);
-    { Prof _p(ctx, "k_tails_expand"); ZKW_LAUNCH(ctx, k_tails_expand, blocks_for(t, 64), 64, w->unsorted_enc, w->unsorted_caps, d_off, nq, t, w->unsorted_tails); }
-    ZKW_TRY(launch_check("k_tails_expand"));
-    { Prof _p(ctx, "k_tails_expand"); ZKW_LAUNCH(ctx, k_tails_expand, blocks_for(t, 64), 64, w->sorted_enc, w->sorted_caps, d_off, nq, t, w->sorted_tails); }
-    ZKW_TRY(launch_check("k_tails_expand"));
+    ZKW_LAUNCH(ctx, k_tails_expand, blocks_for(t, 64), 64, w->unsorted_enc, w->unsorted_caps, d_off, nq, t, w->unsorted_tails);
+    ZKW_LAUNCH(ctx, k_tails_expand, blocks_for(t, 64), 64, w->sorted_enc, w->sorted_caps, d_off, nq, t, w->sorted_tails);
     w->tails_valid = true;
     return ZKW_OK;
 }
@@ -1638,10 +1619,8 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     const size_t z_base = w->offsets[b_first];
     {   // the fills read the sorted queue contiguously: gather the touched blocks once per call
         const size_t cnt = w->offsets[b_end] - z_base;
-        Prof _p(ctx, "k_gather_encode");
         ZKW_LAUNCH(ctx, k_gather_encode, blocks_for(cnt, 256), 256, w->unsorted_q, w->perm + z_base, cnt, w->sq_win, (u64*)nullptr);
     }
-    ZKW_TRY(launch_check("k_gather_encode"));
     const u32 rstride = (u32)RC_REGION_STRIDE(capacity);  // rows per region incl. the alignment gap
     const u32 n_tiles = (rstride + 255) / 256;             // (= ram_nd_tiles(capacity): the stride rounds up to 64)
     u32* d_hist = nullptr;
@@ -1695,26 +1674,27 @@ extern "C" int zkw_ram_synthesize(zkw_ctx* ctx, const zkw_ram_witness* w, size_t
     } else {
         for (size_t k = n_instances; k < (size_t)RC_INLINE_JOBS; k++) tab.j[k] = tab.j[0];  // (never indexed: the grids cover n_instances jobs)
     }
-    // one body, the job table either way (a launch of its own with the table in its arguments is never left with a batch)
-#define SYNTH_LAUNCH(kernel, name, grid, bs, ...)                                                                                  \
+    // one body, the job table either way (a launch of its own with the table in its arguments is never left with a batch); one span over the two
+#define SYNTH_LAUNCH(kernel, weight, grid, bs, ...)                                                                                \
     do {                                                                                                                           \
+        Prof _p(ctx, #kernel, weight);                                                                                             \
         if (inline_jobs) {                                                                                                         \
             LaunchSig<decltype(&kernel<SynthJobsInline>)>::template single<&kernel<SynthJobsInline>, bs>(ctx->stream, grid, 0, tab, __VA_ARGS__); \
-            ZKW_TRY(launch_check(name));                                                                                           \
+            ZKW_TRY(launch_check(#kernel));                                                                                        \
         } else {                                                                                                                   \
-            ZKW_LAUNCH_D(ctx, (kernel<SynthJobsRef>), name, grid, bs, 0, ref, __VA_ARGS__);                                        \
+            ZKW_LAUNCH_D(no_span(ctx), (kernel<SynthJobsRef>), #kernel, grid, bs, 0, ref, __VA_ARGS__);                            \
         }                                                                                                                          \
     } while (0)
     const unsigned nj = (unsigned)n_instances;
     const dim3 g64x2((rstride + 63) / 64, nj, 2), g256(n_tiles, nj);
     // row C needs nothing but the gathered window (its counter's tile prefixes are the builder's); the boundary rows read its last row
-    { Prof _p(ctx, "k_ram_fill_C"); SYNTH_LAUNCH(k_ram_fill_C, "k_ram_fill_C", g256, 256, capacity, n_rows); }
+    SYNTH_LAUNCH(k_ram_fill_C, 1, g256, 256, capacity, n_rows);
     // grid z = 0 fills the PU rows and row A, z = 1 the PS rows and row B (one lane per cycle writes both): one launch, two in the profile
-    { Prof _p(ctx, "k_ram_fill_poseidon", 2); SYNTH_LAUNCH(k_ram_fill_poseidon, "k_ram_fill_poseidon", g64x2, 64, capacity, n_rows); }
-    { Prof _p(ctx, "k_ram_fill_D"); const unsigned d_tiles = (unsigned)((rstride + RC_D_TILES * 256 - 1) / (RC_D_TILES * 256));  // row D: RC_D_TILES tiles per block (they share one inversion per lane)
-      SYNTH_LAUNCH(k_ram_fill_D, "k_ram_fill_D", dim3(nj * (d_tiles + 1)), 256, nj, d_tiles, capacity, n_rows); }
+    SYNTH_LAUNCH(k_ram_fill_poseidon, 2, g64x2, 64, capacity, n_rows);
+    const unsigned d_tiles = (unsigned)((rstride + RC_D_TILES * 256 - 1) / (RC_D_TILES * 256));  // row D: RC_D_TILES tiles per block (they share one inversion per lane)
+    SYNTH_LAUNCH(k_ram_fill_D, 1, dim3(nj * (d_tiles + 1)), 256, nj, d_tiles, capacity, n_rows);
     ctx->synth_hist_dirty = false;  // row D's boundary blocks leave the histograms zero
-    if (!all_clean) { Prof _p(ctx, "k_ram_fill_tail"); SYNTH_LAUNCH(k_ram_fill_tail, "k_ram_fill_tail", dim3(nj * ((RC_G + RC_L + 1) * TAIL_CHUNKS)), 256, capacity, n_rows); }
+    if (!all_clean) SYNTH_LAUNCH(k_ram_fill_tail, 1, dim3(nj * ((RC_G + RC_L + 1) * TAIL_CHUNKS)), 256, capacity, n_rows);
 #undef SYNTH_LAUNCH
     return claims.commit_if(ctx->sync_if_host());
 }
@@ -1758,8 +1738,7 @@ extern "C" int zkw_commit_encodings(zkw_ctx* ctx, const uint64_t* enc, size_t n_
     u64* d_out = nullptr;
     ZKW_TRY(ctx->in("ce_enc", enc, n_items * item_len + 1, &d_enc));
     ZKW_TRY(ctx->out("ce_out", out, n_items * 4, &d_out));
-    { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n_items, 64), 64, d_enc, n_items, item_len, d_out); }
-    ZKW_TRY(launch_check("k_commit_encodings"));
+    ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n_items, 64), 64, d_enc, n_items, item_len, d_out);
     ZKW_TRY(ctx->finish_out(out, d_out, n_items * 4));
     return ctx->sync_if_host();
 }
@@ -1773,8 +1752,7 @@ extern "C" int zkw_encode_recursion_requests(zkw_ctx* ctx, uint64_t circuit_type
     u64* d_enc = nullptr;
     ZKW_TRY(ctx->in("rr_pi", public_inputs, n * 4, &d_pi));
     ZKW_TRY(ctx->out("rr_enc", enc, n * 8, &d_enc));
-    { Prof _p(ctx, "k_encode_recursion"); ZKW_LAUNCH(ctx, k_encode_recursion, blocks_for(n, 64), 64, circuit_type, d_pi, n, d_enc); }
-    ZKW_TRY(launch_check("k_encode_recursion"));
+    ZKW_LAUNCH(ctx, k_encode_recursion, blocks_for(n, 64), 64, circuit_type, d_pi, n, d_enc);
     ZKW_TRY(ctx->finish_out(enc, d_enc, n * 8));
     return ctx->sync_if_host();
 }
@@ -1788,8 +1766,7 @@ extern "C" int zkw_encode_callstack_entries(zkw_ctx* ctx, const zkw_callstack_en
     u64* d_enc = nullptr;
     ZKW_TRY(ctx->in("cs_e", entries, n, &d_e));
     ZKW_TRY(ctx->out("cs_enc", enc, n * 32, &d_enc));
-    { Prof _p(ctx, "k_encode_callstack"); hipLaunchKernelGGL(k_encode_callstack, dim3(blocks_for(n, 64)), dim3(64), 0, ctx->stream, d_e, n, d_enc); }
-    ZKW_TRY(launch_check("k_encode_callstack"));
+    ZKW_TRY(launch_direct(ctx, "k_encode_callstack", k_encode_callstack, dim3(blocks_for(n, 64)), dim3(64), 0, d_e, n, d_enc));
     ZKW_TRY(ctx->finish_out(enc, d_enc, n * 32));
     return ctx->sync_if_host();
 }
@@ -1827,8 +1804,7 @@ extern "C" int zkw_callstack_simulate(zkw_ctx* ctx, const uint8_t* is_push, size
     ZKW_TRY(ctx->scratch_t<u64>("st_totals", 2, &d_totals));
     HIP_TRY(ctx->memset_async(d_meta, 0, 4 * sizeof(u32)));
     ZKW_TRY((sum_prefix<2>(ctx, "k_stack_prefix", StackDelta{d_ops}, n_ops, d_prefix, d_totals)));
-    { Prof _p(ctx, "k_stack_depth"); hipLaunchKernelGGL(k_stack_depth, dim3(blocks_for(n_ops, 256)), dim3(256), 0, ctx->stream, d_ops, n_ops, d_prefix, d_depth, d_rank, d_meta); }
-    ZKW_TRY(launch_check("k_stack_depth"));
+    ZKW_TRY(launch_direct(ctx, "k_stack_depth", k_stack_depth, dim3(blocks_for(n_ops, 256)), dim3(256), 0, d_ops, n_ops, d_prefix, d_depth, d_rank, d_meta));
     u32 meta[3];
     ZKW_TRY(ctx->read_small(meta, d_meta, sizeof meta));
     if (meta[2]) return fail(ZKW_ERR_INVALID, "pop from the empty callstack (circuit_encodings/src/lib.rs:619)");
@@ -1836,19 +1812,14 @@ extern "C" int zkw_callstack_simulate(zkw_ctx* ctx, const uint8_t* is_push, size
     if (n_push > n_pushed) return fail(ZKW_ERR_INVALID, "%u pushes but only %zu entries", n_push, n_pushed);
     const unsigned grid = blocks_for(n_ops, 256);
     if (n_push) {
-        { Prof _p(ctx, "k_stack_push_keys"); hipLaunchKernelGGL(k_stack_push_keys, dim3(grid), dim3(256), 0, ctx->stream, d_ops, n_ops, d_depth, d_rank, d_pd, d_pid); }
-        ZKW_TRY(launch_check("k_stack_push_keys"));
+        ZKW_TRY(launch_direct(ctx, "k_stack_push_keys", k_stack_push_keys, dim3(grid), dim3(256), 0, d_ops, n_ops, d_depth, d_rank, d_pd, d_pid));
         unsigned bits = 1;
         while ((1ull << bits) <= max_depth) bits++;
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u32>(ctx, tmp, tmp_bytes, d_pd, d_sd, d_pid, d_sid, n_push, bits)); }
     }
-    { Prof _p(ctx, "k_stack_links"); hipLaunchKernelGGL(k_stack_links, dim3(grid), dim3(256), 0, ctx->stream, d_ops, n_ops, d_depth, d_rank, d_sd, d_sid, d_meta, d_parent, d_node); }
-    ZKW_TRY(launch_check("k_stack_links"));
-    for (u32 d = 1; d <= max_depth; d++) {
-        Prof _p(ctx, "k_stack_level");
-        hipLaunchKernelGGL(k_stack_level, dim3(blocks_for(n_push, 64)), dim3(64), 0, ctx->stream, d_e, d_pd, d_parent, d_meta, d, d_rounds);
-    }
-    ZKW_TRY(launch_check("k_stack_level"));
+    ZKW_TRY(launch_direct(ctx, "k_stack_links", k_stack_links, dim3(grid), dim3(256), 0, d_ops, n_ops, d_depth, d_rank, d_sd, d_sid, d_meta, d_parent, d_node));
+    for (u32 d = 1; d <= max_depth; d++)
+        ZKW_TRY(launch_direct(ctx, "k_stack_level", k_stack_level, dim3(blocks_for(n_push, 64)), dim3(64), 0, d_e, d_pd, d_parent, d_meta, d, d_rounds));
     u64 *d_prev = nullptr, *d_new = nullptr, *d_rs = nullptr;
     u32 *d_dep = nullptr, *d_idx = nullptr;
     ZKW_TRY(ctx->out("st_o_prev", previous_state, n_ops * 12, &d_prev));
@@ -1856,8 +1827,7 @@ extern "C" int zkw_callstack_simulate(zkw_ctx* ctx, const uint8_t* is_push, size
     ZKW_TRY(ctx->out("st_o_rs", round_states, n_ops * 48, &d_rs));
     ZKW_TRY(ctx->out("st_o_dep", depth, n_ops, &d_dep));
     ZKW_TRY(ctx->out("st_o_idx", entry_index, n_ops, &d_idx));
-    { Prof _p(ctx, "k_stack_emit"); hipLaunchKernelGGL(k_stack_emit, dim3(grid), dim3(256), 0, ctx->stream, d_ops, n_ops, d_depth, d_parent, d_node, d_rounds, d_meta, d_prev, d_new, d_dep, d_rs, d_idx); }
-    ZKW_TRY(launch_check("k_stack_emit"));
+    ZKW_TRY(launch_direct(ctx, "k_stack_emit", k_stack_emit, dim3(grid), dim3(256), 0, d_ops, n_ops, d_depth, d_parent, d_node, d_rounds, d_meta, d_prev, d_new, d_dep, d_rs, d_idx));
     ZKW_TRY(ctx->finish_out(previous_state, d_prev, n_ops * 12));
     ZKW_TRY(ctx->finish_out(new_state, d_new, n_ops * 12));
     ZKW_TRY(ctx->finish_out(round_states, d_rs, n_ops * 48));
@@ -1905,16 +1875,12 @@ extern "C" int zkw_vm_slice_instances(zkw_ctx* ctx, const zkw_vm_tracer_streams*
         ZKW_TRY(ctx->out("vm_ri", memory_read_index, n_mem, &d_ri));
         ZKW_TRY(ctx->out("vm_wi", memory_write_index, n_mem, &d_wi));
     }
-    { Prof _p(ctx, "k_vm_rw_tile_counts"); ZKW_LAUNCH(ctx, k_vm_rw_tile_counts, n_tiles, 256, job.s.vm_memory_queries, (u64)n_mem, d_tiles); }
-    ZKW_TRY(launch_check("k_vm_rw_tile_counts"));
-    { Prof _p(ctx, "k_vm_rw_scan_tiles"); ZKW_LAUNCH(ctx, k_vm_rw_scan_tiles, 1, 1024, d_tiles, n_tiles, d_total); }
-    ZKW_TRY(launch_check("k_vm_rw_scan_tiles"));
-    { Prof _p(ctx, "k_vm_rw_scatter"); ZKW_LAUNCH(ctx, k_vm_rw_scatter, n_tiles, 256, job.s.vm_memory_queries, (u64)n_mem, d_tiles, d_prefix, d_ri, d_wi); }
-    ZKW_TRY(launch_check("k_vm_rw_scatter"));
+    ZKW_LAUNCH(ctx, k_vm_rw_tile_counts, n_tiles, 256, job.s.vm_memory_queries, (u64)n_mem, d_tiles);
+    ZKW_LAUNCH(ctx, k_vm_rw_scan_tiles, 1, 1024, d_tiles, n_tiles, d_total);
+    ZKW_LAUNCH(ctx, k_vm_rw_scatter, n_tiles, 256, job.s.vm_memory_queries, (u64)n_mem, d_tiles, d_prefix, d_ri, d_wi);
     job.read_prefix = d_prefix;
     ZKW_TRY(ctx->out("vm_inst", instances, n_inst, &job.out));
-    { Prof _p(ctx, "k_vm_slice"); ZKW_LAUNCH(ctx, k_vm_slice, blocks_for(n_inst, 64), 64, job); }
-    ZKW_TRY(launch_check("k_vm_slice"));
+    ZKW_LAUNCH(ctx, k_vm_slice, blocks_for(n_inst, 64), 64, job);
     ZKW_TRY(ctx->finish_out(instances, job.out, n_inst));
     if (memory_read_index) {
         ZKW_TRY(ctx->finish_out(memory_read_index, d_ri, n_mem));

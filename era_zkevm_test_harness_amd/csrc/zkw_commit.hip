@@ -64,9 +64,7 @@ int run_ntt(zkw_ctx* ctx, const u64* in, u64* out, u64* tmp, u32 log_n, size_t n
         ZKW_TRY(allow_lds(k_ntt_single));
         A.in = in; A.out = out;
         const size_t lds = (n + 1 + n / 2 + 1) * sizeof(u64);
-        Prof _p(ctx, "k_ntt_single");
-        hipLaunchKernelGGL(k_ntt_single, dim3(1, (unsigned)n_cols), dim3(NTT_THREADS), lds, ctx->stream, A);
-        return launch_check("k_ntt_single");
+        return launch_direct(ctx, "k_ntt_single", k_ntt_single, dim3(1, (unsigned)n_cols), dim3(NTT_THREADS), lds, A);
     }
     ZKW_TRY(allow_lds(k_ntt_pass1));
     ZKW_TRY(allow_lds(k_ntt_pass2));
@@ -75,17 +73,13 @@ int run_ntt(zkw_ctx* ctx, const u64* in, u64* out, u64* tmp, u32 log_n, size_t n
         NttArgs P1 = A;
         P1.in = in; P1.out = tmp;
         const size_t lds = ((size_t)T1 * (n1 + 1) + n1 / 2) * sizeof(u64);
-        Prof _p(ctx, "k_ntt_pass1");
-        hipLaunchKernelGGL(k_ntt_pass1, dim3(n2 / T1, (unsigned)n_cols), dim3(NTT_THREADS), lds, ctx->stream, P1);
-        ZKW_TRY(launch_check("k_ntt_pass1"));
+        ZKW_TRY(launch_direct(ctx, "k_ntt_pass1", k_ntt_pass1, dim3(n2 / T1, (unsigned)n_cols), dim3(NTT_THREADS), lds, P1));
     }
     {
         NttArgs P2 = A;
         P2.in = tmp; P2.out = out;
         const size_t lds = ((size_t)T2 * (n2 + 1) + n2 / 2) * sizeof(u64);
-        Prof _p(ctx, "k_ntt_pass2");
-        hipLaunchKernelGGL(k_ntt_pass2, dim3(n1 / T2, (unsigned)n_cols), dim3(NTT_THREADS), lds, ctx->stream, P2);
-        ZKW_TRY(launch_check("k_ntt_pass2"));
+        ZKW_TRY(launch_direct(ctx, "k_ntt_pass2", k_ntt_pass2, dim3(n1 / T2, (unsigned)n_cols), dim3(NTT_THREADS), lds, P2));
     }
     return ZKW_OK;
 }
@@ -110,17 +104,12 @@ int run_lde(zkw_ctx* ctx, const u64* values, u32 log_n, size_t n_cols, u32 lde_f
 // device: leaf columns [n_sets][n_cols][n] -> tree levels (leaves first) in `tree` (4 * (2 * n_sets * n - cap_size) words), the cap is its last level
 int run_merkle(zkw_ctx* ctx, const u64* cols, size_t n_sets, size_t n_cols, size_t n, u32 cap_size, u64* tree) {
     const size_t n_leaves = n_sets * n;
-    for (size_t s = 0; s < n_sets; s++) {
-        Prof _p(ctx, "k_merkle_leaves");
-        hipLaunchKernelGGL(k_merkle_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, cols + s * n_cols * n, n_cols, n, n, tree + 4 * s * n);
-        ZKW_TRY(launch_check("k_merkle_leaves"));
-    }
+    for (size_t s = 0; s < n_sets; s++)
+        ZKW_TRY(launch_direct(ctx, "k_merkle_leaves", k_merkle_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, cols + s * n_cols * n, n_cols, n, n, tree + 4 * s * n));
     u64* below = tree;
     for (size_t m = n_leaves / 2; m >= cap_size; m /= 2) {
         u64* level = below + 8 * m;
-        Prof _p(ctx, "k_merkle_nodes");
-        hipLaunchKernelGGL(k_merkle_nodes, dim3(blocks_for(m, 256)), dim3(256), 0, ctx->stream, below, m, level);
-        ZKW_TRY(launch_check("k_merkle_nodes"));
+        ZKW_TRY(launch_direct(ctx, "k_merkle_nodes", k_merkle_nodes, dim3(blocks_for(m, 256)), dim3(256), 0, below, m, level));
         below = level;
         if (m == 1) break;
     }
@@ -222,12 +211,9 @@ static int setup_columns_device(zkw_ctx* ctx, uint8_t circuit_type, uint32_t cap
     std::vector<u64> tab = split_powers(root_of_unity(log_n)), reps = powers(GENERATOR, G);
     tab.insert(tab.end(), reps.begin(), reps.end());
     ZKW_TRY(ctx->upload("setup_tab", tab, &d_tab));
-    { Prof _p(ctx, "k_powers"); hipLaunchKernelGGL(k_powers, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_tab, d_tab + NTT_TW, n, d_om); }
-    ZKW_TRY(launch_check("k_powers"));
-    { Prof _p(ctx, "k_sigma_to_field"); hipLaunchKernelGGL(k_sigma_to_field, dim3(4096), dim3(256), 0, ctx->stream, d_sigma, (size_t)G * n, log_n, d_om, d_tab + 2 * NTT_TW, d_cols); }
-    ZKW_TRY(launch_check("k_sigma_to_field"));
-    { Prof _p(ctx, "k_bytes_to_field"); hipLaunchKernelGGL(k_bytes_to_field, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_sel, n, d_cols + (size_t)G * n); }
-    ZKW_TRY(launch_check("k_bytes_to_field"));
+    ZKW_TRY(launch_direct(ctx, "k_powers", k_powers, dim3(blocks_for(n, 256)), dim3(256), 0, d_tab, d_tab + NTT_TW, n, d_om));
+    ZKW_TRY(launch_direct(ctx, "k_sigma_to_field", k_sigma_to_field, dim3(4096), dim3(256), 0, d_sigma, (size_t)G * n, log_n, d_om, d_tab + 2 * NTT_TW, d_cols));
+    ZKW_TRY(launch_direct(ctx, "k_bytes_to_field", k_bytes_to_field, dim3(blocks_for(n, 256)), dim3(256), 0, d_sel, n, d_cols + (size_t)G * n));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host vectors above are the copies' sources
     return ZKW_OK;
 }

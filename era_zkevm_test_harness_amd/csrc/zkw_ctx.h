@@ -2,7 +2,9 @@
 // launch kernels (zkw_api.hip: core + RAM path; zkw_sorters.hip: the four sorter / demuxer circuits; zkw_precompiles.hip: code
 // decommitter, precompiles, storage application and the netlist circuits; zkw_setup.hip: layouts, selectors, sigma). The other
 // units (zkw_block.hip, zkw_comm.hip, zkw_recursion.hip, zkw_vm_trace.hip) are written against include/zkw.h and zkw_internal.h.
-// Kernels live in the *.cuh headers with internal linkage: a unit includes the ones it launches.
+// Kernels live in the *.cuh headers with internal linkage: a unit includes the ones it launches. A launch is ONE statement that opens its
+// profiling span, launches and checks the launch: ZKW_LAUNCH* for a kernel body (zkw_launch.h), launch_direct for a raw __global__ kernel
+// on the context's stream; launch_check by hand only behind a launch on another stream (docs/KERNELS.md 3.29).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -289,12 +291,13 @@ struct zkw_ctx {
     std::vector<void*> retired_dev, retired_host;
 };
 
-// RAII span around one kernel launch (or a library sort); free when profiling is off
+// RAII profiling span; free when profiling is off. A launch opens its own (LaunchAt below): written out, a Prof is for what is not one
+// launch — a library sort, several launches under one name, an if / else of launches. Weight 0: no span.
 struct Prof {
     zkw_ctx* c;
     hipEvent_t b = nullptr;
     Prof(zkw_ctx* ctx, const char* name, unsigned weight = 1) : c(ctx) {
-        if (!c->profiling || c->batched()) return;
+        if (!weight || !c->profiling || c->batched()) return;
         hipEvent_t a = c->prof_event();
         b = c->prof_event();
         (void)hipEventRecord(a, c->stream);
@@ -311,13 +314,29 @@ static inline int launch_check(const char* what) {
     return ZKW_OK;
 }
 
+// The first argument of every launch form: the context, and the profiling span the launch opens. A plain `ctx` is the usual case — a span
+// of weight 1 under the kernel's name; span_as(ctx, name, weight) names or weighs it differently (one kernel timed under two names, a
+// merged launch that counts as two); no_span(ctx) opens none (the inner launches of radix_sort and of the prefix scans, which run under
+// the caller's Prof).
+struct LaunchAt {
+    zkw_ctx* ctx;
+    const char* span;  // nullptr: the kernel's name
+    unsigned weight;   // 0: no span
+    LaunchAt(zkw_ctx* c, const char* s = nullptr, unsigned w = 1) : ctx(c), span(s), weight(w) {}
+};
+static inline LaunchAt span_as(zkw_ctx* ctx, const char* name, unsigned weight = 1) { return LaunchAt(ctx, name, weight); }
+static inline LaunchAt no_span(zkw_ctx* ctx) { return LaunchAt(ctx, nullptr, 0); }
+
 // Launch of a kernel BODY (zkw_launch.h) with a grid of gx x gy workgroups of BS threads: on the context's stream, or — a context of a
 // batch — left with the batch to travel with the other blocks' launches of the same kernel. Arguments convert to the body's parameter types.
+// `name` serves the span, the error message and the batch descriptor. An empty grid launches nothing but still records its span.
 template <auto Body, int BS>
 struct Launcher {
     using S = LaunchSig<decltype(Body)>;
     template <class... A>
-    static int go(zkw_ctx* ctx, const char* name, dim3 grid, size_t lds_bytes, const A&... a) {
+    static int go(const LaunchAt& at, const char* name, dim3 grid, size_t lds_bytes, const A&... a) {
+        zkw_ctx* ctx = at.ctx;
+        Prof _p(ctx, at.span ? at.span : name, at.weight);
         if (grid.x == 0 || grid.y == 0 || grid.z == 0) return ZKW_OK;
         if (ctx->batched()) {
             typename S::T t;
@@ -325,7 +344,7 @@ struct Launcher {
             zkw_batch_launch(ctx->batch, S::template desc<Body, BS>(name), grid, lds_bytes, &t);
             return ZKW_OK;
         }
-        S::template single<Body, BS>(ctx->stream, grid, lds_bytes, a...);  // (timed by the caller's Prof, if any)
+        S::template single<Body, BS>(ctx->stream, grid, lds_bytes, a...);
         return launch_check(name);
     }
     // more than the default 64 KB of dynamic LDS for both launch forms of the kernel (once per device is enough; cheap to repeat)
@@ -335,12 +354,30 @@ struct Launcher {
         return ZKW_OK;
     }
 };
-#define ZKW_LAUNCH(ctx, kernel, gx, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(ctx, #kernel, dim3((unsigned)(gx)), 0, __VA_ARGS__)))
-#define ZKW_LAUNCH_2D(ctx, kernel, gx, gy, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(ctx, #kernel, dim3((unsigned)(gx), (unsigned)(gy)), 0, __VA_ARGS__)))
+// One statement per launch: span, launch and error check; it returns the error from the calling function. `at` is ctx, span_as(ctx, ...)
+// or no_span(ctx).
+#define ZKW_LAUNCH(at, kernel, gx, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, #kernel, dim3((unsigned)(gx)), 0, __VA_ARGS__)))
+#define ZKW_LAUNCH_2D(at, kernel, gx, gy, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, #kernel, dim3((unsigned)(gx), (unsigned)(gy)), 0, __VA_ARGS__)))
 // the same for a template kernel (the name has commas): ZKW_LAUNCH_T(ctx, (k_foo<A, B>), "k_foo", ...)
-#define ZKW_LAUNCH_T(ctx, kernel, name, gx, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(ctx, name, dim3((unsigned)(gx)), 0, __VA_ARGS__)))
+#define ZKW_LAUNCH_T(at, kernel, name, gx, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, name, dim3((unsigned)(gx)), 0, __VA_ARGS__)))
 // the general form: any dim3 grid, dynamic LDS
-#define ZKW_LAUNCH_D(ctx, kernel, name, grid, bs, lds, ...) ZKW_TRY((Launcher<&kernel, bs>::go(ctx, name, grid, lds, __VA_ARGS__)))
+#define ZKW_LAUNCH_D(at, kernel, name, grid, bs, lds, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, name, grid, lds, __VA_ARGS__)))
+
+// The same statement for a raw __global__ kernel (the commit, callstack and check kernels, which have no body form): span, launch on the
+// context's stream, error check. Such a launch cannot travel with a batch and would run before what the batch has queued, so a context of
+// a batch is refused (direct_only: the same refusal up front, for a driver that queues copies or memsets before its first launch).
+// Arguments convert to the kernel's parameter types.
+static inline int direct_only(zkw_ctx* ctx, const char* what) {
+    if (ctx->batched()) return fail(ZKW_ERR_INVALID, "%s launches directly on the stream: not on a context of a batch", what);
+    return ZKW_OK;
+}
+template <class... P, class... A>
+static int launch_direct(zkw_ctx* ctx, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, const A&... a) {
+    ZKW_TRY(direct_only(ctx, name));
+    Prof _p(ctx, name);
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, static_cast<P>(a)...);
+    return launch_check(name);
+}
 
 // rows [0, width) of blockIdx.y's column of a column-major strip
 static __device__ __forceinline__ void k_zero_strip(const VB& vb, u64* __restrict__ base, size_t pitch, size_t width) {
@@ -354,9 +391,8 @@ static __device__ __forceinline__ void k_zero_strip(const VB& vb, u64* __restric
 static inline int zero_netlist_slot(zkw_ctx* ctx, u64* trace, size_t n_rows, size_t g, size_t lookup_cols, size_t n_cols, size_t used_rows) {
     HIP_TRY(hipMemsetAsync(trace, 0, g * n_rows * sizeof(u64), ctx->stream));
     if (used_rows < n_rows) {  // (hipMemset2DAsync ran this strip at 0.8 TB/s: 0.2 ms per Keccak slot)
-        ZKW_LAUNCH_2D(ctx, k_zero_strip, (unsigned)((n_rows - used_rows + 255) / 256), (unsigned)lookup_cols, 256,
+        ZKW_LAUNCH_2D(no_span(ctx), k_zero_strip, (unsigned)((n_rows - used_rows + 255) / 256), (unsigned)lookup_cols, 256,
                            trace + g * n_rows + used_rows, n_rows, n_rows - used_rows);
-        ZKW_TRY(launch_check("k_zero_strip"));
     }
     HIP_TRY(hipMemsetAsync(trace + (g + lookup_cols) * n_rows, 0, (n_cols - g - lookup_cols) * n_rows * sizeof(u64), ctx->stream));
     return ZKW_OK;

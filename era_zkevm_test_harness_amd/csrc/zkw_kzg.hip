@@ -66,14 +66,14 @@ extern "C" int zkw_kzg_settings_create(zkw_ctx* ctx, const uint8_t* g1_monomial,
     }
     std::vector<u32> status(n_points);
     int rc = [&]() -> int {
-        { Prof _p(ctx, "k_kzg_decompress"); ZKW_LAUNCH(ctx, k_kzg_decompress, blocks_for(n_points, 64), 64, d_in, (u32)n_points, s->table, d_status); }
+        ZKW_LAUNCH(ctx, k_kzg_decompress, blocks_for(n_points, 64), 64, d_in, (u32)n_points, s->table, d_status);
         return ctx->read_small(status.data(), d_status, n_points * sizeof(u32));
     }();
     if (rc != ZKW_OK) return drop(rc);
     for (size_t k = 0; k < n_points; k++)
         if (status[k] != bls::G1_OK) return drop(fail(ZKW_ERR_INVALID, "zkw_kzg_settings_create: point %zu is refused: %s", k, kzg_reason(status[k])));
     rc = [&]() -> int {
-        { Prof _p(ctx, "k_kzg_table"); ZKW_LAUNCH_2D(ctx, k_kzg_table, blocks_for(n_points, 64), KZG_WINDOWS - 1, 64, s->table, (u32)n_points); }
+        ZKW_LAUNCH_2D(ctx, k_kzg_table, blocks_for(n_points, 64), KZG_WINDOWS - 1, 64, s->table, (u32)n_points);
         HIP_TRY(ctx->sync_stream());  // other contexts read the table without any ordering with this stream
         return ZKW_OK;
     }();
@@ -99,10 +99,10 @@ extern "C" size_t zkw_kzg_settings_bytes(const zkw_kzg_settings* s) { return s ?
 static int kzg_commit_device(const zkw_kzg_settings* s, zkw_ctx* ctx, KzgSrc src, u32 poly_stride, size_t n_polys, uint8_t* d_out, u32 out_stride) {
     bls::G1Jac* buckets = nullptr;
     ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_buckets", n_polys * (KZG_BUCKETS + 8), &buckets));
-    { Prof _p(ctx, "k_kzg_accumulate"); ZKW_LAUNCH_2D(ctx, k_kzg_accumulate, KZG_BUCKETS - 1, n_polys, KZG_ACC_THREADS, src, poly_stride, (const bls::G1Aff*)s->table, (u32)s->n, buckets); }
+    ZKW_LAUNCH_2D(ctx, k_kzg_accumulate, KZG_BUCKETS - 1, n_polys, KZG_ACC_THREADS, src, poly_stride, (const bls::G1Aff*)s->table, (u32)s->n, buckets);
     bls::G1Jac* sums = buckets + n_polys * KZG_BUCKETS;
-    { Prof _p(ctx, "k_kzg_finish"); ZKW_LAUNCH_2D(ctx, k_kzg_finish, n_polys, 2, KZG_FIN_THREADS, (const bls::G1Jac*)buckets, sums); }
-    { Prof _p(ctx, "k_kzg_compress"); ZKW_LAUNCH(ctx, k_kzg_compress, blocks_for(n_polys, 64), 64, (const bls::G1Jac*)sums, (u32)n_polys, d_out, out_stride); }
+    ZKW_LAUNCH_2D(ctx, k_kzg_finish, n_polys, 2, KZG_FIN_THREADS, (const bls::G1Jac*)buckets, sums);
+    ZKW_LAUNCH(ctx, k_kzg_compress, blocks_for(n_polys, 64), 64, (const bls::G1Jac*)sums, (u32)n_polys, d_out, out_stride);
     return ZKW_OK;
 }
 
@@ -125,7 +125,7 @@ extern "C" int zkw_kzg_commit(const zkw_kzg_settings* s, zkw_ctx* ctx, const uin
         u32 *d_flag = nullptr, h_flag = ~0u;
         ZKW_TRY(ctx->scratch_t<u32>("kzg_flag", 1, &d_flag));
         HIP_TRY(ctx->memset_async(d_flag, 0xFF, sizeof(u32)));
-        { Prof _p(ctx, "k_kzg_check"); ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(total, 256), 256, d_c, (u32)total, d_flag); }
+        ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(total, 256), 256, d_c, (u32)total, d_flag);
         ZKW_TRY(ctx->read_small(&h_flag, d_flag, sizeof h_flag));
         if (h_flag != ~0u)
             return fail(ZKW_ERR_INVALID, "zkw_kzg_commit: coefficient %zu of polynomial %zu is not below r", (size_t)h_flag % n_coeffs, (size_t)h_flag / n_coeffs);
@@ -157,12 +157,11 @@ extern "C" int zkw_eip4844_witness(const zkw_kzg_settings* s, zkw_ctx* ctx, cons
         Launcher<&k_kzg_linear_hash, 64>::S::template single<&k_kzg_linear_hash, 64>(side, dim3((unsigned)n_blobs), 0, d_b, rec + KZG_REC_LINEAR, (u32)KZG_REC_BYTES);
         ZKW_TRY(launch_check("k_kzg_linear_hash"));
     } else {
-        Prof _p(ctx, "k_kzg_linear_hash");
         ZKW_LAUNCH(ctx, k_kzg_linear_hash, n_blobs, 64, d_b, rec + KZG_REC_LINEAR, (u32)KZG_REC_BYTES);
     }
     ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_b, (u32)KZG_BLOB_ELEMENTS, 1}, (u32)KZG_BLOB_BYTES, n_blobs, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES));
     if (beside) ZKW_TRY(ctx->side_join());
-    { Prof _p(ctx, "k_kzg_tail"); ZKW_LAUNCH(ctx, k_kzg_tail, n_blobs, KZG_TAIL_THREADS, d_b, rec); }
+    ZKW_LAUNCH(ctx, k_kzg_tail, n_blobs, KZG_TAIL_THREADS, d_b, rec);
     ZKW_TRY(ctx->finish_out(out, d_rec, n_blobs));
     return ctx->sync_if_host();
 }
@@ -183,8 +182,8 @@ extern "C" int zkw_kzg_open(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8
         u32 *d_flag = nullptr, h_flag[2] = {~0u, ~0u};  // the first bad coefficient, the first bad point
         ZKW_TRY(ctx->scratch_t<u32>("kzg_flag", 2, &d_flag));
         HIP_TRY(ctx->memset_async(d_flag, 0xFF, sizeof h_flag));
-        if (total) { Prof _p(ctx, "k_kzg_check"); ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(total, 256), 256, d_c, (u32)total, d_flag); }
-        { Prof _p(ctx, "k_kzg_check_points"); ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(n_polys, 256), 256, d_z, (u32)n_polys, d_flag + 1); }
+        if (total) ZKW_LAUNCH(ctx, k_kzg_check, blocks_for(total, 256), 256, d_c, (u32)total, d_flag);
+        ZKW_LAUNCH(span_as(ctx, "k_kzg_check_points"), k_kzg_check, blocks_for(n_polys, 256), 256, d_z, (u32)n_polys, d_flag + 1);
         ZKW_TRY(ctx->read_small(h_flag, d_flag, sizeof h_flag));
         if (h_flag[0] != ~0u)
             return fail(ZKW_ERR_INVALID, "zkw_kzg_open: coefficient %zu of polynomial %zu is not below r", (size_t)h_flag[0] % n_coeffs, (size_t)h_flag[0] / n_coeffs);
@@ -194,7 +193,7 @@ extern "C" int zkw_kzg_open(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8
     ZKW_TRY(ctx->out("kzg_out", proofs, n_polys * 48, &d_proofs));
     ZKW_TRY(ctx->out("kzg_out_values", values, n_polys * 32, &d_values));
     ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_quotient_rows", n_polys * n_rows * 32, &d_rows));
-    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, n_polys, KZG_QUO_THREADS, KzgSrc{d_c, (u32)n_coeffs, 0}, (u32)(n_coeffs * 32), d_z, 32u, (u32)KZG_Z_LE32, d_rows, (u32)(n_rows * 32), d_values, 32u, 0u); }
+    ZKW_LAUNCH(ctx, k_kzg_quotient, n_polys, KZG_QUO_THREADS, KzgSrc{d_c, (u32)n_coeffs, 0}, (u32)(n_coeffs * 32), d_z, 32u, (u32)KZG_Z_LE32, d_rows, (u32)(n_rows * 32), d_values, 32u, 0u);
     ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_rows, (u32)n_rows, 0}, (u32)(n_rows * 32), n_polys, d_proofs, 48));
     ZKW_TRY(ctx->finish_out(proofs, d_proofs, n_polys * 48));
     ZKW_TRY(ctx->finish_out(values, d_values, n_polys * 32));
@@ -248,15 +247,15 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
         ZKW_TRY((kzg_launch_on<&k_kzg_blob_challenge, 64>(side, "k_kzg_blob_challenge", nb, 0, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES,
                                                                prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES)));
     } else {
-        { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
-        { Prof _p(ctx, "k_kzg_blob_ntt"); ZKW_LAUNCH_D(ctx, k_kzg_blob_ntt, "k_kzg_blob_ntt", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev); }
-        { Prof _p(ctx, "k_kzg_blob_challenge"); ZKW_LAUNCH(ctx, k_kzg_blob_challenge, nb, 64, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES, prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES); }
+        ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
+        ZKW_LAUNCH_D(ctx, k_kzg_blob_ntt, "k_kzg_blob_ntt", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev);
+        ZKW_LAUNCH(ctx, k_kzg_blob_challenge, nb, 64, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES, prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES);
     }
-    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, rec + KZG_REC_Z, (u32)KZG_REC_BYTES, (u32)KZG_Z_BE16, d_rows, 2 * ROWS, (uint8_t*)nullptr, 0u, 0u); }
+    ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, rec + KZG_REC_Z, (u32)KZG_REC_BYTES, (u32)KZG_Z_BE16, d_rows, 2 * ROWS, (uint8_t*)nullptr, 0u, 0u);
     if (beside) ZKW_TRY(ctx->side_join());
-    { Prof _p(ctx, "k_kzg_quotient"); ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, (const uint8_t*)prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES, (u32)KZG_Z_BE32, d_rows + ROWS, 2 * ROWS, prf + KZG_PRF_VALUE, (u32)KZG_PRF_BYTES, 1u); }
+    ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, (const uint8_t*)prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES, (u32)KZG_Z_BE32, d_rows + ROWS, 2 * ROWS, prf + KZG_PRF_VALUE, (u32)KZG_PRF_BYTES, 1u);
     ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_rows, (u32)KZG_BLOB_ELEMENTS - 1, 0}, ROWS, 2 * n_blobs, d_proofs, 48));
-    { Prof _p(ctx, "k_kzg_proofs_out"); ZKW_LAUNCH(ctx, k_kzg_proofs_out, blocks_for(n_blobs * 96, 256), 256, (const uint8_t*)d_proofs, (u32)nb, prf); }
+    ZKW_LAUNCH(ctx, k_kzg_proofs_out, blocks_for(n_blobs * 96, 256), 256, (const uint8_t*)d_proofs, (u32)nb, prf);
     ZKW_TRY(ctx->finish_out(out, d_out, n_blobs));
     if (blob_evaluations) ZKW_TRY(ctx->finish_out(blob_evaluations, d_ev, n_blobs * KZG_EVAL_BYTES));
     return ctx->sync_if_host();
@@ -307,7 +306,7 @@ extern "C" int zkw_kzg_verifier_create(zkw_ctx* ctx, const uint8_t* tau_g2, zkw_
     }
     u32 status[2] = {0, 0};
     const int rc = [&]() -> int {
-        { Prof _p(ctx, "k_kzg_g2_prepare"); ZKW_LAUNCH(ctx, k_kzg_g2_prepare, 1, 64, d_in, v->lines, d_status); }
+        ZKW_LAUNCH(ctx, k_kzg_g2_prepare, 1, 64, d_in, v->lines, d_status);
         return ctx->read_small(status, d_status, sizeof status);  // (synchronises: other contexts read the lines without any ordering with this stream)
     }();
     if (rc != ZKW_OK) return drop(rc);
@@ -335,8 +334,8 @@ static int kzg_verify_device(const zkw_kzg_verifier* v, zkw_ctx* ctx, const KzgC
     u32* d_status = nullptr;
     ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_verify_points", 2 * n, &d_pts));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_verify_status", n, &d_status));
-    { Prof _p(ctx, "k_kzg_verify_points"); ZKW_LAUNCH(ctx, k_kzg_verify_points, blocks_for(n, 64), 64, claims, (u32)n, d_pts, d_status); }
-    { Prof _p(ctx, "k_kzg_verify_pairing"); ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v->lines, (u32)n, d_verdicts); }
+    ZKW_LAUNCH(ctx, k_kzg_verify_points, blocks_for(n, 64), 64, claims, (u32)n, d_pts, d_status);
+    ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v->lines, (u32)n, d_verdicts);
     return ZKW_OK;
 }
 
@@ -397,8 +396,8 @@ extern "C" int zkw_kzg_evaluate_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluati
     ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
     ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_eval_values", n * 32, &d_y));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
-    { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
-    { Prof _p(ctx, "k_kzg_blob_eval"); ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, d_z, 32u, (const bls::Fr*)d_tw, d_y, 32u, d_st); }
+    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
+    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, d_z, 32u, (const bls::Fr*)d_tw, d_y, 32u, d_st);
     std::vector<u32> st(n);
     ZKW_TRY(ctx->read_small(st.data(), d_st, n * sizeof(u32)));
     for (size_t j = 0; j < n; j++) {
@@ -430,9 +429,9 @@ extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx,
     ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
     // one after another on the context's stream: the evaluation needs the challenge, the points kernel needs both
-    { Prof _p(ctx, "k_kzg_twiddles"); ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw); }
-    { Prof _p(ctx, "k_kzg_blob_challenge"); ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, cl.commitments, 48u, d_open, 64u); }
-    { Prof _p(ctx, "k_kzg_blob_eval"); ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, (const uint8_t*)d_open, 64u, (const bls::Fr*)d_tw, d_open + 32, 64u, d_st); }
+    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
+    ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, cl.commitments, 48u, d_open, 64u);
+    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, (const uint8_t*)d_open, 64u, (const bls::Fr*)d_tw, d_open + 32, 64u, d_st);
     cl.points = d_open;
     cl.values = d_open + 32;
     cl.pre = d_st;

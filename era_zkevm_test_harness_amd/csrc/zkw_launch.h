@@ -1,7 +1,8 @@
 // zkw_launch.h — one kernel body, two launch forms.
 //
 // A builder kernel is written as a __device__ BODY whose first parameter is its virtual block position (VB: index and count of the
-// workgroups of ITS job) and launched through zkw_launch<Body, BS>(ctx, name, grid, args...):
+// workgroups of ITS job) and launched with one statement, ZKW_LAUNCH* (zkw_ctx.h: Launcher<Body, BS>::go(at, name, grid, lds, args...) — it
+// opens the profiling span, launches and checks the launch):
 //   * a context on its own (zkw_block_run, every direct call of a builder): k_single<Body> on the context's stream — the launch the
 //     __global__ kernel of rounds 1-5 was;
 //   * a context that belongs to a batch (zkw_blocks_run: K blocks in flight as fibers of one host thread, zkw_batch.h): nothing is launched.

@@ -56,8 +56,7 @@ extern "C" int zkw_decommitter_memory_queries(zkw_ctx* ctx, const zkw_decommit_q
     ZKW_TRY(ctx->out("dcm_mq_out", out, total, &d_out));
     DecommitterJob job{d_req, d_words, d_woff, nullptr, nullptr, d_out, nullptr, nullptr, n_requests, nullptr};
     if (total) {
-        { Prof _p(ctx, "k_decommitter_mem_queries"); ZKW_LAUNCH(ctx, k_decommitter_mem_queries, blocks_for(total, 256), 256, job, (u64)total); }
-        ZKW_TRY(launch_check("k_decommitter_mem_queries"));
+        ZKW_LAUNCH(ctx, k_decommitter_mem_queries, blocks_for(total, 256), 256, job, (u64)total);
     }
     ZKW_TRY(ctx->finish_out(out, d_out, total));
     return ctx->sync_if_host();
@@ -114,10 +113,8 @@ extern "C" int zkw_decommitter_build_with_tails(zkw_ctx* ctx, const zkw_decommit
         ctx->copy_async(w->dedup_tails, d_dt, n_requests * 96, hipMemcpyDeviceToDevice) != hipSuccess)
         return bail(fail(ZKW_ERR_HIP, "copy of the decommit requests failed"));
     DecommitterJob job{d_req, d_words, d_woff, d_roff, w->round_states, w->mem_q, w->mem_enc, d_viol, n_requests, w->sha256_rounds, w->round_ops};
-    { Prof _p(ctx, "k_decommitter_sha"); ZKW_LAUNCH(ctx, k_decommitter_sha, blocks_for(n_requests, 64), 64, job); }
-    if ((rc = launch_check("k_decommitter_sha")) != ZKW_OK) return bail(rc);
-    { Prof _p(ctx, "k_decommitter_mem_queries"); ZKW_LAUNCH(ctx, k_decommitter_mem_queries, blocks_for(w->total_words, 256), 256, job, (u64)w->total_words); }
-    if ((rc = launch_check("k_decommitter_mem_queries")) != ZKW_OK) return bail(rc);
+    ZKW_LAUNCH(ctx, k_decommitter_sha, blocks_for(n_requests, 64), 64, job);
+    ZKW_LAUNCH(ctx, k_decommitter_mem_queries, blocks_for(w->total_words, 256), 256, job, (u64)w->total_words);
     zkw_queue_state12* d_min = nullptr;
     std::vector<zkw_queue_state12> minv(1, *mem_in);
     if ((rc = ctx->upload("dcm_mem_in", minv, &d_min)) != ZKW_OK) return bail(rc);
@@ -139,8 +136,7 @@ extern "C" int zkw_decommitter_build_with_tails(zkw_ctx* ctx, const zkw_decommit
     blk[0].capacity = capacity;
     DecommitterBlock* d_blk = nullptr;
     if ((rc = ctx->upload("dcm_block", blk, &d_blk)) != ZKW_OK) return bail(rc);
-    { Prof _p(ctx, "k_decommitter_instances"); ZKW_LAUNCH(ctx, k_decommitter_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    if ((rc = launch_check("k_decommitter_instances")) != ZKW_OK) return bail(rc);
+    ZKW_LAUNCH(ctx, k_decommitter_instances, blocks_for(w->n_instances, 64), 64, d_blk);
     u32 viol = 0;
     if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
         return bail(fail(ZKW_ERR_HIP, "readback failed"));
@@ -184,8 +180,7 @@ extern "C" int zkw_linear_keccak256(zkw_ctx* ctx, const zkw_log_query* messages,
     uint8_t* d_out = nullptr;
     ZKW_TRY(ctx->in("lk_q", messages, n, &d_q));
     ZKW_TRY(ctx->out("lk_out", hash_out, 32, &d_out));
-    { Prof _p(ctx, "k_linear_keccak256"); ZKW_LAUNCH(ctx, k_linear_keccak256, 1, 64, d_q, n, d_out, (zkw_keccak_round_record*)nullptr, (const u64*)nullptr, (const u64*)nullptr, false); }
-    ZKW_TRY(launch_check("k_linear_keccak256"));
+    ZKW_LAUNCH(ctx, k_linear_keccak256, 1, 64, d_q, n, d_out, (zkw_keccak_round_record*)nullptr, (const u64*)nullptr, (const u64*)nullptr, false);
     ZKW_TRY(ctx->finish_out(hash_out, d_out, 32));
     return ctx->sync_if_host();
 }
@@ -313,8 +308,7 @@ extern "C" int zkw_precompile_build_with_tails(zkw_ctx* ctx, int kind, const zkw
              (n_queries && ctx->copy_async(w->mem_q, d_mq, n_queries * sizeof(zkw_mem_query), hipMemcpyDeviceToDevice) != hipSuccess)))
             return bail(fail(ZKW_ERR_HIP, "copy of the precompile calls failed"));
         PrecompileJob job{kind, d_req, d_mq, d_roff, d_qoff, d_rdoff, d_snaps, d_viol, n_requests, w->total_rounds, capacity, w->keccak_rounds, w->sha256_rounds, w->round_ops};
-        { Prof _p(ctx, "k_precompile_walk"); ZKW_LAUNCH(ctx, k_precompile_walk, blocks_for(n_requests, 64), 64, job); }
-        if ((rc = launch_check("k_precompile_walk")) != ZKW_OK) return bail(rc);
+        ZKW_LAUNCH(ctx, k_precompile_walk, blocks_for(n_requests, 64), 64, job);
     }
     std::vector<PrecompileBlock> blk(1);
     blk[0].kind = kind;
@@ -329,8 +323,7 @@ extern "C" int zkw_precompile_build_with_tails(zkw_ctx* ctx, int kind, const zkw
     blk[0].capacity = capacity;
     PrecompileBlock* d_blk = nullptr;
     if ((rc = ctx->upload("pc_block", blk, &d_blk)) != ZKW_OK) return bail(rc);
-    { Prof _p(ctx, "k_precompile_instances"); ZKW_LAUNCH(ctx, k_precompile_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    if ((rc = launch_check("k_precompile_instances")) != ZKW_OK) return bail(rc);
+    ZKW_LAUNCH(ctx, k_precompile_instances, blocks_for(w->n_instances, 64), 64, d_blk);
     u32 viol = 0;
     if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
         return bail(fail(ZKW_ERR_HIP, "readback failed"));
@@ -450,29 +443,18 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
     u64 meta[2] = {1, initial_next_enumeration_index};
     if (n) {
         const unsigned g64 = blocks_for(n, 64);
-        { Prof _p(ctx, "k_sap_keys"); ZKW_LAUNCH(ctx, k_sap_keys, g64, 64, job); }
-        TRY(launch_check("k_sap_keys"));
-        { Prof _p(ctx, "k_sap_scan"); ZKW_LAUNCH(ctx, k_sap_scan, 1, 1024, job); }
-        TRY(launch_check("k_sap_scan"));
-        { Prof _p(ctx, "k_sap_items"); ZKW_LAUNCH(ctx, k_sap_items, g64, 64, job, w->items); }
-        TRY(launch_check("k_sap_items"));
-        { Prof _p(ctx, "k_sap_pairs"); ZKW_LAUNCH(ctx, k_sap_pairs, g64, 64, job); }
-        TRY(launch_check("k_sap_pairs"));
-        { Prof _p(ctx, "k_sap_leaves"); ZKW_LAUNCH(ctx, k_sap_leaves, g64, 64, job); }
-        TRY(launch_check("k_sap_leaves"));
+        ZKW_LAUNCH(ctx, k_sap_keys, g64, 64, job);
+        ZKW_LAUNCH(ctx, k_sap_scan, 1, 1024, job);
+        ZKW_LAUNCH(ctx, k_sap_items, g64, 64, job, w->items);
+        ZKW_LAUNCH(ctx, k_sap_pairs, g64, 64, job);
+        ZKW_LAUNCH(ctx, k_sap_leaves, g64, 64, job);
         static_assert(ZKW_STORAGE_TREE_DEPTH == 256, "k_sap_levels walks 256 levels");
         if (n <= SAP_PERSISTENT_MAX) {
-            Prof _p(ctx, "k_sap_levels");
             ZKW_LAUNCH(ctx, k_sap_levels, 1, SAP_PERSISTENT_THREADS, job);
         } else {
-            for (int L = 0; L < ZKW_STORAGE_TREE_DEPTH && rc == ZKW_OK; L++) {
-                Prof _p(ctx, "k_sap_level");
-                ZKW_LAUNCH(ctx, k_sap_level, g64, 64, job, L);
-            }
+            for (int L = 0; L < ZKW_STORAGE_TREE_DEPTH && rc == ZKW_OK; L++) ZKW_LAUNCH(ctx, k_sap_level, g64, 64, job, L);
         }
-        TRY(launch_check("k_sap_level"));
-        { Prof _p(ctx, "k_sap_roots"); ZKW_LAUNCH(ctx, k_sap_roots, g64, 64, job); }
-        TRY(launch_check("k_sap_roots"));
+        ZKW_LAUNCH(ctx, k_sap_roots, g64, 64, job);
         if (rc != ZKW_OK) return bail(rc);
         if (ctx->copy_async(w->leaf_indexes, job.init_index, n * 8, hipMemcpyDeviceToDevice) != hipSuccess ||
             ctx->read_small(meta, d_meta, sizeof meta) != ZKW_OK)
@@ -482,8 +464,7 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
     if (dev_malloc((void**)&w->instances, w->n_instances * sizeof(zkw_storage_application_instance) + 64) != hipSuccess)
         return bail(fail(ZKW_ERR_OOM, "zkw_storage_application_build: hipMalloc failed"));
     SapKeccakOut ko{d_snap, d_hash};
-    { Prof _p(ctx, "k_sap_keccak"); ZKW_LAUNCH(ctx, k_sap_keccak, 1, 64, job, ko); }
-    TRY(launch_check("k_sap_keccak"));
+    ZKW_LAUNCH(ctx, k_sap_keccak, 1, 64, job, ko);
     std::vector<SapBlock> blk(1);
     blk[0].job = job;
     blk[0].query_tails = d_qt;
@@ -494,8 +475,7 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
     SapBlock* d_blk = nullptr;
     TRY(ctx->upload("sap_block", blk, &d_blk));
     if (rc != ZKW_OK) return bail(rc);
-    { Prof _p(ctx, "k_sap_instances"); ZKW_LAUNCH(ctx, k_sap_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    TRY(launch_check("k_sap_instances"));
+    ZKW_LAUNCH(ctx, k_sap_instances, blocks_for(w->n_instances, 64), 64, d_blk);
     if (rc != ZKW_OK) return bail(rc);
     u32 viol = 0;
     if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
@@ -907,11 +887,11 @@ int nl_launch_fill_w(zkw_ctx* ctx, const NlCached* nc, const NlJob* d_jobs, unsi
     if constexpr (WAVES == 16) {
         Prof _p(ctx, "k_nl_fill");
         L::S::template single<&k_nl_fill<W, R, WAVES>, 64 * WAVES>(ctx->stream, dim3(blocks, nj), lds, nc->dev, d_jobs, capacity, n_rows, probe);
+        return launch_check("k_nl_fill");
     } else {
-        Prof _p(ctx, "k_nl_fill");
         ZKW_LAUNCH_D(ctx, (k_nl_fill<W, R, WAVES>), "k_nl_fill", dim3(blocks, nj), 64 * WAVES, lds, nc->dev, d_jobs, capacity, n_rows, probe);
+        return ZKW_OK;
     }
-    return launch_check("k_nl_fill");
 }
 // the lane-per-cycle path (k_nl_walk + k_nl_expand), for netlists whose live values fit the LDS
 template <int W, int R>
@@ -926,10 +906,9 @@ int nl_launch_fill_lanes(zkw_ctx* ctx, const NlCached* nc, const NlJob* d_jobs, 
     const size_t per_job = ((size_t)tiles * S.mult_col * S.rows_per_cycle * 64 + 255) & ~(size_t)255;
     uint8_t* d_bytes = nullptr;
     ZKW_TRY(ctx->scratch_t<uint8_t>("nl_bytes", per_job * nj, &d_bytes));
-    { Prof _p(ctx, "k_nl_walk"); ZKW_LAUNCH_D(ctx, (k_nl_walk<W, R>), "k_nl_walk", dim3(tiles, nj), 64, nc->host.walk_lds, nc->dev, d_jobs, capacity, d_bytes, per_job, nc->host.prog, nc->host.prog0, nc->host.out_src); }
-    ZKW_TRY(launch_check("k_nl_walk"));
-    { Prof _p(ctx, "k_nl_expand"); ZKW_LAUNCH_D(ctx, (k_nl_expand<W, R>), "k_nl_expand", dim3((S.g + R) * row_blocks, tiles, nj), 64, 0, nc->dev, d_jobs, capacity, n_rows, d_bytes, per_job); }
-    return launch_check("k_nl_expand");
+    ZKW_LAUNCH_D(ctx, (k_nl_walk<W, R>), "k_nl_walk", dim3(tiles, nj), 64, nc->host.walk_lds, nc->dev, d_jobs, capacity, d_bytes, per_job, nc->host.prog, nc->host.prog0, nc->host.out_src);
+    ZKW_LAUNCH_D(ctx, (k_nl_expand<W, R>), "k_nl_expand", dim3((S.g + R) * row_blocks, tiles, nj), 64, 0, nc->dev, d_jobs, capacity, n_rows, d_bytes, per_job);
+    return ZKW_OK;
 }
 
 using NlAfterFill = std::function<int()>;  // runs once the fill kernel is queued, before the histogram / finish / queue-section kernels (the closed-form sponges fork here)
@@ -941,15 +920,15 @@ int nl_launch_fill(zkw_ctx* ctx, const NlCached* nc, const NlJob* d_jobs, unsign
     if ((lanes_env || ctx->netlist_fill_form == 1) && nc->host.walk_lds <= 160 * 1024) {
         ZKW_TRY((nl_launch_fill_lanes<W, R>(ctx, nc, d_jobs, nj, capacity, n_rows)));
         if (after_fill) ZKW_TRY(after_fill());
-        { Prof _p(ctx, "k_nl_hist"); ZKW_LAUNCH_D(ctx, (k_nl_hist<R>), "k_nl_hist", dim3(nc->host.n_hist_slices, nc->host.s.total_table_rows > NL_HIST_HALF ? 2 : 1, nj), NL_HIST_THREADS, 0, nc->dev, d_jobs, capacity, n_rows); }
-        return launch_check("k_nl_hist");
+        ZKW_LAUNCH_D(ctx, (k_nl_hist<R>), "k_nl_hist", dim3(nc->host.n_hist_slices, nc->host.s.total_table_rows > NL_HIST_HALF ? 2 : 1, nj), NL_HIST_THREADS, 0, nc->dev, d_jobs, capacity, n_rows);
+        return ZKW_OK;
     }
     // (a call with few cycles keeps 8 waves per workgroup: twice the workgroups, so that every CU has one)
     if (nc->host.fill_waves == 16 && (size_t)((capacity + 15) / 16) * nj >= 128 && !ctx->batched()) ZKW_TRY((nl_launch_fill_w<W, R, 16>(ctx, nc, d_jobs, nj, capacity, n_rows)));
     else ZKW_TRY((nl_launch_fill_w<W, R, 8>(ctx, nc, d_jobs, nj, capacity, n_rows)));
     if (after_fill) ZKW_TRY(after_fill());
-    { Prof _p(ctx, "k_nl_hist"); ZKW_LAUNCH_D(ctx, (k_nl_hist<R>), "k_nl_hist", dim3(nc->host.n_hist_slices, nc->host.s.total_table_rows > NL_HIST_HALF ? 2 : 1, nj), NL_HIST_THREADS, 0, nc->dev, d_jobs, capacity, n_rows); }
-    return launch_check("k_nl_hist");
+    ZKW_LAUNCH_D(ctx, (k_nl_hist<R>), "k_nl_hist", dim3(nc->host.n_hist_slices, nc->host.s.total_table_rows > NL_HIST_HALF ? 2 : 1, nj), NL_HIST_THREADS, 0, nc->dev, d_jobs, capacity, n_rows);
+    return ZKW_OK;
 }
 
 // synthesis of instances of one netlist circuit: `prepare` turns the builder's records into the engine's inputs (header bits, free
@@ -994,8 +973,7 @@ int nl_synthesize_with(zkw_ctx* ctx, int circuit_type, const NlPrepare& prepare,
         jobs[k] = NlJob{prep[k].hdr_bits, prep[k].free_elems, prep[k].state_before, inst[k].public_input, tr, d_keys + k * keys_n, d_hist + k * hist_n};
         if (!clean) {
             HIP_TRY(ctx->memset_async(tr, 0, (size_t)S.g * n_rows * sizeof(u64)));  // general-purpose columns
-            ZKW_LAUNCH_2D(ctx, k_zero_strip, (unsigned)((n_rows - bnd + 255) / 256), S.mult_col - S.g, 256, tr + (size_t)S.g * n_rows + bnd, n_rows, n_rows - bnd);
-            ZKW_TRY(launch_check("k_zero_strip"));
+            ZKW_LAUNCH_2D(no_span(ctx), k_zero_strip, (unsigned)((n_rows - bnd + 255) / 256), S.mult_col - S.g, 256, tr + (size_t)S.g * n_rows + bnd, n_rows, n_rows - bnd);
             HIP_TRY(ctx->memset_async(tr + (size_t)S.mult_col * n_rows, 0, n_rows * sizeof(u64)));
         }
     }
@@ -1011,19 +989,19 @@ int nl_synthesize_with(zkw_ctx* ctx, int circuit_type, const NlPrepare& prepare,
         case 7: ZKW_TRY((nl_launch_fill<EK_W, EK_R>(ctx, nc, d_jobs, nj, capacity, n_rows, after_fill))); break;
         default: ZKW_TRY((nl_launch_fill<LH_W, LH_R>(ctx, nc, d_jobs, nj, capacity, n_rows, after_fill))); break;  // 13 and 10: 3 x 26
     }
-    { Prof _p(ctx, "k_nl_finish"); ZKW_LAUNCH_2D(ctx, k_nl_finish, (std::max(S.state, S.total_table_rows) + 255) / 256, nj, 256, nc->dev, d_jobs, capacity, n_rows); }
-    const int rc = launch_check("k_nl_finish");
-    if (rc == ZKW_OK && hold) {
+    ZKW_LAUNCH_2D(ctx, k_nl_finish, (std::max(S.state, S.total_table_rows) + 255) / 256, nj, 256, nc->dev, d_jobs, capacity, n_rows);
+    if (hold) {
         hold->pending.insert(hold->pending.end(), claims.pending.begin(), claims.pending.end());
         return ZKW_OK;
     }
-    return claims.commit_if(rc);
+    claims.commit();
+    return ZKW_OK;
 }
 
 // ... from the block's round records (`sha_like`: zkw_sha256_round_record, else zkw_keccak_round_record)
 int nl_synthesize(zkw_ctx* ctx, int circuit_type, bool sha_like, const void* d_rounds, const std::vector<NlInstance>& inst, u32 capacity, size_t n_rows,
                   const NlAfterFill& after_fill = {}, SlotClaims* hold = nullptr) {
-    return nl_synthesize_with(ctx, circuit_type, [&](std::vector<NlPrepJob>& prep) {
+    return nl_synthesize_with(ctx, circuit_type, [&](std::vector<NlPrepJob>& prep) -> int {
         const size_t rec_bytes = sha_like ? sizeof(zkw_sha256_round_record) : sizeof(zkw_keccak_round_record);
         for (size_t k = 0; k < prep.size(); k++) {
             if (inst[k].fresh) { prep[k].rounds = static_cast<const char*>(d_rounds) + inst[k].first_round * rec_bytes; prep[k].first_round = 0; }
@@ -1032,9 +1010,9 @@ int nl_synthesize(zkw_ctx* ctx, int circuit_type, bool sha_like, const void* d_r
         NlPrepJob* d_prep = nullptr;
         ZKW_TRY(ctx->upload("nl_prep", prep, &d_prep));
         const unsigned nj = (unsigned)prep.size();
-        if (sha_like) { Prof _p(ctx, "k_nl_prepare"); ZKW_LAUNCH_2D(ctx, k_nl_prepare_sha, capacity + 1, nj, 128, d_prep, capacity); }
-        else { Prof _p(ctx, "k_nl_prepare"); ZKW_LAUNCH_2D(ctx, k_nl_prepare_keccak, capacity + 1, nj, 256, d_prep, capacity); }
-        return launch_check("k_nl_prepare");
+        if (sha_like) ZKW_LAUNCH_2D(span_as(ctx, "k_nl_prepare"), k_nl_prepare_sha, capacity + 1, nj, 128, d_prep, capacity);
+        else ZKW_LAUNCH_2D(span_as(ctx, "k_nl_prepare"), k_nl_prepare_keccak, capacity + 1, nj, 256, d_prep, capacity);
+        return ZKW_OK;
     }, inst, capacity, n_rows, after_fill, hold);
 }
 
@@ -1064,10 +1042,9 @@ int nlq_synthesize(zkw_ctx* ctx, int circuit_type, const NlqQueues& Q, const std
     ZKW_TRY(ctx->upload("nlq_feed_jobs", fj, &d_fj));
     ZKW_TRY(ctx->upload("nlq_jobs", jobs, &d_jobs));
     const unsigned cb = (capacity + 63) / 64;
-    { Prof _p(ctx, "k_nlq_feed"); ZKW_LAUNCH_2D(ctx, k_nlq_feed, cb, (unsigned)ni, 64, circuit_type, d_fj, capacity, d->n_ops); }
-    ZKW_TRY(launch_check("k_nlq_feed"));
-    { Prof _p(ctx, "k_nlq_fill"); ZKW_LAUNCH_D(ctx, (k_nlq_fill), "k_nlq_fill", dim3((capacity + 3) / 4, d->n_ops, (unsigned)ni), 64, 0, nc->dev, nc->free_home, nc->link_home, *d, d_jobs, capacity, n_rows); }
-    return launch_check("k_nlq_fill");
+    ZKW_LAUNCH_2D(ctx, k_nlq_feed, cb, (unsigned)ni, 64, circuit_type, d_fj, capacity, d->n_ops);
+    ZKW_LAUNCH_D(ctx, (k_nlq_fill), "k_nlq_fill", dim3((capacity + 3) / 4, d->n_ops, (unsigned)ni), 64, 0, nc->dev, nc->free_home, nc->link_home, *d, d_jobs, capacity, n_rows);
+    return ZKW_OK;
 }
 
 // ---- the closed-form section (include/zkw_netlist_closed_form.h; netlist_closed_form_kernels.cuh) of the instances first_index + k of a
@@ -1094,7 +1071,7 @@ int nlcf_begin(zkw_ctx* ctx, int circuit_type, const typename T::Inst* d_inst, s
     if (jobs.empty()) return ZKW_OK;
     if (ctx->batched() || on_main_stream) {  // a context of a batch has one stream: the sponges of all the group's blocks travel as one launch, behind the fills
                                              // (on_main_stream: the caller's own fork is open — ECRecover's EC section)
-        ZKW_LAUNCH_D(ctx, (k_nlcf_sponges<T>), "k_nlcf_sponges", dim3((unsigned)jobs.size()), 256, 0, *d, d_inst, (const NlcfJob*)call->d_jobs, S->g, n_rows, (u64)nlcf_first_row(circuit_type, S, cycles));
+        ZKW_LAUNCH_D(no_span(ctx), (k_nlcf_sponges<T>), "k_nlcf_sponges", dim3((unsigned)jobs.size()), 256, 0, *d, d_inst, (const NlcfJob*)call->d_jobs, S->g, n_rows, (u64)nlcf_first_row(circuit_type, S, cycles));
         return ZKW_OK;
     }
     hipStream_t side = nullptr;
@@ -1113,8 +1090,8 @@ int nlcf_end(zkw_ctx* ctx, int circuit_type, const NlcfCall& call, u32 cycles, s
     if (cells == 0) return ZKW_OK;
     const nlq_desc* qd = nlq_desc_of(circuit_type);
     const nlq_desc none{};
-    { Prof _p(ctx, "k_nlcf_ties"); ZKW_LAUNCH_2D(ctx, k_nlcf_ties, (cells + 255) / 256, (unsigned)call.n, 256, *d, qd ? *qd : none, nc->dev, call.d_jobs, cycles, n_rows, (u64)nlcf_first_row(circuit_type, &nc->host.s, cycles)); }
-    return launch_check("k_nlcf_ties");
+    ZKW_LAUNCH_2D(ctx, k_nlcf_ties, (cells + 255) / 256, (unsigned)call.n, 256, *d, qd ? *qd : none, nc->dev, call.d_jobs, cycles, n_rows, (u64)nlcf_first_row(circuit_type, &nc->host.s, cycles));
+    return ZKW_OK;
 }
 
 // ---- the EC section of the ECRecover circuit (ecrecover_kernels.cuh): the spec on the device, once per device
@@ -1212,6 +1189,7 @@ int ec_get(zkw_ctx* ctx, const EcCached** out) {
 }
 
 int nl_check(zkw_ctx* ctx, int circuit_type, const zkw_trace* t, size_t slot, u32 capacity, uint64_t* n_violations, uint64_t* first_bad) {
+    ZKW_TRY(direct_only(ctx, "nl_check"));  // (as check_satisfied: the same calls for the init, the memset and the kernels)
     const NlCached* nc = nullptr;
     ZKW_TRY(nl_get(ctx, circuit_type, &nc));
     const nl_spec& S = nc->host.s;
@@ -1228,36 +1206,29 @@ int nl_check(zkw_ctx* ctx, int circuit_type, const zkw_trace* t, size_t slot, u3
     CheckResult init{0ull, ~0ull};
     HIP_TRY(ctx->copy_async(d_res, &init, sizeof init, hipMemcpyHostToDevice));
     HIP_TRY(ctx->memset_async(d_hist, 0, S.total_table_rows * sizeof(u32)));
-    { Prof _p(ctx, "k_nl_check_steps"); hipLaunchKernelGGL(k_nl_check_steps, dim3((nc->host.max_items + 255) / 256, capacity * S.steps_per_cycle), dim3(256), 0, ctx->stream, nc->dev, trace, capacity, n_rows, d_hist, d_res); }
-    ZKW_TRY(launch_check("k_nl_check_steps"));
+    ZKW_TRY(launch_direct(ctx, "k_nl_check_steps", k_nl_check_steps, dim3((nc->host.max_items + 255) / 256, capacity * S.steps_per_cycle), dim3(256), 0, nc->dev, trace, capacity, n_rows, d_hist, d_res));
     u64 e_begin = 0, e_end = 0;
     if (circuit_type == 7) {  // the EC section below the queue section: its own checker, which adds its lookups to the histogram first
         const EcCached* ec = nullptr;
         ZKW_TRY(ec_get(ctx, &ec));
         e_begin = ec_first_row(capacity); e_end = ec_used_rows(capacity);
         if (e_end > n_rows) return fail(ZKW_ERR_INVALID, "capacity does not fit the trace");
-        { Prof _p(ctx, "k_ec_check_items"); hipLaunchKernelGGL(k_ec_check_items, dim3((EC_MAX_ITEMS + 255) / 256, ec->segments_per_cycle, capacity), dim3(256), 0, ctx->stream, ec->dev, trace, capacity, n_rows, (size_t)e_begin, d_res); }
-        ZKW_TRY(launch_check("k_ec_check_items"));
-        { Prof _p(ctx, "k_ec_check_rows"); hipLaunchKernelGGL(k_ec_check_rows, dim3((EC_ROWS_PER_CYCLE + 63) / 64, capacity), dim3(64), 0, ctx->stream, ec->dev, nc->dev, *qd, trace, capacity, n_rows, (size_t)e_begin, d_hist, d_res); }
-        ZKW_TRY(launch_check("k_ec_check_rows"));
-        { Prof _p(ctx, "k_ec_check_links"); hipLaunchKernelGGL(k_ec_check_links, dim3(capacity), dim3(128), 0, ctx->stream, ec->dev, nc->dev, nc->free_home, trace, n_rows, (size_t)e_begin, d_res); }
-        ZKW_TRY(launch_check("k_ec_check_links"));
+        ZKW_TRY(launch_direct(ctx, "k_ec_check_items", k_ec_check_items, dim3((EC_MAX_ITEMS + 255) / 256, ec->segments_per_cycle, capacity), dim3(256), 0, ec->dev, trace, capacity, n_rows, (size_t)e_begin, d_res));
+        ZKW_TRY(launch_direct(ctx, "k_ec_check_rows", k_ec_check_rows, dim3((EC_ROWS_PER_CYCLE + 63) / 64, capacity), dim3(64), 0, ec->dev, nc->dev, *qd, trace, capacity, n_rows, (size_t)e_begin, d_hist, d_res));
+        ZKW_TRY(launch_direct(ctx, "k_ec_check_links", k_ec_check_links, dim3(capacity), dim3(128), 0, ec->dev, nc->dev, nc->free_home, trace, n_rows, (size_t)e_begin, d_res));
     }
-    { Prof _p(ctx, "k_nl_check_tail"); hipLaunchKernelGGL(k_nl_check_tail, dim3(1024), dim3(256), 0, ctx->stream, nc->dev, trace, capacity, n_rows, d_hist, d_res, (u64)NL_USED_ROWS(&S, capacity), (u64)nlq_used_rows(&S, qd, capacity), e_begin, e_end,
-                                                        (u64)nlcf_first_row(circuit_type, &S, capacity), (u64)nlcf_used_rows(circuit_type, &S, capacity)); }
-    ZKW_TRY(launch_check("k_nl_check_tail"));
+    ZKW_TRY(launch_direct(ctx, "k_nl_check_tail", k_nl_check_tail, dim3(1024), dim3(256), 0, nc->dev, trace, capacity, n_rows, d_hist, d_res, (u64)NL_USED_ROWS(&S, capacity), (u64)nlq_used_rows(&S, qd, capacity), e_begin, e_end,
+                                                        (u64)nlcf_first_row(circuit_type, &S, capacity), (u64)nlcf_used_rows(circuit_type, &S, capacity)));
     if (const nlcf_desc* cd = nlcf_desc_of(circuit_type)) {  // the closed-form section: its own checker (its lookup cells: the tail kernel)
         u32 ties = 0;
         for (u32 gi = 0; gi < cd->n_groups; gi++) ties += cd->g[gi].count;
         const u32 tie_blocks = (ties + 255) / 256, perm_blocks = (nlcf_n_perms(cd) + 15) / 16;
         const nlq_desc none{};
-        { Prof _p(ctx, "k_nlcf_check"); hipLaunchKernelGGL(k_nlcf_check, dim3(tie_blocks + perm_blocks + 1), dim3(256), 0, ctx->stream, *cd, qd ? *qd : none, nc->dev, trace, capacity, n_rows,
-                                                         (u64)nlcf_first_row(circuit_type, &S, capacity), tie_blocks, perm_blocks, d_res); }
-        ZKW_TRY(launch_check("k_nlcf_check"));
+        ZKW_TRY(launch_direct(ctx, "k_nlcf_check", k_nlcf_check, dim3(tie_blocks + perm_blocks + 1), dim3(256), 0, *cd, qd ? *qd : none, nc->dev, trace, capacity, n_rows,
+                                                         (u64)nlcf_first_row(circuit_type, &S, capacity), tie_blocks, perm_blocks, d_res));
     }
     if (qd) {
-        { Prof _p(ctx, "k_nlq_check"); hipLaunchKernelGGL(k_nlq_check, dim3((capacity + 63) / 64, qd->n_ops), dim3(64), 0, ctx->stream, nc->dev, nc->free_home, *qd, *nlq_rels_of(circuit_type), trace, capacity, n_rows, d_res); }
-        ZKW_TRY(launch_check("k_nlq_check"));
+        ZKW_TRY(launch_direct(ctx, "k_nlq_check", k_nlq_check, dim3((capacity + 63) / 64, qd->n_ops), dim3(64), 0, nc->dev, nc->free_home, *qd, *nlq_rels_of(circuit_type), trace, capacity, n_rows, d_res));
     }
     CheckResult res;
     ZKW_TRY(ctx->read_small(&res, d_res, sizeof res));
@@ -1376,24 +1347,18 @@ static int ecrecover_synthesize_many(zkw_ctx* ctx, zkw_precompile_witness* const
             jobs[k] = EcJob{ws[w_of[k]]->mem_q, inst[k].first_round, inst[k].n_active, d_inputs + k * capacity * (size_t)128, d_tape + k * tape_per_instance,
                             inst[k].t->data + inst[k].slot * inst[k].t->slot_elems(), prep[k].hdr_bits, prep[k].free_elems, prep[k].state_before};
         ZKW_TRY(ctx->upload("ec_jobs", jobs, &d_jobs));
-        { Prof _p(ctx, "k_ec_inputs"); ZKW_LAUNCH_2D(ctx, k_ec_inputs, capacity, nj, 128, d_jobs); }
-        ZKW_TRY(launch_check("k_ec_inputs"));
+        ZKW_LAUNCH_2D(ctx, k_ec_inputs, capacity, nj, 128, d_jobs);
         if (serial) {
-            { Prof _p(ctx, "k_ec_tape"); ZKW_LAUNCH_2D(ctx, k_ec_tape, (capacity + EC_TAPE_LANES - 1) / EC_TAPE_LANES, nj, EC_TAPE_LANES, ec->dev, d_jobs, capacity, d_status); }
-            ZKW_TRY(launch_check("k_ec_tape"));
+            ZKW_LAUNCH_2D(ctx, k_ec_tape, (capacity + EC_TAPE_LANES - 1) / EC_TAPE_LANES, nj, EC_TAPE_LANES, ec->dev, d_jobs, capacity, d_status);
         } else {
             EcChainScratch sc{};
             ZKW_TRY(ctx->scratch_t<ec_jac>("ec_chain_pts", ni * capacity * (size_t)EC_CHAIN_POINTS, &sc.pts));
-            { Prof _p(ctx, "k_ec_chain"); ZKW_LAUNCH_2D(ctx, k_ec_chain, capacity, nj, 64, ec->dev, d_jobs, capacity, d_status, sc); }
-            ZKW_TRY(launch_check("k_ec_chain"));
-            { Prof _p(ctx, "k_ec_affine"); ZKW_LAUNCH(ctx, k_ec_affine, ((size_t)n_cycles * EC_CHAIN_POINTS + 63) / 64, 64, ec->dev, d_jobs, capacity, n_cycles, d_status, sc); }
-            ZKW_TRY(launch_check("k_ec_affine"));
-            { Prof _p(ctx, "k_ec_segments_main"); ZKW_LAUNCH_2D(ctx, k_ec_segments, ec->n_main, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_main, d_status); }
-            ZKW_TRY(launch_check("k_ec_segments"));
+            ZKW_LAUNCH_2D(ctx, k_ec_chain, capacity, nj, 64, ec->dev, d_jobs, capacity, d_status, sc);
+            ZKW_LAUNCH(ctx, k_ec_affine, ((size_t)n_cycles * EC_CHAIN_POINTS + 63) / 64, 64, ec->dev, d_jobs, capacity, n_cycles, d_status, sc);
+            ZKW_LAUNCH_2D(span_as(ctx, "k_ec_segments_main"), k_ec_segments, ec->n_main, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_main, d_status);
         }
         // the netlist's inputs need the globals (PRE's MAIN: the chain kernel) and the state POST leaves (its MAIN) only
-        { Prof _p(ctx, "k_ec_prepare"); ZKW_LAUNCH_2D(ctx, k_ec_prepare, cb, nj, 64, ec->dev, d_jobs, capacity); }
-        ZKW_TRY(launch_check("k_ec_prepare"));
+        ZKW_LAUNCH_2D(ctx, k_ec_prepare, cb, nj, 64, ec->dev, d_jobs, capacity);
         if (!serial) {
             // the rest of the EC section — MUL rows, leaves, the rows themselves — beside the netlist's fill, histogram and queue section:
             // on the side stream (a context of a batch has one stream: behind the fills there)
@@ -1407,10 +1372,8 @@ static int ecrecover_synthesize_many(zkw_ctx* ctx, zkw_precompile_witness* const
                 Launcher<&k_ec_stream, EC_STREAM_THREADS>::S::template single<&k_ec_stream, EC_STREAM_THREADS>(st, stream_grid, 0, ec->stream, (const EcJob*)d_jobs, capacity, n_rows, ec_first_row(capacity), d_keys);
                 ZKW_TRY(launch_check("k_ec_stream"));
             } else {
-                { Prof _p(ctx, "k_ec_segments_muls"); ZKW_LAUNCH_2D(ctx, k_ec_segments, ec->n_muls, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_muls, d_status); }
-                ZKW_TRY(launch_check("k_ec_segments"));
-                { Prof _p(ctx, "k_ec_leaves"); ZKW_LAUNCH_2D(ctx, k_ec_leaves, ec->n_leaves, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_leaves, d_status); }
-                ZKW_TRY(launch_check("k_ec_leaves"));
+                ZKW_LAUNCH_2D(span_as(ctx, "k_ec_segments_muls"), k_ec_segments, ec->n_muls, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_muls, d_status);
+                ZKW_LAUNCH_2D(ctx, k_ec_leaves, ec->n_leaves, chunks, EC_TAPE_LANES, ec->dev, d_jobs, capacity, n_cycles, ec->tasks_leaves, d_status);
             }
         }
         return ZKW_OK;
@@ -1432,10 +1395,9 @@ static int ecrecover_synthesize_many(zkw_ctx* ctx, zkw_precompile_witness* const
         ZKW_TRY(nlcf_end(ctx, 7, cf, capacity, n_rows));
     }
     if (forked) ZKW_TRY(ctx->side_join());
-    else { Prof _p(ctx, "k_ec_stream"); ZKW_LAUNCH_D(ctx, (k_ec_stream), "k_ec_stream", stream_grid, EC_STREAM_THREADS, 0, ec->stream, d_jobs, capacity, n_rows, ec_first_row(capacity), d_keys); }
+    else ZKW_LAUNCH_D(ctx, (k_ec_stream), "k_ec_stream", stream_grid, EC_STREAM_THREADS, 0, ec->stream, d_jobs, capacity, n_rows, ec_first_row(capacity), d_keys);
     // the Xor8 multiplicities onto the column the netlist's finish kernel has written
-    { Prof _p(ctx, "k_ec_hist"); ZKW_LAUNCH_2D(ctx, k_ec_hist, 2, nj, EC_HIST_THREADS, ec->stream, d_jobs, capacity, n_rows, ec_first_row(capacity), (u32)EK_MULT_COL, d_keys); }
-    ZKW_TRY(launch_check("k_ec_hist"));
+    ZKW_LAUNCH_2D(ctx, k_ec_hist, 2, nj, EC_HIST_THREADS, ec->stream, d_jobs, capacity, n_rows, ec_first_row(capacity), (u32)EK_MULT_COL, d_keys);
     u32 status = 0;
     ZKW_TRY(ctx->read_small(&status, d_status, 4));
     if (status) return fail(ZKW_ERR_CHECK_FAILED, "zkw_ecrecover_synthesize: request %llu (instance %u of the call) has no witness (the accumulator of the incomplete addition met x1 == x2)",
@@ -1548,7 +1510,7 @@ extern "C" int zkw_storage_application_synthesize(zkw_ctx* ctx, zkw_storage_appl
     const u32 capacity = w->capacity;
     NlcfCall cf;
     SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize_with(ctx, 10, [&](std::vector<NlPrepJob>& prep) {
+    ZKW_TRY(nl_synthesize_with(ctx, 10, [&](std::vector<NlPrepJob>& prep) -> int {
         std::vector<SapWalkJob> jobs(prep.size());
         for (size_t k = 0; k < prep.size(); k++)
             jobs[k] = SapWalkJob{w->items, w->keys, w->paths, w->walk_hashes, w->n ? prep[k].first_round : 0, w->n ? prep[k].n_active : 0, prep[k].hdr_bits, prep[k].free_elems, prep[k].state_before,
@@ -1556,8 +1518,8 @@ extern "C" int zkw_storage_application_synthesize(zkw_ctx* ctx, zkw_storage_appl
                                      offsetof(zkw_storage_application_fsm, current_root_hash)};
         SapWalkJob* d_jobs = nullptr;
         ZKW_TRY(ctx->upload("sap_walk_jobs", jobs, &d_jobs));
-        { Prof _p(ctx, "k_sap_walk_cycles"); ZKW_LAUNCH_2D(ctx, k_sap_walk_cycles, (capacity * SAP_WALK_CYCLES + 256) / 256, (unsigned)jobs.size(), 256, d_jobs, capacity); }
-        return launch_check("k_sap_walk_cycles");
+        ZKW_LAUNCH_2D(ctx, k_sap_walk_cycles, (capacity * SAP_WALK_CYCLES + 256) / 256, (unsigned)jobs.size(), 256, d_jobs, capacity);
+        return ZKW_OK;
     }, inst, capacity * SA_CYCLES_PER_WALK, t->n_rows, [&] {
         return nlcf_begin<CfStorageApplication>(ctx, 10, w->instances, first_instance, inst, capacity * SA_CYCLES_PER_WALK, t->n_rows, &cf);
     }, &claims));
@@ -1603,10 +1565,8 @@ extern "C" int zkw_linear_hasher_synthesize_batch_with_tails(zkw_ctx* ctx, const
     ZKW_TRY(ctx->scratch_t<uint8_t>("lh_hash", 32 * n_queues, &d_hash));
     ZKW_TRY(ctx->upload("lh_moff", moff, &d_moff));
     ZKW_TRY(ctx->upload("lh_roff", roff, &d_roff));
-    { Prof _p(ctx, "k_linear_blocks"); ZKW_LAUNCH(ctx, k_linear_blocks, blocks_for(roff[n_queues] * 18, 256), 256, d_q, d_moff, d_roff, (u32)n_queues, d_rounds); }
-    ZKW_TRY(launch_check("k_linear_blocks"));
-    { Prof _p(ctx, "k_linear_keccak256"); ZKW_LAUNCH(ctx, k_linear_keccak256, (unsigned)n_queues, 64, d_q, (size_t)0, d_hash, d_rounds, d_moff, d_roff, true); }
-    ZKW_TRY(launch_check("k_linear_keccak256"));
+    ZKW_LAUNCH(ctx, k_linear_blocks, blocks_for(roff[n_queues] * 18, 256), 256, d_q, d_moff, d_roff, (u32)n_queues, d_rounds);
+    ZKW_LAUNCH(ctx, k_linear_keccak256, (unsigned)n_queues, 64, d_q, (size_t)0, d_hash, d_rounds, d_moff, d_roff, true);
     std::vector<zkw_linear_hasher_instance> recv(n_queues);
     std::vector<uint8_t> hashes(32 * n_queues);
     ZKW_TRY(ctx->read_small(hashes.data(), d_hash, hashes.size()));
@@ -1621,13 +1581,8 @@ extern "C" int zkw_linear_hasher_synthesize_batch_with_tails(zkw_ctx* ctx, const
     u64 *d_cf = nullptr, *d_pi = nullptr;
     ZKW_TRY(ctx->scratch_t<u64>("lh_cf", COMPACT_FORM_LEN * n_queues, &d_cf));
     ZKW_TRY(ctx->scratch_t<u64>("lh_pi", 4 * n_queues, &d_pi));
-    {
-        Prof _p(ctx, "k_closed_form_commitments");
-        ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<CfLinearHasher>), "k_closed_form_commitments", (unsigned)n_queues, 64, d_rec, n_queues, d_cf);
-    }
-    ZKW_TRY(launch_check("k_closed_form_commitments"));
-    { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n_queues, 64), 64, d_cf, n_queues, (u32)COMPACT_FORM_LEN, d_pi); }
-    ZKW_TRY(launch_check("k_commit_encodings"));
+    ZKW_LAUNCH_T(ctx, (k_closed_form_commitments<CfLinearHasher>), "k_closed_form_commitments", (unsigned)n_queues, 64, d_rec, n_queues, d_cf);
+    ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n_queues, 64), 64, d_cf, n_queues, (u32)COMPACT_FORM_LEN, d_pi);
     std::vector<NlInstance> inst(n_queues);
     for (size_t b = 0; b < n_queues; b++) inst[b] = NlInstance{roff[b], (u32)(roff[b + 1] - roff[b]), d_pi + 4 * b, t, first_slot + b, true};
     NlcfCall cf;
@@ -1643,8 +1598,7 @@ extern "C" int zkw_linear_hasher_synthesize_batch_with_tails(zkw_ctx* ctx, const
             std::vector<u64> heads(4 * n_queues);
             for (size_t b = 0; b < n_queues; b++) memcpy(&heads[4 * b], queue_states[b].head, 32);
             ZKW_TRY(ctx->upload("lh_heads", heads, &d_heads));
-            { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, blocks_for(total, 256), 256, d_q, total, (const u32*)nullptr, d_enc); }
-            ZKW_TRY(launch_check("k_encode_log"));
+            ZKW_LAUNCH(ctx, k_encode_log, blocks_for(total, 256), 256, d_q, total, (const u32*)nullptr, d_enc);
             std::vector<LogChainJob> chains;
             for (size_t b = 0; b < n_queues; b++)
                 if (moff[b + 1] > moff[b]) chains.push_back(LogChainJob{d_enc + 20 * moff[b], nullptr, nullptr, d_new + 4 * moff[b], d_heads + 4 * b, moff[b + 1] - moff[b]});

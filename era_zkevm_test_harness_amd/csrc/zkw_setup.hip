@@ -544,8 +544,7 @@ extern "C" int zkw_check_copy_permutation(zkw_ctx* ctx, const zkw_trace* t, size
     ZKW_TRY(ctx->scratch_t<CheckResult>("check_res", 1, &d_res));
     CheckResult init{0ull, ~0ull};
     HIP_TRY(hipMemcpyAsync(d_res, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-    { Prof _p(ctx, "k_check_sigma"); hipLaunchKernelGGL(k_check_sigma, dim3(2048), dim3(256), 0, ctx->stream, t->data + slot * t->slot_elems(), d_sigma, n_cells, d_res, t->n_rows); }
-    ZKW_TRY(launch_check("k_check_sigma"));
+    ZKW_TRY(launch_direct(ctx, "k_check_sigma", k_check_sigma, dim3(2048), dim3(256), 0, t->data + slot * t->slot_elems(), d_sigma, n_cells, d_res, t->n_rows));
     CheckResult res;
     ZKW_TRY(ctx->read_small(&res, d_res, sizeof res));
     *n_violations = res.violations;

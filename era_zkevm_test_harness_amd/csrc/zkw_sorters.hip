@@ -40,8 +40,7 @@ static int decommit_prepare(zkw_ctx* ctx, zkw_decommit_witness* w, const zkw_dec
     const size_t n = w->n;
     const unsigned grid = blocks_for(n, 256);
     // unsorted side
-    { Prof _p(ctx, "k_encode_decommit"); ZKW_LAUNCH(ctx, k_encode_decommit, grid, 256, d_q, n, w->unsorted_enc); }
-    ZKW_TRY(launch_check("k_encode_decommit"));
+    ZKW_LAUNCH(ctx, k_encode_decommit, grid, 256, d_q, n, w->unsorted_enc);
     // sort: timestamp, then the hash from its least to its most significant 64 bits (stable LSD)
     u32 *ts = nullptr, *k32 = nullptr, *v0 = nullptr, *v1 = nullptr;
     u64 *hk[4] = {nullptr, nullptr, nullptr, nullptr}, *k64a = nullptr, *k64b = nullptr;
@@ -56,18 +55,15 @@ static int decommit_prepare(zkw_ctx* ctx, zkw_decommit_witness* w, const zkw_dec
     ZKW_TRY(ctx->scratch_t<u64>("sort_k64a", n, &k64a));
     ZKW_TRY(ctx->scratch_t<u64>("sort_k64b", n, &k64b));
     ZKW_TRY(ctx->scratch("sort_tmp", tmp_bytes + 256, &tmp));
-    { Prof _p(ctx, "k_decommit_sort_keys"); ZKW_LAUNCH(ctx, k_decommit_sort_keys, grid, 256, d_q, n, ts, hk[0], hk[1], hk[2], hk[3], v0); }
-    ZKW_TRY(launch_check("k_decommit_sort_keys"));
+    ZKW_LAUNCH(ctx, k_decommit_sort_keys, grid, 256, d_q, n, ts, hk[0], hk[1], hk[2], hk[3], v0);
     { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u32>(ctx, tmp, tmp_bytes, ts, k32, v0, v1, n, 32)); }
     u32 *cur = v1, *nxt = v0;
     for (int k = 0; k < 4; k++) {
-        { Prof _p(ctx, "k_gather_u64_by_u32"); ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, hk[k], cur, n, k64a); }
-        ZKW_TRY(launch_check("k_gather_u64_by_u32"));
+        ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, hk[k], cur, n, k64a);
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, cur, nxt, n, 64)); }
         u32* t = cur; cur = nxt; nxt = t;
     }
-    { Prof _p(ctx, "k_decommit_gather_encode"); ZKW_LAUNCH(ctx, k_decommit_gather_encode, grid, 256, d_q, cur, n, w->sorted_q, w->sorted_enc); }
-    ZKW_TRY(launch_check("k_decommit_gather_encode"));
+    ZKW_LAUNCH(ctx, k_decommit_gather_encode, grid, 256, d_q, cur, n, w->sorted_q, w->sorted_enc);
     // deduplicated queue = the fresh requests in sorted order
     u32 *fresh_count = nullptr, *last_fresh = nullptr, *totals = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("dec_fresh", n, &fresh_count));
@@ -78,10 +74,8 @@ static int decommit_prepare(zkw_ctx* ctx, zkw_decommit_witness* w, const zkw_dec
     ZKW_TRY(ctx->scratch_t<u32>("dec_fresh_pos", n, &fresh_pos));
     HIP_TRY(ctx->memset_async(totals, 0, 2 * sizeof(u32)));
     ZKW_TRY(flag_prefix(ctx, "k_decommit_fresh_prefix", DecommitFreshFlag{w->sorted_q}, n, fresh_prefix));
-    { Prof _p(ctx, "k_decommit_dedup"); ZKW_LAUNCH(ctx, k_decommit_dedup, grid, 256, w->sorted_q, w->sorted_enc, n, fresh_prefix, fresh_count, fresh_pos, w->dedup_q, w->dedup_enc, totals); }
-    ZKW_TRY(launch_check("k_decommit_dedup"));
-    { Prof _p(ctx, "k_decommit_last_fresh"); ZKW_LAUNCH(ctx, k_decommit_last_fresh, grid, 256, fresh_count, fresh_pos, n, last_fresh); }
-    ZKW_TRY(launch_check("k_decommit_last_fresh"));
+    ZKW_LAUNCH(ctx, k_decommit_dedup, grid, 256, w->sorted_q, w->sorted_enc, n, fresh_prefix, fresh_count, fresh_pos, w->dedup_q, w->dedup_enc, totals);
+    ZKW_LAUNCH(ctx, k_decommit_last_fresh, grid, 256, fresh_count, fresh_pos, n, last_fresh);
     u32 h_totals[2] = {0, 0};
     ZKW_TRY(ctx->read_small(h_totals, totals, sizeof h_totals));
     if (h_totals[1]) return fail(ZKW_ERR_CHECK_FAILED, "decommit requests with the same hash disagree on page or are not "
@@ -117,8 +111,8 @@ static int decommit_finish(zkw_ctx* ctx, zkw_decommit_witness* w) {
                            fresh_count, last_fresh, w->instances, dedup_in, n, w->capacity};
     DecommitBlock* d_blk = nullptr;
     ZKW_TRY(ctx->upload("dec_block", blk, &d_blk));
-    { Prof _p(ctx, "k_decommit_instances"); ZKW_LAUNCH(ctx, k_decommit_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    return launch_check("k_decommit_instances");
+    ZKW_LAUNCH(ctx, k_decommit_instances, blocks_for(w->n_instances, 64), 64, d_blk);
+    return ZKW_OK;
 }
 
 extern "C" void zkw_decommit_witness_free(zkw_decommit_witness* w);
@@ -172,12 +166,8 @@ extern "C" int zkw_decommit_sorter_finish(zkw_ctx* ctx, zkw_decommit_witness* w)
     int rc = decommit_finish(ctx, w);
     if (rc == ZKW_OK) {  // a20: compact forms and public inputs (postprocessing/mod.rs:353-369)
         const size_t ni = w->n_instances;
-        { Prof _p(ctx, "k_ds_commitments"); ZKW_LAUNCH(ctx, k_ds_commitments, blocks_for(4 * ni, 64), 64, w->instances, ni, w->compact_forms); }
-        rc = launch_check("k_ds_commitments");
-        if (rc == ZKW_OK) {
-            { Prof _p(ctx, "k_commit_encodings"); ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, w->compact_forms, ni, (u32)COMPACT_FORM_LEN, w->public_inputs); }
-            rc = launch_check("k_commit_encodings");
-        }
+        ZKW_LAUNCH(ctx, k_ds_commitments, blocks_for(4 * ni, 64), 64, w->instances, ni, w->compact_forms);
+        ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(ni, 64), 64, w->compact_forms, ni, (u32)COMPACT_FORM_LEN, w->public_inputs);
     }
     if (rc == ZKW_OK) rc = ctx->sync_if_host();
     if (rc == ZKW_OK && ctx->ptr_mode == ZKW_PTR_HOST) {  // lhs == rhs at the end (utils.rs:685-696)
@@ -262,8 +252,7 @@ static int events_run(zkw_ctx* ctx, zkw_events_witness* w, const zkw_log_query* 
     const unsigned grid = blocks_for(n, 256);
     u64 *u_enc = w->enc_all, *s_enc = w->enc_all + 20 * n, *r_enc = w->enc_all + 40 * n;
     u64 *u_old = w->tails_all, *u_new = u_old + 4 * n, *s_old = u_new + 4 * n, *s_new = s_old + 4 * n, *r_new = s_new + 4 * n;
-    { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)nullptr, u_enc); }
-    ZKW_TRY(launch_check("k_encode_log"));
+    ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)nullptr, u_enc);
     // stable sort by (timestamp, rollback): 33-bit key
     u64 *key = nullptr, *key_out = nullptr;
     u32 *v0 = nullptr, *v1 = nullptr, *kept = nullptr, *totals = nullptr;
@@ -274,19 +263,16 @@ static int events_run(zkw_ctx* ctx, zkw_events_witness* w, const zkw_log_query* 
     ZKW_TRY(ctx->scratch_t<u32>("sort_v0", n, &v0));
     ZKW_TRY(ctx->scratch_t<u32>("sort_v1", n, &v1));
     ZKW_TRY(ctx->scratch("sort_tmp", tmp_bytes + 256, &tmp));
-    { Prof _p(ctx, "k_events_sort_keys"); ZKW_LAUNCH(ctx, k_events_sort_keys, grid, 256, d_q, n, key, v0); }
-    ZKW_TRY(launch_check("k_events_sort_keys"));
+    ZKW_LAUNCH(ctx, k_events_sort_keys, grid, 256, d_q, n, key, v0);
     { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, key, key_out, v0, v1, n, 33)); }
-    { Prof _p(ctx, "k_log_gather_encode"); ZKW_LAUNCH(ctx, k_log_gather_encode, grid, 256, d_q, v1, n, w->sorted_q, s_enc); }
-    ZKW_TRY(launch_check("k_log_gather_encode"));
+    ZKW_LAUNCH(ctx, k_log_gather_encode, grid, 256, d_q, v1, n, w->sorted_q, s_enc);
     ZKW_TRY(ctx->scratch_t<u32>("evt_kept", n, &kept));
     ZKW_TRY(ctx->scratch_t<u32>("evt_totals", 2, &totals));
     u32* kept_prefix = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("evt_kept_prefix", n + 1, &kept_prefix));
     HIP_TRY(ctx->memset_async(totals, 0, 2 * sizeof(u32)));
     ZKW_TRY(flag_prefix(ctx, "k_events_kept_prefix", EventsKeptFlag{w->sorted_q, n}, n, kept_prefix));
-    { Prof _p(ctx, "k_events_dedup"); ZKW_LAUNCH(ctx, k_events_dedup, grid, 256, w->sorted_q, n, kept_prefix, kept, w->result_q, r_enc, totals); }
-    ZKW_TRY(launch_check("k_events_dedup"));
+    ZKW_LAUNCH(ctx, k_events_dedup, grid, 256, w->sorted_q, n, kept_prefix, kept, w->result_q, r_enc, totals);
     u32 h_totals[2] = {0, 0};
     ZKW_TRY(ctx->read_small(h_totals, totals, sizeof h_totals));
     if (h_totals[1]) return fail(ZKW_ERR_CHECK_FAILED, "event queue is not a sequence of forward events each optionally followed by "
@@ -311,8 +297,8 @@ static int events_run(zkw_ctx* ctx, zkw_events_witness* w, const zkw_log_query* 
     blk[0] = EventsBlock{w->sorted_q, u_new, s_new, r_new, w->lhs_z, w->rhs_z, kept, w->instances, result_in, n, w->capacity};
     EventsBlock* d_blk = nullptr;
     ZKW_TRY(ctx->upload("evt_block", blk, &d_blk));
-    { Prof _p(ctx, "k_events_instances"); ZKW_LAUNCH(ctx, k_events_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    return launch_check("k_events_instances");
+    ZKW_LAUNCH(ctx, k_events_instances, blocks_for(w->n_instances, 64), 64, d_blk);
+    return ZKW_OK;
 }
 
 extern "C" int zkw_events_sorter_build(zkw_ctx* ctx, const zkw_log_query* q, size_t n, uint32_t capacity,
@@ -437,15 +423,12 @@ static int demux_run(zkw_ctx* ctx, zkw_demux_witness* w, const zkw_log_query* d_
     const size_t n = w->n;
     u64 *in_enc = w->enc_all, *out_enc = w->enc_all + 20 * n;
     u64 *in_old = w->tails_all, *in_new = in_old + 4 * n, *out_old = in_new + 4 * n, *out_new = out_old + 4 * n;
-    { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, blocks_for(n, 256), 256, d_q, n, (const u32*)nullptr, in_enc); }
-    ZKW_TRY(launch_check("k_encode_log"));
+    ZKW_LAUNCH(ctx, k_encode_log, blocks_for(n, 256), 256, d_q, n, (const u32*)nullptr, in_enc);
     u32* route_count = w->route_count;
     HIP_TRY(ctx->memset_async(w->d_offsets, 0, 8 * sizeof(u64)));
     ZKW_TRY((route_prefix<6>(ctx, "k_demux_route_prefix", DemuxRoute{d_q, params}, n, route_count)));
-    ZKW_LAUNCH(ctx, k_demux_offsets, 1, 64, route_count, n, w->d_offsets);
-    ZKW_TRY(launch_check("k_demux_offsets"));
-    { Prof _p(ctx, "k_demux_route"); ZKW_LAUNCH(ctx, k_demux_route, blocks_for(n, 256), 256, d_q, in_enc, n, params, route_count, w->out_q, out_enc, w->d_offsets); }
-    ZKW_TRY(launch_check("k_demux_route"));
+    ZKW_LAUNCH(no_span(ctx), k_demux_offsets, 1, 64, route_count, n, w->d_offsets);
+    ZKW_LAUNCH(ctx, k_demux_route, blocks_for(n, 256), 256, d_q, in_enc, n, params, route_count, w->out_q, out_enc, w->d_offsets);
     u64 h_tot[8];
     ZKW_TRY(ctx->read_small(h_tot, w->d_offsets, sizeof h_tot));
     if (h_tot[7]) return fail(ZKW_ERR_CHECK_FAILED, "%llu log queries have an aux byte / shard / rollback combination the "
@@ -469,8 +452,8 @@ static int demux_run(zkw_ctx* ctx, zkw_demux_witness* w, const zkw_log_query* d_
     blk[0].capacity = w->capacity;
     DemuxBlock* d_blk = nullptr;
     ZKW_TRY(ctx->upload("dmx_block", blk, &d_blk));
-    { Prof _p(ctx, "k_demux_instances"); ZKW_LAUNCH(ctx, k_demux_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    return launch_check("k_demux_instances");
+    ZKW_LAUNCH(ctx, k_demux_instances, blocks_for(w->n_instances, 64), 64, d_blk);
+    return ZKW_OK;
 }
 
 extern "C" int zkw_log_demux_build(zkw_ctx* ctx, const zkw_log_query* q, size_t n, uint32_t capacity,
@@ -596,27 +579,21 @@ static int storage_run(zkw_ctx* ctx, zkw_storage_witness* w, const zkw_log_query
     ZKW_TRY(ctx->scratch("sort_tmp", tmp_bytes + 256, &tmp));
     u32* iota = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("ssort_iota", n, &iota));
-    { Prof _p(ctx, "k_storage_sort_keys"); ZKW_LAUNCH(ctx, k_storage_sort_keys, grid, 256, d_q, n, kk[0], kk[1], kk[2], kk[3], kk[4], kk[5], a2, iota); }
-    ZKW_TRY(launch_check("k_storage_sort_keys"));
+    ZKW_LAUNCH(ctx, k_storage_sort_keys, grid, 256, d_q, n, kk[0], kk[1], kk[2], kk[3], kk[4], kk[5], a2, iota);
     // plain and extended encodings of the unsorted side
-    { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)nullptr, u_enc); }
-    ZKW_TRY(launch_check("k_encode_log"));
-    { Prof _p(ctx, "k_encode_log"); ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)iota, w->lhs_enc); }
-    ZKW_TRY(launch_check("k_encode_log"));
+    ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)nullptr, u_enc);
+    ZKW_LAUNCH(ctx, k_encode_log, grid, 256, d_q, n, (const u32*)iota, w->lhs_enc);
     HIP_TRY(ctx->copy_async(v0, iota, n * sizeof(u32), hipMemcpyDeviceToDevice));
     u32 *cur = v0, *nxt = v1;
     for (int k = 0; k < 6; k++) {
-        { Prof _p(ctx, "k_gather_u64_by_u32"); ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, kk[k], cur, n, k64a); }
-        ZKW_TRY(launch_check("k_gather_u64_by_u32"));
+        ZKW_LAUNCH(ctx, k_gather_u64_by_u32, grid, 256, kk[k], cur, n, k64a);
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, cur, nxt, n, 64)); }
         u32* t = cur; cur = nxt; nxt = t;
     }
-    { Prof _p(ctx, "k_gather_u32_by_u32"); ZKW_LAUNCH(ctx, k_gather_u32_by_u32, grid, 256, a2, cur, n, k32a); }
-    ZKW_TRY(launch_check("k_gather_u32_by_u32"));
+    ZKW_LAUNCH(ctx, k_gather_u32_by_u32, grid, 256, a2, cur, n, k32a);
     { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u32>(ctx, tmp, tmp_bytes, k32a, k32b, cur, nxt, n, 32)); }
     { u32* t = cur; cur = nxt; nxt = t; }
-    { Prof _p(ctx, "k_storage_gather_encode"); ZKW_LAUNCH(ctx, k_storage_gather_encode, grid, 256, d_q, cur, n, w->sorted_q, w->sorted_ext, s_enc); }
-    ZKW_TRY(launch_check("k_storage_gather_encode"));
+    ZKW_LAUNCH(ctx, k_storage_gather_encode, grid, 256, d_q, cur, n, w->sorted_q, w->sorted_ext, s_enc);
     // per-cell registers and the deduplicated queue
     StorageScan sc;
     u32* totals = nullptr;
@@ -637,14 +614,11 @@ static int storage_run(zkw_ctx* ctx, zkw_storage_witness* w, const zkw_log_query
         HIP_TRY(ctx->memset_async(totals, 0, 2 * sizeof(u32)));
         ZKW_TRY((sum_prefix<1>(ctx, "k_storage_depth_prefix", StoDelta{w->sorted_q}, n, d_dpfx, d_dtot)));
         ZKW_TRY(flag_prefix(ctx, "k_storage_start_prefix", StoIsStart{w->sorted_q}, n, d_spfx));
-        { Prof _p(ctx, "k_storage_first"); ZKW_LAUNCH(ctx, k_storage_first, grid, 256, d_spfx, n, d_first); }
-        ZKW_TRY(launch_check("k_storage_first"));
-        { Prof _p(ctx, "k_storage_ds"); ZKW_LAUNCH(ctx, k_storage_ds, grid, 256, w->sorted_q, n, d_dpfx, d_spfx, d_first, sc, totals + 1); }
-        ZKW_TRY(launch_check("k_storage_ds"));
+        ZKW_LAUNCH(ctx, k_storage_first, grid, 256, d_spfx, n, d_first);
+        ZKW_LAUNCH(ctx, k_storage_ds, grid, 256, w->sorted_q, n, d_dpfx, d_spfx, d_first, sc, totals + 1);
         ZKW_TRY(flag_prefix(ctx, "k_storage_read_prefix", StoReadAtZero{w->sorted_q, sc, totals + 1}, n, d_rpfx));
         ZKW_TRY(flag_prefix(ctx, "k_storage_emit_prefix", StoEmits{sc, d_rpfx, n}, n, d_epfx));
-        { Prof _p(ctx, "k_storage_emit"); ZKW_LAUNCH(ctx, k_storage_emit, grid, 256, w->sorted_q, n, sc, d_rpfx, d_epfx, w->result_q, r_enc, totals); }
-        ZKW_TRY(launch_check("k_storage_emit"));
+        ZKW_LAUNCH(ctx, k_storage_emit, grid, 256, w->sorted_q, n, sc, d_rpfx, d_epfx, w->result_q, r_enc, totals);
     }
     u32 h_totals[2] = {0, 0};
     ZKW_TRY(ctx->read_small(h_totals, totals, sizeof h_totals));
@@ -667,8 +641,8 @@ static int storage_run(zkw_ctx* ctx, zkw_storage_witness* w, const zkw_log_query
     blk[0] = StorageBlock{w->sorted_q, w->sorted_ext, u_new, s_new, r_new, w->lhs_z, w->rhs_z, sc, w->instances, n, w->capacity};
     StorageBlock* d_blk = nullptr;
     ZKW_TRY(ctx->upload("sto_block", blk, &d_blk));
-    { Prof _p(ctx, "k_storage_instances"); ZKW_LAUNCH(ctx, k_storage_instances, blocks_for(w->n_instances, 64), 64, d_blk); }
-    return launch_check("k_storage_instances");
+    ZKW_LAUNCH(ctx, k_storage_instances, blocks_for(w->n_instances, 64), 64, d_blk);
+    return ZKW_OK;
 }
 
 extern "C" int zkw_storage_sorter_build(zkw_ctx* ctx, const zkw_log_query* q, size_t n, uint32_t capacity,
@@ -772,15 +746,9 @@ extern "C" void zkw_storage_witness_free(zkw_storage_witness* w) { witness_free(
 //   its tail span; refuse(w, t): its own refusals, none for most; prepare(ctx, w): what its fills need and the builder did not leave (the lazy
 //   prefix); public_inputs(w); fill_job(w, job): the witness's pointers; launch_fills(..): its fill kernels in order.
 
-// one fill launch: its profile span, the launch's name, the text of its launch check
-template <auto Body, int BS, class J>
-static int launch_fill(zkw_ctx* ctx, const char* span, const char* name, const char* what, dim3 grid, const J* d_jobs, u32 capacity, size_t n_rows) {
-    { Prof _p(ctx, span); ZKW_TRY((Launcher<Body, BS>::go(ctx, name, grid, 0, d_jobs, capacity, n_rows))); }
-    return launch_check(what);
-}
-// (queue / Poseidon2 kernels: a lane per cycle in blocks of 64; row kernels: blocks of 256)
-#define FILL_Q(kernel, P) ZKW_TRY((launch_fill<&kernel<P>, 64>(ctx, #kernel, #kernel, #kernel "<" #P ">", g64, d_jobs, capacity, n_rows)));
-#define FILL_ROW(kernel, row, R, span) ZKW_TRY((launch_fill<&kernel<row>, 256>(ctx, span, #kernel, #kernel "<" #R ">", g256, d_jobs, capacity, n_rows)));
+// one fill launch (queue / Poseidon2 kernels: a lane per cycle in blocks of 64; row kernels: blocks of 256, under the span the circuit names)
+#define FILL_Q(kernel, P) ZKW_LAUNCH_D(ctx, kernel<P>, #kernel, g64, 64, 0, d_jobs, capacity, n_rows);
+#define FILL_ROW(kernel, row, span) ZKW_LAUNCH_D(span_as(ctx, span), kernel<row>, #kernel, g256, 256, 0, d_jobs, capacity, n_rows);
 
 template <class S>
 static int sorter_synthesize(zkw_ctx* ctx, typename S::W* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
@@ -823,8 +791,7 @@ static int sorter_synthesize(zkw_ctx* ctx, typename S::W* w, size_t first_instan
     const u32 rstride = (u32)C::region_stride(capacity);
     const dim3 g64((rstride + 63) / 64, nj), g256((rstride + 255) / 256, nj);
     ZKW_TRY(S::launch_fills(ctx, d_jobs, capacity, n_rows, g64, g256));
-    { Prof _p(ctx, S::TAIL); ZKW_LAUNCH_T(ctx, k_sorter_fill_tail<C>, S::TAIL, nj * ((C::G + C::L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows); }
-    ZKW_TRY(launch_check(S::TAIL));
+    ZKW_LAUNCH_T(ctx, k_sorter_fill_tail<C>, S::TAIL, nj * ((C::G + C::L + 1) * TAIL_CHUNKS + 1), 256, d_jobs, nj, capacity, n_rows);
     return claims.commit_if(ctx->sync_if_host());
 }
 
@@ -852,7 +819,7 @@ struct DsSynth {
         j.rq_len_in = w->dedup_in.length;
     }
     static int launch_fills(zkw_ctx* ctx, const DsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
-#define ROW(R) FILL_ROW(k_ds_fill_row, DS_ROW_##R, R, "k_ds_fill_row_" #R)
+#define ROW(R) FILL_ROW(k_ds_fill_row, DS_ROW_##R, "k_ds_fill_row_" #R)
         FILL_Q(k_ds_fill_poseidon, 0) FILL_Q(k_ds_fill_poseidon, 1) FILL_Q(k_ds_fill_poseidon, 2) ROW(A) ROW(B) ROW(C) ROW(D)
 #undef ROW
         return ZKW_OK;
@@ -883,7 +850,7 @@ struct EsSynth {  // events and L1 messages sorters (types 11 / 12): one layout,
         j.rq_len_in = w->result_in.length;
     }
     static int launch_fills(zkw_ctx* ctx, const EsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
-#define ROW(R) FILL_ROW(k_es_fill_row, ES_ROW_##R, R, "k_es_fill_row")
+#define ROW(R) FILL_ROW(k_es_fill_row, ES_ROW_##R, "k_es_fill_row")
         FILL_Q(k_es_fill_queue, 0) FILL_Q(k_es_fill_queue, 1) FILL_Q(k_es_fill_queue, 2)
         ROW(A) ROW(NTV) ROW(W) ROW(Q)  // NTV after the queue kernels: it writes the range checks into their rows' lookup columns
 #undef ROW
@@ -913,7 +880,7 @@ struct LdSynth {
         for (int c = 0; c < 7; c++) j.offsets[c] = w->offsets[c];
     }
     static int launch_fills(zkw_ctx* ctx, const LdSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
-#define ROW(R) FILL_ROW(k_ld_fill_row, LD_ROW_##R, R, "k_ld_fill_row")
+#define ROW(R) FILL_ROW(k_ld_fill_row, LD_ROW_##R, "k_ld_fill_row")
         FILL_Q(k_ld_fill_queue, 0) FILL_Q(k_ld_fill_queue, 1) ROW(X0) ROW(X1) ROW(X2) ROW(X3) ROW(R) ROW(Q)
 #undef ROW
         return ZKW_OK;
@@ -940,7 +907,7 @@ struct SsSynth {
         j.sc.D = reinterpret_cast<int*>(w->scans); j.sc.S = w->scans + n; j.sc.R = w->scans + 2 * n; j.sc.E = w->scans + 3 * n;
     }
     static int launch_fills(zkw_ctx* ctx, const SsSynthJob* d_jobs, u32 capacity, size_t n_rows, dim3 g64, dim3 g256) {
-#define ROW(R) FILL_ROW(k_ss_fill_row, SS_ROW_##R, R, "k_ss_fill_row")
+#define ROW(R) FILL_ROW(k_ss_fill_row, SS_ROW_##R, "k_ss_fill_row")
         FILL_Q(k_ss_fill_queue, 0) FILL_Q(k_ss_fill_queue, 1) FILL_Q(k_ss_fill_queue, 2)
         ROW(A) ROW(X0) ROW(X1) ROW(X2) ROW(X3) ROW(X4) ROW(X5) ROW(X6) ROW(X7) ROW(K) ROW(C1) ROW(C2) ROW(Q)
 #undef ROW

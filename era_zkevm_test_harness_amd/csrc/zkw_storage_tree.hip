@@ -67,8 +67,7 @@ extern "C" int zkw_storage_tree_create(zkw_ctx* ctx, size_t capacity_leaves, zkw
                          capacity_leaves * ST_BYTES_PER_LEAF, hipGetErrorString(e)));
     }
     int rc = [&]() -> int {
-        { Prof _p(ctx, "k_st_empty"); ZKW_LAUNCH(ctx, k_st_empty, 1, 64, t->empty); }
-        ZKW_TRY(launch_check("k_st_empty"));
+        ZKW_LAUNCH(ctx, k_st_empty, 1, 64, t->empty);
         return ctx->read_small(t->empty_root, t->empty + 8 * ST_DEPTH, 32);
     }();
     if (rc != ZKW_OK) return bail(rc);
@@ -114,19 +113,13 @@ static int st_rebuild(zkw_storage_tree* t) {
     }
     StBuild b{t->keys[t->cur], t->index[t->cur], t->values[t->cur], t->nodes, t->empty, t->d, t->nxt, t->root_dev, (u64)t->n, (u64)t->cap};
     const unsigned g64 = blocks_for(t->n, 64);
-    { Prof _p(ctx, "k_st_leaves"); ZKW_LAUNCH(ctx, k_st_leaves, g64, 64, b); }
-    ZKW_TRY(launch_check("k_st_leaves"));
+    ZKW_LAUNCH(ctx, k_st_leaves, g64, 64, b);
     static_assert(ZKW_STORAGE_TREE_DEPTH == ST_DEPTH, "the tree kernels walk 256 levels");
     if (t->n <= ST_PERSISTENT_MAX) {
-        Prof _p(ctx, "k_st_levels");
         ZKW_LAUNCH(ctx, k_st_levels, 1, ST_PERSISTENT_THREADS, b);
     } else {
-        for (int L = 0; L < ST_DEPTH; L++) {
-            Prof _p(ctx, "k_st_level");
-            ZKW_LAUNCH(ctx, k_st_level, g64, 64, b, L);
-        }
+        for (int L = 0; L < ST_DEPTH; L++) ZKW_LAUNCH(ctx, k_st_level, g64, 64, b, L);
     }
-    ZKW_TRY(launch_check("k_st_level"));
     return ctx->read_small(t->root, t->root_dev, 32);
 }
 
@@ -143,12 +136,10 @@ static int st_sort_merged(zkw_ctx* ctx, const StMerge& g, size_t N, const u32** 
     ZKW_TRY(ctx->scratch_t<u64>("st_k64b", N, &k64b));
     ZKW_TRY(ctx->scratch("st_sort_tmp", tmp_bytes + 256, &tmp));
     const unsigned grid = blocks_for(N, 256);
-    { Prof _p(ctx, "k_st_iota"); ZKW_LAUNCH(ctx, k_st_iota, grid, 256, perm0, (u64)N); }
-    ZKW_TRY(launch_check("k_st_iota"));
+    ZKW_LAUNCH(ctx, k_st_iota, grid, 256, perm0, (u64)N);
     u32 *pc = perm0, *pn = perm1;
     for (int w = 0; w < 4; w++) {
-        { Prof _p(ctx, "k_st_gather_word"); ZKW_LAUNCH(ctx, k_st_gather_word, grid, 256, g, (const u32*)pc, w, (u64)N, k64a); }
-        ZKW_TRY(launch_check("k_st_gather_word"));
+        ZKW_LAUNCH(ctx, k_st_gather_word, grid, 256, g, (const u32*)pc, w, (u64)N, k64a);
         { Prof _p(ctx, "radix_sort"); ZKW_TRY(radix_sort_pairs<u64>(ctx, tmp, tmp_bytes, k64a, k64b, pc, pn, N, 64)); }
         u32* x = pc; pc = pn; pn = x;
     }
@@ -174,16 +165,14 @@ static int st_insert_device(zkw_storage_tree* t, const u32* d_keys, const u32* d
     const u32* pc = nullptr;
     ZKW_TRY(st_sort_merged(ctx, g, N, &pc));
     // which batch entries bring a new leaf, and their ranks in array order
-    { Prof _p(ctx, "k_st_mark"); ZKW_LAUNCH(ctx, k_st_mark, grid, 256, g, pc, (u64)N, new_first); }
-    ZKW_TRY(launch_check("k_st_mark"));
+    ZKW_LAUNCH(ctx, k_st_mark, grid, 256, g, pc, (u64)N, new_first);
     ZKW_TRY(flag_prefix(ctx, "k_st_new_rank", StArrayFlag{new_first}, m, new_rank));
     u32 n_new = 0;
     ZKW_TRY(ctx->read_small(&n_new, new_rank + m, sizeof n_new));
     if (t->n + n_new > t->cap)  // nothing of the tree has been written yet
         return fail(ZKW_ERR_OOM, "zkw_storage_tree: %zu leaves + %u new ones exceed the capacity of %zu", t->n, n_new, t->cap);
     ZKW_TRY(flag_prefix(ctx, "k_st_heads", StHeadFlag{g, pc}, N, heads));
-    { Prof _p(ctx, "k_st_emit"); ZKW_LAUNCH(ctx, k_st_emit, grid, 256, g, pc, (u64)N, (const u32*)heads, (const u32*)new_rank, t->keys[oth], t->index[oth], t->values[oth]); }
-    ZKW_TRY(launch_check("k_st_emit"));
+    ZKW_LAUNCH(ctx, k_st_emit, grid, 256, g, pc, (u64)N, (const u32*)heads, (const u32*)new_rank, t->keys[oth], t->index[oth], t->values[oth]);
     t->cur = oth;
     t->n += n_new;
     t->next_index += n_new;
@@ -204,11 +193,11 @@ extern "C" int zkw_storage_tree_insert(zkw_storage_tree* t, const uint8_t* keys,
 // `missing`: the flag word of k_sw_lookup, or NULL; a full tree answers every key and leaves it alone
 static int st_query(zkw_ctx* ctx, const zkw_storage_tree* t, const StQuery& q, size_t n, u32* missing = nullptr) {
     if (t->witness) {
-        { Prof _p(ctx, "k_sw_lookup"); ZKW_LAUNCH(ctx, k_sw_lookup, n, ST_DEPTH, t->table(), q, missing); }
-        return launch_check("k_sw_lookup");
+        ZKW_LAUNCH(ctx, k_sw_lookup, n, ST_DEPTH, t->table(), q, missing);
+        return ZKW_OK;
     }
-    { Prof _p(ctx, "k_st_query"); ZKW_LAUNCH(ctx, k_st_query, n, ST_DEPTH, t->view(), q); }
-    return launch_check("k_st_query");
+    ZKW_LAUNCH(ctx, k_st_query, n, ST_DEPTH, t->view(), q);
+    return ZKW_OK;
 }
 
 extern "C" int zkw_storage_tree_get_leaves(const zkw_storage_tree* t, const uint8_t* keys, size_t n, uint64_t* leaf_indexes, uint8_t* values,
@@ -277,8 +266,7 @@ int zkw_storage_tree_apply_queries_device(zkw_storage_tree* t, const zkw_log_que
     ZKW_TRY(ctx->scratch_t<u32>("st_ap_keys", n * 8, &wk));
     ZKW_TRY(ctx->scratch_t<u32>("st_ap_values", n * 8, &wv));
     ZKW_TRY(flag_prefix(ctx, "k_st_write_rank", StWriteFlag{d_queries}, n, rank));
-    { Prof _p(ctx, "k_st_writes"); ZKW_LAUNCH(ctx, k_st_writes, blocks_for(n, 64), 64, d_queries, (u64)n, (const u32*)rank, wk, wv); }
-    ZKW_TRY(launch_check("k_st_writes"));
+    ZKW_LAUNCH(ctx, k_st_writes, blocks_for(n, 64), 64, d_queries, (u64)n, (const u32*)rank, wk, wv);
     u32 m = 0;
     ZKW_TRY(ctx->read_small(&m, rank + n, sizeof m));
     return st_insert_device(t, wk, wv, m);
@@ -358,11 +346,11 @@ extern "C" int zkw_storage_tree_create_witness(zkw_ctx* ctx, const uint8_t* keys
         if (n == 0) return ZKW_OK;
         SwEntries e{reinterpret_cast<const u32*>(d_k), d_i, reinterpret_cast<const u32*>(d_v), reinterpret_cast<const u32*>(d_p), (u64)n, next_enumeration_index, {}};
         memcpy(e.root, root, 32);
-        { Prof _p(ctx, "k_sw_verify"); ZKW_LAUNCH(ctx, k_sw_verify, blocks_for(n, 64), 64, e, status, meta); }
+        ZKW_LAUNCH(ctx, k_sw_verify, blocks_for(n, 64), 64, e, status, meta);
         const u32* perm = nullptr;
         ZKW_TRY(st_sort_merged(ctx, st_keys_only(e.keys, n), n, &perm));
-        { Prof _p(ctx, "k_sw_gather"); ZKW_LAUNCH(ctx, k_sw_gather, n, ST_DEPTH, e, perm, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}, status, meta); }
-        { Prof _p(ctx, "k_sw_count"); ZKW_LAUNCH(ctx, k_sw_count, blocks_for(n, 256), 256, (const u64*)t->index[0], (u64)n, meta + 1); }
+        ZKW_LAUNCH(ctx, k_sw_gather, n, ST_DEPTH, e, perm, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}, status, meta);
+        ZKW_LAUNCH(ctx, k_sw_count, blocks_for(n, 256), 256, (const u64*)t->index[0], (u64)n, meta + 1);
         return ctx->read_small(h_meta, meta, sizeof h_meta);
     }();
     if (rc != ZKW_OK) return sw_drop(t, rc);
@@ -408,10 +396,10 @@ extern "C" int zkw_storage_tree_extract_witness(const zkw_storage_tree* tree, zk
         u32* d_count = nullptr;
         ZKW_TRY(ctx->scratch_t<u32>("sw_meta", 2, &d_count));
         HIP_TRY(ctx->memset_async(d_count, 0, sizeof(u32)));
-        { Prof _p(ctx, "k_sw_unique_keys"); ZKW_LAUNCH(ctx, k_sw_unique_keys, blocks_for(n, 256), 256, d_keys, perm, (const u32*)heads, (u64)n, t->keys[0]); }
+        ZKW_LAUNCH(ctx, k_sw_unique_keys, blocks_for(n, 256), 256, d_keys, perm, (const u32*)heads, (u64)n, t->keys[0]);
         // the full tree's answers straight into the table
         ZKW_TRY(st_query(ctx, tree, StQuery{nullptr, t->keys[0], t->index[0], t->values[0], t->paths}, unique));
-        { Prof _p(ctx, "k_sw_count"); ZKW_LAUNCH(ctx, k_sw_count, blocks_for(unique, 256), 256, (const u64*)t->index[0], (u64)unique, d_count); }
+        ZKW_LAUNCH(ctx, k_sw_count, blocks_for(unique, 256), 256, (const u64*)t->index[0], (u64)unique, d_count);
         return ctx->read_small(&count, d_count, sizeof count);
     }();
     if (rc != ZKW_OK) return sw_drop(t, rc);
@@ -449,21 +437,17 @@ static int sw_advance(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx
         HIP_TRY(ctx->memset_async(meta, 0, (SWA_META_WORDS + entries) * sizeof(u32)));
         const SwView tv = src->table();
         const SwaFold f{tv, wlist, up, d, nxt, meta, (u64)bound};
-        { Prof _p(ctx, "k_swa_locate"); ZKW_LAUNCH(ctx, k_swa_locate, blocks_for(n, 64), 64, tv, wr, ent, first, last, meta); }
+        ZKW_LAUNCH(ctx, k_swa_locate, blocks_for(n, 64), 64, tv, wr, ent, first, last, meta);
         ZKW_TRY(flag_prefix(ctx, "k_swa_new_rank", SwaNewFlag{ent, first, tv.index}, n, new_rank));
         ZKW_TRY(flag_prefix(ctx, "k_swa_wrank", SwaWrittenFlag{first}, entries, wrank));
-        { Prof _p(ctx, "k_swa_compact"); ZKW_LAUNCH(ctx, k_swa_compact, blocks_for(entries, 256), 256, (const u32*)first, (const u32*)wrank, (const u32*)new_rank, (u64)entries, (u64)n, wlist, meta); }
-        { Prof _p(ctx, "k_swa_leaves"); ZKW_LAUNCH(ctx, k_swa_leaves, blocks_for(bound, 64), 64, f, wr, (const u32*)first, (const u32*)last, (const u32*)new_rank, src->next_index, widx, wval); }
+        ZKW_LAUNCH(ctx, k_swa_compact, blocks_for(entries, 256), 256, (const u32*)first, (const u32*)wrank, (const u32*)new_rank, (u64)entries, (u64)n, wlist, meta);
+        ZKW_LAUNCH(ctx, k_swa_leaves, blocks_for(bound, 64), 64, f, wr, (const u32*)first, (const u32*)last, (const u32*)new_rank, src->next_index, widx, wval);
         if (bound <= ST_PERSISTENT_MAX) {
-            Prof _p(ctx, "k_swa_fold");
-            ZKW_LAUNCH(ctx, k_swa_fold, bound ? 1 : 0, ST_PERSISTENT_THREADS, f);
+            ZKW_LAUNCH(ctx, k_swa_fold, bound ? 1 : 0, ST_PERSISTENT_THREADS, f);  // (no writes: nothing is launched, the span is still recorded)
         } else {
-            for (int L = 0; L < ST_DEPTH; L++) {
-                Prof _p(ctx, "k_swa_level");
-                ZKW_LAUNCH(ctx, k_swa_level, blocks_for(bound, 64), 64, f, L);
-            }
+            for (int L = 0; L < ST_DEPTH; L++) ZKW_LAUNCH(ctx, k_swa_level, blocks_for(bound, 64), 64, f, L);
         }
-        { Prof _p(ctx, "k_swa_paths"); ZKW_LAUNCH(ctx, k_swa_paths, entries, ST_DEPTH, f, (const u32*)first, (const u32*)wrank, (const u64*)widx, (const u32*)wval, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}); }
+        ZKW_LAUNCH(ctx, k_swa_paths, entries, ST_DEPTH, f, (const u32*)first, (const u32*)wrank, (const u64*)widx, (const u32*)wval, SwTable{t->keys[0], t->index[0], t->values[0], t->paths});
         return ctx->read_small(h_meta, meta, sizeof h_meta);
     }();
     if (rc != ZKW_OK) return sw_drop(t, rc);
@@ -546,11 +530,11 @@ static int sw_chain(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx, 
         }
         HIP_TRY(ctx->memset_async(hdr, 0, hdr_words * sizeof(u32)));
         HIP_TRY(ctx->memset_async(fin, 0, fin_words * sizeof(u32)));
-        { Prof _p(ctx, "k_swc_locate"); ZKW_LAUNCH(ctx, k_swc_locate, blocks_for(N, 64), 64, tv, SwcQueries{wr, d_offs, (u32)K}, ent, touched, first, last, cfirst, hdr); }
+        ZKW_LAUNCH(ctx, k_swc_locate, blocks_for(N, 64), 64, tv, SwcQueries{wr, d_offs, (u32)K}, ent, touched, first, last, cfirst, hdr);
         ZKW_TRY(flag_prefix(ctx, "k_swc_trank", SwcTouchedFlag{touched}, KE, trank));
         ZKW_TRY(flag_prefix(ctx, "k_swc_wrank", SwaWrittenFlag{first}, KE, wrank));
         ZKW_TRY(flag_prefix(ctx, "k_swc_new_rank", SwcNewFlag{ent, cfirst, tv.index}, N, new_rank));
-        { Prof _p(ctx, "k_swc_compact"); ZKW_LAUNCH(ctx, k_swc_compact, blocks_for(std::max(KE, K + 1), 256), 256, c, tbase, wbase); }
+        ZKW_LAUNCH(ctx, k_swc_compact, blocks_for(std::max(KE, K + 1), 256), 256, c, tbase, wbase);
         ZKW_TRY(ctx->read_small(h_hdr.data(), hdr, hdr_words * sizeof(u32)));
     }
     if (h_hdr[SWC_HDR_MISSING]) {
@@ -587,13 +571,10 @@ static int sw_chain(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx, 
             Prof _p(ctx, "swc_copy_paths");
             HIP_TRY(ctx->copy_async(work->paths, tv.paths, E * (size_t)ST_DEPTH * 32, hipMemcpyDeviceToDevice));
         }
-        { Prof _p(ctx, "k_swc_walk"); ZKW_LAUNCH(ctx, k_swc_walk, blocks_for(E, 64), 64, c, wr, tv.index, tv.values, (const u32*)last, (const u32*)cfirst, (const u32*)new_rank, src->next_index); }
+        ZKW_LAUNCH(ctx, k_swc_walk, blocks_for(E, 64), 64, c, wr, tv.index, tv.values, (const u32*)last, (const u32*)cfirst, (const u32*)new_rank, src->next_index);
         const unsigned fold_wgs = blocks_for(h_wbase[K], 256), all_wgs = fold_wgs + blocks_for(KE, 256);
         if (h_tbase[K])  // (a chain without a query captures and folds nothing)
-            for (int s = 0; s < ST_DEPTH + (int)K - 1; s++) {
-                Prof _p(ctx, "k_swc_step");
-                ZKW_LAUNCH(ctx, k_swc_step, all_wgs, 256, c, fold_wgs, s);
-            }
+            for (int s = 0; s < ST_DEPTH + (int)K - 1; s++) ZKW_LAUNCH(ctx, k_swc_step, all_wgs, 256, c, fold_wgs, s);
         return ctx->read_small(h_fin.data(), fin, fin_words * sizeof(u32));
     }();
     if (rc != ZKW_OK) return drop_all(rc);
