@@ -12,6 +12,8 @@
 //   k_kzg_twiddles        a lane per j < 2048: w^j by square-and-multiply (per call, into context scratch)
 //   k_kzg_blob_ntt        a workgroup per blob: the 4 096 coefficients in 128 KiB of dynamic LDS, twelve decimation-in-frequency stages
 //                         on natural-order input, so that position i of the result is p(w^brp12(i)): the blob's evaluation form as is
+//   k_kzg_blob_intt       a workgroup per blob, the way back: the evaluation form (range-checked while it is loaded) to the 4 096
+//                         coefficients, the same twelve stages undone last first with the same table, then 1 / 4096
 //   k_kzg_blob_challenge  a wave per blob: SHA-256 over "FSBLOBVERIFY_V1_" || 4096 || evaluation form || commitment (2 050 blocks),
 //                         reduced below r
 //   k_kzg_proofs_out      the 2 n compressed proofs into the n records
@@ -194,6 +196,75 @@ static __device__ __forceinline__ void k_kzg_blob_ntt(const VB& vb, const uint8_
             kzg_put_be32(out + 32 * (size_t)i, v);
         }
     }
+}
+
+// 32 big-endian bytes as plain words: eight word loads when the address allows, byte loads otherwise
+static __device__ __forceinline__ bls::Fr kzg_get_be32(const uint8_t* b, bool aligned) {
+    bls::Fr e;
+    if (aligned) {
+        const u32* p = reinterpret_cast<const u32*>(b);
+#pragma unroll
+        for (int m = 0; m < 8; m++) e.w[7 - m] = __builtin_bswap32(p[m]);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const uint8_t* p = b + 4 * (7 - m);
+            e.w[m] = ((u32)p[0] << 24) | ((u32)p[1] << 16) | ((u32)p[2] << 8) | (u32)p[3];
+        }
+    }
+    return e;
+}
+
+// The way back: grid n_blobs, 512 lanes, KZG_NTT_LDS bytes of dynamic LDS. evals: [n_blobs][4096][32] big-endian, element i = p(w^brp12(i)),
+// any address. coeffs: [n_blobs][4096][32] little-endian, row k = the coefficient of X^k (KzgSrc{.., 4096, 0}: what k_kzg_quotient and
+// k_kzg_accumulate read), 16-byte aligned. The twelve stages of k_kzg_blob_ntt undone last first, on bit-reversed-order input with
+// natural-order output: a forward stage of half-width h sent (u, v) to (a, b) = (u + v, (u - v) w^e), e = j 2048 / h, so
+// (2 u, 2 v) = (a + b w^-e, a - b w^-e), and w^-e = -w^(2048 - e) (w^2048 = -1): the table of k_kzg_twiddles with add and sub exchanged,
+// for e = 0 entry 0 with them as they are. The twelve factors of two leave with one product by 1 / 4096 per element on the way out.
+// status[blob]: 0, or 1 + e for the LOWEST element index e that is not below r (k_kzg_blob_eval's form); such a blob is not transformed.
+// points (may be null): [n_blobs][32] big-endian; status[n_blobs + blob] = 1 when the blob's point is not below r, else 0
+static __device__ __forceinline__ void k_kzg_blob_intt(const VB& vb, const uint8_t* __restrict__ evals, const bls::Fr* __restrict__ tw, uint8_t* __restrict__ coeffs,
+                                                       const uint8_t* __restrict__ points, u32 n_blobs, u32* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) uint4 kzg_ntt_lds[];
+    __shared__ u32 s_bad;
+    uint4* x = kzg_ntt_lds;
+    const u32 t = threadIdx.x;
+    if (t == 0) s_bad = ~0u;
+    __syncthreads();
+    const uint8_t* ev = evals + (size_t)vb.x * KZG_EVAL_BYTES;
+    const bool aligned = (reinterpret_cast<uintptr_t>(evals) & 3) == 0;  // (a caller's device pointer may be odd)
+#pragma unroll 1
+    for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {
+        const bls::Fr f = kzg_get_be32(ev + 32 * (size_t)i, aligned);
+        if (!bls::below_modulus<bls::FrT>(f.w)) atomicMin(&s_bad, i);
+        kzg_lds_put(x, i, f);
+    }
+    if (points && t == 0) status[n_blobs + vb.x] = bls::below_modulus<bls::FrT>(kzg_get_be32(points + 32 * (size_t)vb.x, false).w) ? 0u : 1u;
+    __syncthreads();
+    const u32 bad = s_bad;  // (the same for every lane: all leave, or none)
+    if (t == 0) status[vb.x] = bad + 1u;
+    if (bad != ~0u) return;
+#pragma unroll 1
+    for (u32 s = 12; s-- > 0;) {
+        const u32 half = 2048u >> s;
+#pragma unroll 1
+        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
+            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
+            const bls::Fr u = kzg_lds_get(x, i0);
+            bls::Fr m = kzg_lds_get(x, i1);
+            if (s < 11) m = bls::mul<bls::FrT>(m, tw[(2048u - (j << s)) & 2047u]);  // (the first stage undone has no twiddle but 1)
+            const bls::Fr with = bls::add(u, m), without = bls::sub(u, m);
+            kzg_lds_put(x, i0, bls::select(j == 0, with, without));
+            kzg_lds_put(x, i1, bls::select(j == 0, without, with));
+        }
+        __syncthreads();
+    }
+    // 1 / 4096 in Montgomery form is 2^256 / 2^12 = 2^244, which is below r (a number of 255 bits) as it stands
+    bls::Fr inv_width = bls::zero<bls::FrT>();
+    inv_width.w[7] = 1u << 20;
+    uint4* out = reinterpret_cast<uint4*>(coeffs + (size_t)vb.x * KZG_EVAL_BYTES);
+#pragma unroll 1
+    for (u32 k = t; k < 4096; k += KZG_NTT_THREADS) kzg_lds_put(out, k, bls::mul<bls::FrT>(kzg_lds_get(x, k), inv_width));
 }
 
 // word `wi` (big-endian, as SHA-256 reads it) of the padded preimage of compute_challenge: 8 words of domain and degree, 32 768 of the

@@ -2,7 +2,9 @@
 // HBM), zkw_kzg_commit and zkw_eip4844_witness (generate_eip4844_witness, src/utils.rs:119-231 of the reference), and the KZG proofs
 // zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs), and their check, zkw_kzg_verifier with
 // zkw_kzg_verify and zkw_eip4844_verify (verify_kzg_proof), zkw_kzg_evaluate_blobs (eval_poly) and zkw_eip4844_verify_blobs
-// (verify_proof_poly). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh,
+// (verify_proof_poly), and the producers from a blob in evaluation form, zkw_kzg_blob_coefficients, zkw_kzg_commit_blobs,
+// zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them).
+// Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh,
 // kzg_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
@@ -258,6 +260,130 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
     ZKW_LAUNCH(ctx, k_kzg_proofs_out, blocks_for(n_blobs * 96, 256), 256, (const uint8_t*)d_proofs, (u32)nb, prf);
     ZKW_TRY(ctx->finish_out(out, d_out, n_blobs));
     if (blob_evaluations) ZKW_TRY(ctx->finish_out(blob_evaluations, d_ev, n_blobs * KZG_EVAL_BYTES));
+    return ctx->sync_if_host();
+}
+
+// ---- the producers from a blob in evaluation form: back to the coefficients in Fr, then the kernels above as they are ------------------
+static int kzg_blobs_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
+    if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "%s: a blob has 4096 elements, the settings hold %zu points", who, s->n);
+    if (n > 32767) return fail(ZKW_ERR_INVALID, "%s: at most 32767 blobs per call, not %zu", who, n);
+    return kzg_check_call(who, s, ctx, n);
+}
+
+// the twiddles and k_kzg_blob_intt over n >= 1 blobs on the context's stream, then the call's ONE readback: the n status words and, with
+// d_points, the n flags of the points. The coefficients ([n][4096][32], zkw_kzg_commit's form) are left in context scratch, so that a
+// refused call has written nothing of the caller's
+static int kzg_blob_coefficients_device(const char* who, zkw_ctx* ctx, const uint8_t* d_ev, const uint8_t* d_points, size_t n, const uint8_t** d_coeffs) {
+    static bool attr_set[16] = {};
+    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
+        ZKW_TRY((Launcher<&k_kzg_blob_intt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+        attr_set[ctx->device & 15] = true;
+    }
+    bls::Fr* d_tw = nullptr;
+    uint8_t* d_c = nullptr;
+    u32* d_st = nullptr;
+    const size_t words = d_points ? 2 * n : n;
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_blob_coeffs", n * KZG_EVAL_BYTES, &d_c));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_intt_status", words, &d_st));
+    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
+    ZKW_LAUNCH_D(ctx, k_kzg_blob_intt, "k_kzg_blob_intt", dim3((unsigned)n), KZG_NTT_THREADS, KZG_NTT_LDS, d_ev, (const bls::Fr*)d_tw, d_c, d_points, (u32)n, d_st);
+    std::vector<u32> st(words);
+    ZKW_TRY(ctx->read_small(st.data(), d_st, words * sizeof(u32)));
+    for (size_t j = 0; j < n; j++)
+        if (st[j]) return fail(ZKW_ERR_INVALID, "%s: element %u of blob %zu is not below r", who, (unsigned)(st[j] - 1), j);
+    for (size_t j = n; j < words; j++)
+        if (st[j]) return fail(ZKW_ERR_INVALID, "%s: the point of blob %zu is not below r", who, j - n);
+    *d_coeffs = d_c;
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_blob_coefficients(zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* coeffs) {
+    if (!ctx || (n && (!blob_evaluations || !coeffs))) return fail(ZKW_ERR_INVALID, "zkw_kzg_blob_coefficients: null argument");
+    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_kzg_blob_coefficients: at most 32767 blobs per call, not %zu", n);
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_blob_coefficients", ctx, d_ev, nullptr, n, &d_c));
+    HIP_TRY(ctx->copy_async(coeffs, d_c, n * KZG_EVAL_BYTES, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_kzg_commit_blobs(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* commitments) {
+    if (!s || !ctx || (n && (!blob_evaluations || !commitments))) return fail(ZKW_ERR_INVALID, "zkw_kzg_commit_blobs: null argument");
+    ZKW_TRY(kzg_blobs_check_call("zkw_kzg_commit_blobs", s, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_commit_blobs", ctx, d_ev, nullptr, n, &d_c));
+    uint8_t* d_out = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", commitments, n * 48, &d_out));
+    ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_c, (u32)KZG_BLOB_ELEMENTS, 0}, (u32)KZG_EVAL_BYTES, n, d_out, 48));
+    ZKW_TRY(ctx->finish_out(commitments, d_out, n * 48));
+    return ctx->sync_if_host();
+}
+
+// the quotients of n polynomials of 4 096 coefficients (scratch rows) at points of 32 big-endian bytes, the values in the same form, and
+// the commitments of the quotients at d_proofs
+static int kzg_open_coefficients_device(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* d_c, const uint8_t* d_z, u32 z_stride, size_t n, uint8_t* d_proofs,
+                                        uint8_t* d_values, u32 value_stride) {
+    constexpr u32 ROWS = (KZG_BLOB_ELEMENTS - 1) * 32;
+    uint8_t* d_rows = nullptr;
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_quotient_rows", n * ROWS, &d_rows));
+    ZKW_LAUNCH(ctx, k_kzg_quotient, n, KZG_QUO_THREADS, KzgSrc{d_c, (u32)KZG_BLOB_ELEMENTS, 0}, (u32)KZG_EVAL_BYTES, d_z, z_stride, (u32)KZG_Z_BE32, d_rows, ROWS, d_values, value_stride, 1u);
+    return kzg_commit_device(s, ctx, KzgSrc{d_rows, (u32)KZG_BLOB_ELEMENTS - 1, 0}, ROWS, n, d_proofs, 48);
+}
+
+extern "C" int zkw_kzg_open_blobs(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* points, size_t n, uint8_t* proofs,
+                                  uint8_t* values) {
+    if (!s || !ctx || (n && (!blob_evaluations || !points || !proofs || !values))) return fail(ZKW_ERR_INVALID, "zkw_kzg_open_blobs: null argument");
+    ZKW_TRY(kzg_blobs_check_call("zkw_kzg_open_blobs", s, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_z = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(ctx->in("kzg_in_points", points, n * 32, &d_z));
+    ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_open_blobs", ctx, d_ev, d_z, n, &d_c));
+    uint8_t *d_proofs = nullptr, *d_values = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", proofs, n * 48, &d_proofs));
+    ZKW_TRY(ctx->out("kzg_out_values", values, n * 32, &d_values));
+    ZKW_TRY(kzg_open_coefficients_device(s, ctx, d_c, d_z, 32u, n, d_proofs, d_values, 32u));
+    ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * 48));
+    ZKW_TRY(ctx->finish_out(values, d_values, n * 32));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_eip4844_prove_blobs(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* commitments, size_t n,
+                                       uint8_t* proofs, uint8_t* openings) {
+    if (!s || !ctx || (n && (!blob_evaluations || !commitments || !proofs))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove_blobs: null argument");
+    ZKW_TRY(kzg_blobs_check_call("zkw_eip4844_prove_blobs", s, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_cm = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(ctx->in("kzg_in_commitments", commitments, n * 48, &d_cm));
+    uint8_t* d_open = nullptr;  // a row: the blob's challenge, then its value there (scratch in both pointer modes: a refused call leaves `openings` untouched)
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_openings", n * 64, &d_open));
+    // the sponge depends on nothing the transform writes: beside it on a stream of the pool, joined ahead of the quotient. (A context of a
+    // batch has one stream; under zkw_profile every span times its own kernel.)
+    const bool beside = !ctx->batched() && !ctx->profiling;
+    if (beside) {
+        hipStream_t side = nullptr;
+        ZKW_TRY(ctx->side_fork(&side));
+        ZKW_TRY((kzg_launch_on<&k_kzg_blob_challenge, 64>(side, "k_kzg_blob_challenge", (unsigned)n, 0, d_ev, d_cm, 48u, d_open, 64u)));
+    } else {
+        ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, d_cm, 48u, d_open, 64u);
+    }
+    const int rc = kzg_blob_coefficients_device("zkw_eip4844_prove_blobs", ctx, d_ev, nullptr, n, &d_c);
+    if (beside) ZKW_TRY(ctx->side_join());  // (after a refusal too: the sponge of this call is not left to run into the next one's scratch)
+    if (rc != ZKW_OK) return rc;
+    uint8_t* d_proofs = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", proofs, n * 48, &d_proofs));
+    ZKW_TRY(kzg_open_coefficients_device(s, ctx, d_c, d_open, 64u, n, d_proofs, d_open + 32, 64u));
+    ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * 48));
+    if (openings) HIP_TRY(ctx->copy_async(openings, d_open, n * 64, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return ctx->sync_if_host();
 }
 

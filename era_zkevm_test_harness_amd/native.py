@@ -194,6 +194,10 @@ SYMBOLS = [
     ("zkw_eip4844_verify", _int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zkw_kzg_evaluate_blobs", _int, [_vp, _vp, _vp, _sz, _vp]),
     ("zkw_eip4844_verify_blobs", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_kzg_blob_coefficients", _int, [_vp, _vp, _sz, _vp]),
+    ("zkw_kzg_commit_blobs", _int, [_vp, _vp, _vp, _sz, _vp]),
+    ("zkw_kzg_open_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_eip4844_prove_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -886,6 +890,54 @@ class KzgSettings:
                                         _np_ptr(ev) if evaluations and n else None))
         return (out, ev) if evaluations else out
 
+    @staticmethod
+    def _empty(ctx, like, shape):
+        """(array, pointer) of an output of `shape` bytes: a tensor on `like`'s device in device pointer mode, numpy otherwise"""
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty(shape, dtype=torch.uint8, device=like.device)
+            return out, C.c_void_p(out.data_ptr() if shape[0] else None)
+        out = np.zeros(shape, np.uint8)
+        return out, (_np_ptr(out) if shape[0] else None)
+
+    def commit_blobs(self, evaluations, ctx=None):
+        """zkw_kzg_commit_blobs (compute_commitment, kzg/src/lib.rs:188-191): `evaluations` = [n, 131072] bytes, blobs in evaluation
+        form (4 096 elements of 32 big-endian bytes below r, as a sidecar carries them); returns [n, 48] commitments. An element that is
+        not below r raises ZkwError(ERR_INVALID) naming blob and element."""
+        ctx = ctx or self.ctx
+        eptr, n, _ke = self._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+        out, optr = self._empty(ctx, _ke, (n, 48))
+        _check(load().zkw_kzg_commit_blobs(self.handle, ctx.handle, eptr, n, optr))
+        return out
+
+    def open_blobs(self, evaluations, points, ctx=None):
+        """zkw_kzg_open_blobs (compute_proof, kzg/src/lib.rs:218-256): `evaluations` as for `commit_blobs`, `points` = [n, 32] bytes, a
+        point as 32 big-endian bytes below r (`kzg_evaluate_blobs`' form); returns (proofs [n, 48], values [n, 32]), the values in the
+        points' form. A point on the evaluation domain is no special case: the value there is the blob's element."""
+        ctx = ctx or self.ctx
+        eptr, n, _ke = self._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+        zptr, nz, _kz = self._bytes(ctx, points, 32)
+        assert n == nz
+        proofs, pptr = self._empty(ctx, _ke, (n, 48))
+        values, vptr = self._empty(ctx, _ke, (n, 32))
+        _check(load().zkw_kzg_open_blobs(self.handle, ctx.handle, eptr, zptr, n, pptr, vptr))
+        return proofs, values
+
+    def eip4844_prove_blobs(self, evaluations, commitments, ctx=None, openings=False):
+        """zkw_eip4844_prove_blobs (compute_proof_poly, kzg/src/lib.rs:285-288): `evaluations` as for `commit_blobs`, `commitments` =
+        [n, 48] bytes, hashed into the challenge as they are (not checked: `KzgVerifier.eip4844_verify_blobs` judges them); returns
+        [n, 48] blob proofs; with `openings=True` returns (proofs, [n, 64] bytes): per blob the challenge and the value, 32 big-endian
+        bytes each."""
+        ctx = ctx or self.ctx
+        eptr, n, _ke = self._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+        cptr, nc, _kc = self._bytes(ctx, commitments, 48)
+        assert n == nc
+        proofs, pptr = self._empty(ctx, _ke, (n, 48))
+        op, optr = self._empty(ctx, _ke, (n, 64)) if openings else (None, None)
+        _check(load().zkw_eip4844_prove_blobs(self.handle, ctx.handle, eptr, cptr, n, pptr, optr))
+        return (proofs, op) if openings else proofs
+
     def free(self):
         if self.handle:
             load().zkw_kzg_settings_free(self.handle)
@@ -914,6 +966,17 @@ def kzg_evaluate_blobs(ctx, evaluations, points):
         return out
     out = np.zeros((n, 32), np.uint8)
     _check(load().zkw_kzg_evaluate_blobs(ctx.handle, eptr, zptr, n, _np_ptr(out) if n else None))
+    return out
+
+
+def kzg_blob_coefficients(ctx, evaluations):
+    """zkw_kzg_blob_coefficients: `evaluations` = [n, 131072] bytes, blobs in evaluation form (the inverse of what
+    `KzgSettings.eip4844_prove(evaluations=True)` returns); returns [n, 4096, 32] bytes: row k = the coefficient of X^k as 32
+    little-endian bytes, `KzgSettings.commit`'s form. An element that is not below r raises ZkwError(ERR_INVALID) naming blob and
+    element. Arrays as for `KzgSettings`."""
+    eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+    out, optr = KzgSettings._empty(ctx, _ke, (n, 4096, 32))
+    _check(load().zkw_kzg_blob_coefficients(ctx.handle, eptr, n, optr))
     return out
 
 

@@ -811,6 +811,36 @@ int zkw_kzg_evaluate_blobs(zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][1
 int zkw_eip4844_verify_blobs(const zkw_kzg_verifier *v, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
                              const uint8_t *commitments /*[n][48]*/, const uint8_t *proofs /*[n][48]*/, size_t n,
                              uint8_t *verdicts /*[n]*/, uint8_t *openings /*[n][64] or NULL*/);
+/* The producers from a blob in EVALUATION form (a sidecar's blob: 4096 x 32 big-endian bytes, element i = p(w^brp12(i)), any
+   value below r, whether or not it came from pubdata) — what the reference's KZG helper takes everywhere.  The setup stays the
+   monomial one: each blob goes back to its coefficients by one inverse transform of 4 096 scalars in Fr on the device, and the
+   commitment and quotient kernels of zkw_kzg_commit and zkw_kzg_open run on those.  Common to the four calls: ZKW_ERR_INVALID,
+   naming the blob and the LOWEST offending element (or the point) in zkw_last_error, when something is not below r; the outputs
+   are then untouched (in device pointer mode nothing that writes them is enqueued ahead of the check).  One readback per call
+   (the n status words, with them the points' flags).  n = 0 is a no-op; at most 32 767 blobs per call.  The three calls that
+   take settings require num_points == 4096 and a context on the settings' device.
+
+   zkw_kzg_blob_coefficients: the inverse of what zkw_eip4844_prove writes into blob_evaluations; coeffs is zkw_kzg_commit's
+   form.
+   zkw_kzg_commit_blobs: compute_commitment (kzg/src/lib.rs:188-191).
+   zkw_kzg_open_blobs: compute_proof (lib.rs:218-256).  Points and values are 32 big-endian bytes (zkw_kzg_evaluate_blobs'
+   form).  A point on the evaluation domain is no special case (the quotient is Horner's walk; compute_quotient_eval, lib.rs:303-324,
+   has no counterpart): the value there is the blob's element.
+   zkw_eip4844_prove_blobs: compute_proof_poly (lib.rs:285-288), the argument order of zkw_eip4844_verify_blobs.  The challenge
+   is compute_challenge over the caller's evaluation form and the caller's 48 commitment bytes AS THEY ARE: the commitment is
+   neither decompressed nor checked, and a proof made for a wrong one is a proof zkw_eip4844_verify_blobs rejects — that call
+   judges it.  openings (may be NULL): per blob the challenge, then p(challenge), 32 big-endian bytes each.  (There is no call that
+   returns commitment and blob proof together: the challenge depends on the commitment, so nothing would be shared but the
+   transform.) */
+int zkw_kzg_blob_coefficients(zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/, size_t n,
+                              uint8_t *coeffs /*[n][4096][32] little-endian, row k = coefficient of X^k*/);
+int zkw_kzg_commit_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/, size_t n,
+                         uint8_t *commitments /*[n][48]*/);
+int zkw_kzg_open_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
+                       const uint8_t *points /*[n][32]*/, size_t n, uint8_t *proofs /*[n][48]*/, uint8_t *values /*[n][32]*/);
+int zkw_eip4844_prove_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
+                            const uint8_t *commitments /*[n][48]*/, size_t n, uint8_t *proofs /*[n][48]*/,
+                            uint8_t *openings /*[n][64] or NULL: challenge, then p(challenge), big-endian*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
