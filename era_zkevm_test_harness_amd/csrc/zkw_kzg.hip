@@ -3,14 +3,16 @@
 // zkw_kzg_open and zkw_eip4844_prove (compute_proof, compute_proof_poly, kzg/src/lib.rs), and their check, zkw_kzg_verifier with
 // zkw_kzg_verify and zkw_eip4844_verify (verify_kzg_proof), zkw_kzg_evaluate_blobs (eval_poly) and zkw_eip4844_verify_blobs
 // (verify_proof_poly), and the producers from a blob in evaluation form, zkw_kzg_blob_coefficients, zkw_kzg_commit_blobs,
-// zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them).
-// Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh,
-// kzg_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
+// zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them), and
+// the EIP-7594 cells and cell proofs, zkw_kzg_cell_settings with zkw_kzg_g1_fft, zkw_kzg_cells_blobs, zkw_kzg_cell_proofs_blobs and
+// zkw_eip4844_cell_proofs (the reference has no counterpart). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh,
+// kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
 #include "kzg_open_kernels.cuh"
 #include "kzg_eval_kernels.cuh"
 #include "kzg_verify_kernels.cuh"
+#include "kzg_cell_kernels.cuh"
 
 #include <cstddef>
 
@@ -565,4 +567,203 @@ extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx,
     ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, n));
     if (openings) ZKW_TRY(ctx->finish_out(openings, d_open, n * 64));
     return ctx->sync_if_host();
+}
+
+// ---- EIP-7594: the 128 cells of a blob and their proofs (kzg_cell_kernels.cuh) ----------------------------------------------------------
+static_assert(KZG_CELL_POINTS == 64 * KZG_CELLS && KZG_CELLS_BYTES == 2 * KZG_EVAL_BYTES, "64 offsets of 128 points; the extended blob is two blobs long");
+
+struct zkw_kzg_cell_settings {
+    zkw_ctx* ctx = nullptr;
+    size_t bytes = 0;
+    bls::G1Aff* table = nullptr;  // [32][8192]: table[w * 8192 + j * 64 + i] = 2^(8 w) X_i[j], X_i = G1_FFT_128(x_i)
+};
+
+// n_ffts transforms of 2^log_n Jacobian points each on the context's stream (d_in == d_out is fine)
+static int kzg_g1_fft_device(zkw_ctx* ctx, const bls::G1Jac* d_in, bls::G1Jac* d_out, u32 log_n, size_t n_ffts, bool inverse, bool scale, bool upper_inf) {
+    u32* d_tab = nullptr;  // the lanes' window tables
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_g1_fft_tables", n_ffts * KZG_G1_TAB_WORDS, &d_tab));
+    ZKW_LAUNCH(ctx, k_kzg_g1_fft, n_ffts, KZG_G1_FFT_THREADS, d_in, d_out, d_tab, log_n, inverse ? 1u : 0u, scale ? 1u : 0u, upper_inf ? 1u : 0u);
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_cell_settings_create(const zkw_kzg_settings* s, zkw_ctx* ctx, zkw_kzg_cell_settings** out) {
+    if (!s || !ctx || !out) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: null argument");
+    if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: a blob has 4096 elements, the settings hold %zu points", s->n);
+    if (ctx->device != s->ctx->device)
+        return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: the settings live on device %d, the context on device %d", s->ctx->device, ctx->device);
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: the context belongs to a batch of blocks");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    bls::G1Jac* d_x = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_setup", KZG_CELL_POINTS, &d_x));
+    zkw_kzg_cell_settings* cs = new zkw_kzg_cell_settings();
+    cs->ctx = ctx;
+    cs->bytes = (size_t)KZG_WINDOWS * KZG_CELL_POINTS * sizeof(bls::G1Aff);
+    auto drop = [&](int rc) {
+        (void)ctx->sync_stream();  // nothing queued may still write the table
+        if (cs->table) dev_free(cs->table);
+        delete cs;
+        return rc;
+    };
+    const hipError_t e = dev_malloc(&cs->table, cs->bytes + 64);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return drop(fail(ZKW_ERR_OOM, "zkw_kzg_cell_settings_create: %zu bytes of device memory: %s", cs->bytes, hipGetErrorString(e)));
+    }
+    const int rc = [&]() -> int {
+        ZKW_LAUNCH(ctx, k_kzg_cell_setup_x, blocks_for(KZG_CELL_POINTS, 64), 64, (const bls::G1Aff*)s->table, d_x);
+        ZKW_TRY(kzg_g1_fft_device(ctx, d_x, d_x, 7, 64, false, false, false));
+        ZKW_LAUNCH(ctx, k_kzg_cell_setup_affine, blocks_for(KZG_CELL_POINTS, 64), 64, (const bls::G1Jac*)d_x, cs->table);
+        ZKW_LAUNCH_2D(ctx, k_kzg_table, blocks_for(KZG_CELL_POINTS, 64), KZG_WINDOWS - 1, 64, cs->table, (u32)KZG_CELL_POINTS);
+        HIP_TRY(ctx->sync_stream());  // other contexts read the table without any ordering with this stream
+        return ZKW_OK;
+    }();
+    if (rc != ZKW_OK) return drop(rc);
+    ctx_retain(ctx);
+    *out = cs;
+    return ZKW_OK;
+}
+
+extern "C" void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings* cs) {
+    if (!cs) return;
+    (void)hipSetDevice(cs->ctx->device);
+    (void)cs->ctx->sync_stream();
+    dev_free(cs->table);
+    zkw_ctx* owner = cs->ctx;
+    delete cs;
+    ctx_release(owner);
+}
+extern "C" size_t zkw_kzg_cell_settings_bytes(const zkw_kzg_cell_settings* cs) { return cs ? cs->bytes : 0; }
+
+extern "C" int zkw_kzg_g1_fft(zkw_ctx* ctx, const uint8_t* points, size_t n, size_t n_ffts, int inverse, uint8_t* out) {
+    if (!ctx || (n_ffts && (!points || !out))) return fail(ZKW_ERR_INVALID, "zkw_kzg_g1_fft: null argument");
+    if (n == 0 || n > KZG_G1_FFT_MAX || (n & (n - 1))) return fail(ZKW_ERR_INVALID, "zkw_kzg_g1_fft: a power of two from 1 to %u points, not %zu", (unsigned)KZG_G1_FFT_MAX, n);
+    if (n_ffts > 65535) return fail(ZKW_ERR_INVALID, "zkw_kzg_g1_fft: at most 65535 transforms per call, not %zu", n_ffts);
+    if (n_ffts == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = n * n_ffts;
+    u32 log_n = 0;
+    while ((size_t)1 << log_n < n) log_n++;
+    const uint8_t* d_in = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_points", points, total * 48, &d_in));
+    bls::G1Aff* d_aff = nullptr;
+    bls::G1Jac* d_jac = nullptr;
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_g1_fft_affine", total, &d_aff));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_points", total, &d_jac));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_status", total, &d_status));
+    ZKW_LAUNCH(ctx, k_kzg_decompress, blocks_for(total, 64), 64, d_in, (u32)total, d_aff, d_status);
+    std::vector<u32> status(total);
+    ZKW_TRY(ctx->read_small(status.data(), d_status, total * sizeof(u32)));
+    for (size_t k = 0; k < total; k++)
+        if (status[k] != bls::G1_OK) return fail(ZKW_ERR_INVALID, "zkw_kzg_g1_fft: point %zu of transform %zu is refused: %s", k % n, k / n, kzg_reason(status[k]));
+    uint8_t* d_out = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", out, total * 48, &d_out));
+    ZKW_LAUNCH(ctx, k_kzg_g1_lift, blocks_for(total, 64), 64, (const bls::G1Aff*)d_aff, (u32)total, d_jac);
+    ZKW_TRY(kzg_g1_fft_device(ctx, d_jac, d_jac, log_n, n_ffts, inverse != 0, inverse != 0, false));
+    ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(total, 64), 64, (const bls::G1Jac*)d_jac, (u32)total, 0u, d_out);
+    ZKW_TRY(ctx->finish_out(out, d_out, total * 48));
+    return ctx->sync_if_host();
+}
+
+// w^j (j < 2048) and W^k (k < 4096) into context scratch on the context's stream
+static int kzg_cell_twiddles_device(zkw_ctx* ctx, const bls::Fr** d_tw, const bls::Fr** d_wpow) {
+    bls::Fr *tw = nullptr, *wpow = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &tw));
+    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, tw);
+    *d_tw = tw;
+    if (d_wpow) {
+        ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_cell_wpow", 4096, &wpow));
+        ZKW_LAUNCH(ctx, k_kzg_cell_wpow, 16, 256, wpow);
+        *d_wpow = wpow;
+    }
+    return ZKW_OK;
+}
+
+// the cells of n >= 1 polynomials read through src; d_evals: their evaluation forms, when the caller has them (cells 0..63 are a copy)
+static int kzg_cells_device(zkw_ctx* ctx, KzgSrc src, u32 poly_stride, const uint8_t* d_evals, const bls::Fr* d_tw, const bls::Fr* d_wpow, size_t n, uint8_t* d_cells) {
+    static bool attr_set[16] = {};
+    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
+        ZKW_TRY((Launcher<&k_kzg_cells, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+        attr_set[ctx->device & 15] = true;
+    }
+    ZKW_LAUNCH_D(ctx, k_kzg_cells, "k_kzg_cells", dim3((unsigned)n, 2), KZG_NTT_THREADS, KZG_NTT_LDS, src, poly_stride, d_evals, d_tw, d_wpow, d_cells);
+    return ZKW_OK;
+}
+
+// FK20 from the coefficients of n >= 1 polynomials read through src: the 128 proofs of each at d_proofs ([n][128][48])
+static int kzg_cell_proofs_device(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, KzgSrc src, u32 poly_stride, const bls::Fr* d_tw, size_t n, uint8_t* d_proofs) {
+    const size_t n_sums = n * KZG_CELLS;
+    uint8_t* d_c = nullptr;
+    bls::G1Jac *d_sums = nullptr, *d_h = nullptr;
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_cell_scalars", n_sums * 2048, &d_c));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_sums", n_sums * 8, &d_sums));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_points", n_sums, &d_h));
+    ZKW_LAUNCH_2D(ctx, k_kzg_cell_toeplitz, 16, n, KZG_CELL_FR_THREADS, src, poly_stride, d_tw, d_c);
+    ZKW_LAUNCH_2D(ctx, k_kzg_cell_msm, KZG_CELLS, n, KZG_CELL_MSM_THREADS, (const uint8_t*)d_c, (const bls::G1Aff*)cs->table, d_sums);
+    ZKW_LAUNCH(ctx, k_kzg_cell_horner, blocks_for(n_sums, 64), 64, (const bls::G1Jac*)d_sums, (u32)n_sums, d_h);
+    ZKW_TRY(kzg_g1_fft_device(ctx, d_h, d_h, 7, n, true, false, false));   // h (its 1 / 128 is in the scalars); entries 64..127 are not h
+    ZKW_TRY(kzg_g1_fft_device(ctx, d_h, d_h, 7, n, false, false, true));   // P[u] = sum_(j < 64) w128^(u j) h[j]
+    ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(n_sums, 64), 64, (const bls::G1Jac*)d_h, (u32)n_sums, 1u, d_proofs);
+    return ZKW_OK;
+}
+
+static int kzg_cells_check_call(const char* who, const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, size_t n) {
+    if (cs && ctx->device != cs->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, cs->ctx->device, ctx->device);
+    if (n > 32767) return fail(ZKW_ERR_INVALID, "%s: at most 32767 blobs per call, not %zu", who, n);
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_cells_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* cells) {
+    if (!ctx || (n && (!blob_evaluations || !cells))) return fail(ZKW_ERR_INVALID, "zkw_kzg_cells_blobs: null argument");
+    ZKW_TRY(kzg_cells_check_call("zkw_kzg_cells_blobs", nullptr, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_cells_blobs", ctx, d_ev, nullptr, n, &d_c));
+    const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
+    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, &d_wpow));
+    uint8_t* d_cells = nullptr;
+    ZKW_TRY(ctx->out("kzg_cells", cells, n * KZG_CELLS_BYTES, &d_cells));
+    ZKW_TRY(kzg_cells_device(ctx, KzgSrc{d_c, (u32)KZG_BLOB_ELEMENTS, 0}, (u32)KZG_EVAL_BYTES, d_ev, d_tw, d_wpow, n, d_cells));
+    ZKW_TRY(ctx->finish_out(cells, d_cells, n * KZG_CELLS_BYTES));
+    return ctx->sync_if_host();
+}
+
+// the routine both proof calls share: it starts at the coefficients (src), on the device
+static int kzg_cells_and_proofs(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, KzgSrc src, u32 poly_stride, const uint8_t* d_evals, size_t n, uint8_t* cells, uint8_t* proofs) {
+    const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
+    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, cells ? &d_wpow : nullptr));
+    uint8_t *d_cells = nullptr, *d_proofs = nullptr;
+    if (cells) {
+        ZKW_TRY(ctx->out("kzg_cells", cells, n * KZG_CELLS_BYTES, &d_cells));
+        ZKW_TRY(kzg_cells_device(ctx, src, poly_stride, d_evals, d_tw, d_wpow, n, d_cells));
+    }
+    ZKW_TRY(ctx->out("kzg_out", proofs, n * KZG_CELLS * 48, &d_proofs));
+    ZKW_TRY(kzg_cell_proofs_device(cs, ctx, src, poly_stride, d_tw, n, d_proofs));
+    if (cells) ZKW_TRY(ctx->finish_out(cells, d_cells, n * KZG_CELLS_BYTES));
+    ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * KZG_CELLS * 48));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_kzg_cell_proofs_blobs(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* cells, uint8_t* proofs) {
+    if (!cs || !ctx || (n && (!blob_evaluations || !proofs))) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_proofs_blobs: null argument");
+    ZKW_TRY(kzg_cells_check_call("zkw_kzg_cell_proofs_blobs", cs, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t *d_ev = nullptr, *d_c = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
+    ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_cell_proofs_blobs", ctx, d_ev, nullptr, n, &d_c));
+    return kzg_cells_and_proofs(cs, ctx, KzgSrc{d_c, (u32)KZG_BLOB_ELEMENTS, 0}, (u32)KZG_EVAL_BYTES, d_ev, n, cells, proofs);
+}
+
+extern "C" int zkw_eip4844_cell_proofs(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, const uint8_t* blobs, size_t n, uint8_t* cells, uint8_t* proofs) {
+    if (!cs || !ctx || (n && (!blobs || !proofs))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_cell_proofs: null argument");
+    ZKW_TRY(kzg_cells_check_call("zkw_eip4844_cell_proofs", cs, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint8_t* d_b = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_blobs", blobs, n * KZG_BLOB_BYTES, &d_b));  // (elements of 31 bytes: all below r)
+    return kzg_cells_and_proofs(cs, ctx, KzgSrc{d_b, (u32)KZG_BLOB_ELEMENTS, 1}, (u32)KZG_BLOB_BYTES, nullptr, n, cells, proofs);
 }

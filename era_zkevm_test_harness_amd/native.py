@@ -198,6 +198,13 @@ SYMBOLS = [
     ("zkw_kzg_commit_blobs", _int, [_vp, _vp, _vp, _sz, _vp]),
     ("zkw_kzg_open_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_eip4844_prove_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_kzg_g1_fft", _int, [_vp, _vp, _sz, _sz, _int, _vp]),
+    ("zkw_kzg_cell_settings_create", _int, [_vp, _vp, C.POINTER(_vp)]),
+    ("zkw_kzg_cell_settings_free", None, [_vp]),
+    ("zkw_kzg_cell_settings_bytes", _sz, [_vp]),
+    ("zkw_kzg_cells_blobs", _int, [_vp, _vp, _sz, _vp]),
+    ("zkw_kzg_cell_proofs_blobs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_eip4844_cell_proofs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -977,6 +984,81 @@ def kzg_blob_coefficients(ctx, evaluations):
     eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
     out, optr = KzgSettings._empty(ctx, _ke, (n, 4096, 32))
     _check(load().zkw_kzg_blob_coefficients(ctx.handle, eptr, n, optr))
+    return out
+
+
+EIP7594_CELLS = 128
+EIP7594_CELL_BYTES = 64 * 32
+
+
+class KzgCellSettings:
+    """zkw_kzg_cell_settings: the setup side of the EIP-7594 cell proofs (FK20), made from a `KzgSettings` of 4 096 points on a context
+    of its device: the G1 transforms of the 64 vectors x_i[m] = S[4031 - i - 64 m] as a byte-window table in HBM (`nbytes`). Immutable
+    afterwards and it keeps its context alive: the proof calls may run on any context of the same device (`ctx=`), several at once.
+    Arrays as for `KzgSettings`. Verification of cell proofs and recovery from half the cells are not offered."""
+
+    def __init__(self, settings, ctx=None):
+        self.ctx = ctx or settings.ctx
+        self.handle = C.c_void_p(None)
+        _check(load().zkw_kzg_cell_settings_create(settings.handle, self.ctx.handle, C.byref(self.handle)))
+
+    @property
+    def nbytes(self) -> int:
+        """device memory held by the table"""
+        return load().zkw_kzg_cell_settings_bytes(self.handle)
+
+    def _proofs(self, call, ctx, ptr, n, like, cells):
+        proofs, pptr = KzgSettings._empty(ctx, like, (n, EIP7594_CELLS, 48))
+        out, cptr = KzgSettings._empty(ctx, like, (n, EIP7594_CELLS, EIP7594_CELL_BYTES)) if cells else (None, None)
+        _check(call(self.handle, ctx.handle, ptr, n, cptr, pptr))
+        return (out, proofs) if cells else proofs
+
+    def cell_proofs_blobs(self, evaluations, ctx=None, cells=False):
+        """zkw_kzg_cell_proofs_blobs: `evaluations` = [n, 131072] bytes, blobs in evaluation form as a sidecar carries them; returns
+        [n, 128, 48] proofs: proof k = compress([q_k(tau)] G1), q_k the quotient of the blob's polynomial by X^64 - w128^brp7(k). With
+        `cells=True` returns (cells [n, 128, 2048], proofs). An element that is not below r raises ZkwError(ERR_INVALID) naming blob and
+        element."""
+        ctx = ctx or self.ctx
+        eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+        return self._proofs(load().zkw_kzg_cell_proofs_blobs, ctx, eptr, n, _ke, cells)
+
+    def eip4844_cell_proofs(self, blobs, ctx=None, cells=False):
+        """zkw_eip4844_cell_proofs: the same from `blobs` = [n, 126976] bytes of pubdata, `KzgSettings.eip4844_witness`'s form."""
+        ctx = ctx or self.ctx
+        bptr, n, _kb = KzgSettings._bytes(ctx, blobs, EIP4844_BLOB_BYTES)
+        return self._proofs(load().zkw_eip4844_cell_proofs, ctx, bptr, n, _kb, cells)
+
+    def free(self):
+        if self.handle:
+            load().zkw_kzg_cell_settings_free(self.handle)
+            self.handle = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def kzg_cells_blobs(ctx, evaluations):
+    """zkw_kzg_cells_blobs: `evaluations` = [n, 131072] bytes, blobs in evaluation form; returns [n, 128, 2048] bytes: the extended
+    blob e[j] = p(W^brp13(j)), W = 7^((r - 1) / 8192), cut into 128 cells of 64 elements of 32 big-endian bytes. Cells 0..63 are the
+    blob itself. An element that is not below r raises ZkwError(ERR_INVALID) naming blob and element. Arrays as for `KzgSettings`."""
+    eptr, n, _ke = KzgSettings._bytes(ctx, evaluations, EIP4844_EVALUATION_BYTES)
+    out, optr = KzgSettings._empty(ctx, _ke, (n, EIP7594_CELLS, EIP7594_CELL_BYTES))
+    _check(load().zkw_kzg_cells_blobs(ctx.handle, eptr, n, optr))
+    return out
+
+
+def kzg_g1_fft(ctx, points, n, inverse=False):
+    """zkw_kzg_g1_fft: `points` = [n_ffts, n, 48] bytes of compressed G1 points, n a power of two from 1 to 128; returns the same shape:
+    out[u] = sum_j w_n^(u j) in[j] with w_n = 7^((r - 1) / n), natural order; `inverse`: w_n^-1 and the factor 1 / n. A point that
+    `KzgSettings` would refuse raises ZkwError(ERR_INVALID) naming its position. Arrays as for `KzgSettings`."""
+    ptr, rows, _keep = KzgSettings._bytes(ctx, points, 48)
+    n_ffts = rows // n if n else 0
+    assert n_ffts * n == rows
+    out, optr = KzgSettings._empty(ctx, _keep, (n_ffts, n, 48))
+    _check(load().zkw_kzg_g1_fft(ctx.handle, ptr, n, n_ffts, 1 if inverse else 0, optr))
     return out
 
 

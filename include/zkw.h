@@ -841,6 +841,41 @@ int zkw_kzg_open_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *b
 int zkw_eip4844_prove_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
                             const uint8_t *commitments /*[n][48]*/, size_t n, uint8_t *proofs /*[n][48]*/,
                             uint8_t *openings /*[n][64] or NULL: challenge, then p(challenge), big-endian*/);
+/* EIP-7594 (PeerDAS): the 128 cells of a blob and one KZG multi-opening proof per cell — what a blob transaction carries since
+   that fork instead of the single blob proof.  The reference has no counterpart.  With r, w = 7^((r-1)/4096) as above,
+   W = 7^((r-1)/8192) (W^2 = w), w128 = w^32 and brpB the B-bit bit reversal:
+     cells: extended evaluation e[j] = p(W^brp13(j)), j < 8192; cell k = e[64k .. 64k+63], 64 x 32 big-endian bytes.  e[j] for
+       j < 4096 is the blob's own element j (cells 0..63 are the blob, byte for byte); e[4096+j] = p(W w^brp12(j)).
+     proof[k] = compress([q_k(tau)] G1), q_k the quotient of p by X^64 - c_k, c_k = w128^brp7(k) (the cell's 64 points are the
+       roots of that binomial; the remainder is the cell's interpolant).  A zero quotient is the point at infinity, 0xc0 then
+       47 zero bytes.
+   The 128 proofs of a blob are computed together (FK20: 128 sums of 64 terms over a fixed-base table, two transforms of 128
+   G1 points), not as 128 commitments.  zkw_kzg_cell_settings holds the setup side of that — the transforms of the 64 vectors
+   x_i[m] = S[4031-i-64m] as a byte-window table, 25 MB of HBM — and is created from a zkw_kzg_settings of 4096 points on a
+   context of its device (not one of a batch); like the settings handle it is immutable, retains its context until it is freed
+   and may be used from any context of the same device, several at once.
+   The three blob calls follow the contract of the producers above: pointer modes as the context's; ZKW_ERR_INVALID naming the
+   blob and the LOWEST offending element when one is not below r, the outputs then untouched; one readback per call in the
+   evaluation form, none in the pubdata form (31-byte elements are below r); n = 0 is a no-op; at most 32 767 blobs per call;
+   the context must be on the settings' device.  zkw_eip4844_cell_proofs takes zkw_eip4844_witness's blobs (element i = the
+   coefficient of X^(4095-i)) and needs no inverse transform; on the evaluations zkw_eip4844_prove returns for the same blobs
+   zkw_kzg_cell_proofs_blobs gives the same bytes.  cells may be NULL in the two proof calls.
+   zkw_kzg_g1_fft is the transform the proofs run on, for callers: n_ffts transforms of n compressed points each, n a power of
+   two from 1 to 128, natural order in and out: out[u] = sum_j w_n^(u j) in[j], w_n = 7^((r-1)/n); inverse != 0: w_n^-1 and the
+   factor 1/n.  The points are checked as zkw_kzg_settings_create checks them (the point at infinity is allowed); a bad one is
+   ZKW_ERR_INVALID naming its position and its transform, the outputs untouched.  At most 65 535 transforms per call.
+   Not offered: verification of cell proofs (it needs [tau^64] G2), recovery from half the cells, a Lagrange-basis setup. */
+typedef struct zkw_kzg_cell_settings zkw_kzg_cell_settings;
+int zkw_kzg_cell_settings_create(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_cell_settings **out);
+void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings *cs);
+size_t zkw_kzg_cell_settings_bytes(const zkw_kzg_cell_settings *cs); /* HBM held */
+int zkw_kzg_g1_fft(zkw_ctx *ctx, const uint8_t *points /*[n_ffts][n][48]*/, size_t n, size_t n_ffts, int inverse,
+                   uint8_t *out /*[n_ffts][n][48]*/);
+int zkw_kzg_cells_blobs(zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/, size_t n, uint8_t *cells /*[n][128][2048]*/);
+int zkw_kzg_cell_proofs_blobs(const zkw_kzg_cell_settings *cs, zkw_ctx *ctx, const uint8_t *blob_evaluations /*[n][131072]*/,
+                              size_t n, uint8_t *cells /*[n][128][2048] or NULL*/, uint8_t *proofs /*[n][128][48]*/);
+int zkw_eip4844_cell_proofs(const zkw_kzg_cell_settings *cs, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n,
+                            uint8_t *cells /*[n][128][2048] or NULL*/, uint8_t *proofs /*[n][128][48]*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
