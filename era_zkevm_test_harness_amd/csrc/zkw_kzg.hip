@@ -5,14 +5,16 @@
 // (verify_proof_poly), and the producers from a blob in evaluation form, zkw_kzg_blob_coefficients, zkw_kzg_commit_blobs,
 // zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them), and
 // the EIP-7594 cells and cell proofs, zkw_kzg_cell_settings with zkw_kzg_g1_fft, zkw_kzg_cells_blobs, zkw_kzg_cell_proofs_blobs and
-// zkw_eip4844_cell_proofs (the reference has no counterpart). Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh,
-// kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
+// zkw_eip4844_cell_proofs, and the way back from any half of the cells, zkw_kzg_recover_cells_blobs (the reference has no counterpart).
+// Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh,
+// kzg_recover_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
 #include "kzg_open_kernels.cuh"
 #include "kzg_eval_kernels.cuh"
 #include "kzg_verify_kernels.cuh"
 #include "kzg_cell_kernels.cuh"
+#include "kzg_recover_kernels.cuh"
 
 #include <cstddef>
 
@@ -766,4 +768,71 @@ extern "C" int zkw_eip4844_cell_proofs(const zkw_kzg_cell_settings* cs, zkw_ctx*
     const uint8_t* d_b = nullptr;
     ZKW_TRY(ctx->in("kzg_in_blobs", blobs, n * KZG_BLOB_BYTES, &d_b));  // (elements of 31 bytes: all below r)
     return kzg_cells_and_proofs(cs, ctx, KzgSrc{d_b, (u32)KZG_BLOB_ELEMENTS, 1}, (u32)KZG_BLOB_BYTES, nullptr, n, cells, proofs);
+}
+
+// ---- EIP-7594 recovery: every cell (and proof) of a blob from any 64 or more of its cells (kzg_recover_kernels.cuh) -----------------------
+static_assert(sizeof(KzgSlots) == KZG_CELLS, "the slot table is 128 bytes of kernel argument");
+
+extern "C" int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, const uint8_t* cell_indices, size_t n_cells, const uint8_t* cells, size_t n,
+                                           uint8_t* recovered, uint8_t* proofs) {
+    const char* who = "zkw_kzg_recover_cells_blobs";
+    if (!ctx || (n && (!cells || !recovered))) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (n_cells < KZG_CELL_ELEMENTS || n_cells > KZG_CELLS) return fail(ZKW_ERR_INVALID, "%s: 64 to 128 cells, not %zu", who, n_cells);
+    if (!cell_indices) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    KzgSlots slots;
+    memset(slots.slot, KZG_RECOVER_ABSENT, sizeof slots.slot);
+    for (size_t i = 0; i < n_cells; i++) {
+        if (cell_indices[i] >= KZG_CELLS) return fail(ZKW_ERR_INVALID, "%s: cell_indices[%zu] is %u, a cell index is below 128", who, i, (unsigned)cell_indices[i]);
+        if (i && cell_indices[i] <= cell_indices[i - 1])
+            return fail(ZKW_ERR_INVALID, "%s: cell_indices[%zu] is %u after %u: the indices must ascend strictly", who, i, (unsigned)cell_indices[i], (unsigned)cell_indices[i - 1]);
+        slots.slot[cell_indices[i]] = (uint8_t)i;
+    }
+    if (proofs && !cs) return fail(ZKW_ERR_INVALID, "%s: proofs need cell settings", who);
+    ZKW_TRY(kzg_cells_check_call(who, cs, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    static bool attr_set[16] = {};
+    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
+        ZKW_TRY((Launcher<&k_kzg_recover_halves, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+        ZKW_TRY((Launcher<&k_kzg_recover_quotient, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+        attr_set[ctx->device & 15] = true;
+    }
+    const uint8_t* d_in = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_cells", cells, n * n_cells * KZG_CELL_BYTES, &d_in));
+    const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
+    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, &d_wpow));
+    bls::Fr* d_z = nullptr;  // z(c_k), k < 128, then the 64 inverses of Z on the coset
+    uint8_t *d_ab = nullptr, *d_c = nullptr, *d_full = nullptr;
+    u32* d_st = nullptr;  // [n][2] range words, then [n] consistency words
+    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_recover_vanish", KZG_CELLS + KZG_CELL_ELEMENTS, &d_z));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_recover_halves", 2 * n * KZG_EVAL_BYTES, &d_ab));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_blob_coeffs", n * KZG_EVAL_BYTES, &d_c));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_recover_cells", n * KZG_CELLS_BYTES, &d_full));  // (scratch in both pointer modes: a refused call leaves `recovered` untouched)
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_recover_status", 3 * n, &d_st));
+    const bls::Fr* d_zinv = d_z + KZG_CELLS;
+    const unsigned nb = (unsigned)n;
+    ZKW_LAUNCH(ctx, k_kzg_recover_vanish, 1, KZG_RECOVER_VANISH_THREADS, slots, d_tw, d_z, d_z + KZG_CELLS);
+    ZKW_LAUNCH_D(ctx, k_kzg_recover_halves, "k_kzg_recover_halves", dim3(nb, 2), KZG_NTT_THREADS, KZG_NTT_LDS, slots, d_in, (u32)n_cells, (const bls::Fr*)d_z, d_tw, d_wpow,
+                 d_ab, d_st);
+    ZKW_LAUNCH_D(ctx, k_kzg_recover_quotient, "k_kzg_recover_quotient", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, (const uint8_t*)d_ab, d_zinv, d_tw, d_c, d_st + 2 * n);
+    const KzgSrc src{d_c, (u32)KZG_BLOB_ELEMENTS, 0};
+    ZKW_TRY(kzg_cells_device(ctx, src, (u32)KZG_EVAL_BYTES, nullptr, d_tw, d_wpow, n, d_full));
+    ZKW_LAUNCH_2D(ctx, k_kzg_recover_check, KZG_CELLS, n, KZG_RECOVER_CHECK_THREADS, slots, d_in, (u32)n_cells, (const uint8_t*)d_full, d_st + 2 * n);
+    std::vector<u32> st(3 * n);  // the call's ONE readback, ahead of anything that writes the caller's buffers
+    ZKW_TRY(ctx->read_small(st.data(), d_st, 3 * n * sizeof(u32)));
+    for (size_t j = 0; j < n; j++) {
+        const u32 lo = st[2 * j] - 1u, hi = st[2 * j + 1] - 1u, bad = lo < hi ? lo : hi;  // (0 - 1: no offender)
+        if (bad != ~0u)
+            return fail(ZKW_ERR_INVALID, "%s: element %u of cell_indices[%u] (cell %u) of blob %zu is not below r", who, bad & 63u, bad >> 6, (unsigned)cell_indices[bad >> 6], j);
+    }
+    for (size_t j = 0; j < n; j++)
+        if (st[2 * n + j]) return fail(ZKW_ERR_INVALID, "%s: the %zu cells of blob %zu do not lie on one polynomial of degree below 4096", who, n_cells, j);
+    HIP_TRY(ctx->copy_async(recovered, d_full, n * KZG_CELLS_BYTES, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (proofs) {
+        uint8_t* d_proofs = nullptr;
+        ZKW_TRY(ctx->out("kzg_out", proofs, n * KZG_CELLS * 48, &d_proofs));
+        ZKW_TRY(kzg_cell_proofs_device(cs, ctx, src, (u32)KZG_EVAL_BYTES, d_tw, n, d_proofs));
+        ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * KZG_CELLS * 48));
+    }
+    return ctx->sync_if_host();
 }

@@ -205,6 +205,7 @@ SYMBOLS = [
     ("zkw_kzg_cells_blobs", _int, [_vp, _vp, _sz, _vp]),
     ("zkw_kzg_cell_proofs_blobs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_eip4844_cell_proofs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zkw_kzg_recover_cells_blobs", _int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -995,7 +996,8 @@ class KzgCellSettings:
     """zkw_kzg_cell_settings: the setup side of the EIP-7594 cell proofs (FK20), made from a `KzgSettings` of 4 096 points on a context
     of its device: the G1 transforms of the 64 vectors x_i[m] = S[4031 - i - 64 m] as a byte-window table in HBM (`nbytes`). Immutable
     afterwards and it keeps its context alive: the proof calls may run on any context of the same device (`ctx=`), several at once.
-    Arrays as for `KzgSettings`. Verification of cell proofs and recovery from half the cells are not offered."""
+    Arrays as for `KzgSettings`. `recover_cells_and_proofs` (and `kzg_recover_cells`, which needs no settings) is the way back from any 64
+    of the 128 cells. Verification of cell proofs is not offered."""
 
     def __init__(self, settings, ctx=None):
         self.ctx = ctx or settings.ctx
@@ -1028,6 +1030,14 @@ class KzgCellSettings:
         bptr, n, _kb = KzgSettings._bytes(ctx, blobs, EIP4844_BLOB_BYTES)
         return self._proofs(load().zkw_eip4844_cell_proofs, ctx, bptr, n, _kb, cells)
 
+    def recover_cells_and_proofs(self, cell_indices, cells, ctx=None):
+        """zkw_kzg_recover_cells_blobs (recover_cells_and_kzg_proofs of the consensus specs): `cell_indices` = the n_cells indices of the
+        cells present, strictly ascending, 64 to 128 of them, ONE list for every blob of the call (a host sequence in both pointer
+        modes); `cells` = [n, n_cells, 2048] bytes, `cells[b][i]` = cell `cell_indices[i]` of blob b. Returns (cells [n, 128, 2048],
+        proofs [n, 128, 48]): what `cell_proofs_blobs(cells=True)` gives for the blob. An element that is not below r, or a set of more
+        than 64 cells that lies on no polynomial of degree below 4 096, raises ZkwError(ERR_INVALID) naming the blob."""
+        return _kzg_recover(self.handle, ctx or self.ctx, cell_indices, cells, True)
+
     def free(self):
         if self.handle:
             load().zkw_kzg_cell_settings_free(self.handle)
@@ -1048,6 +1058,27 @@ def kzg_cells_blobs(ctx, evaluations):
     out, optr = KzgSettings._empty(ctx, _ke, (n, EIP7594_CELLS, EIP7594_CELL_BYTES))
     _check(load().zkw_kzg_cells_blobs(ctx.handle, eptr, n, optr))
     return out
+
+
+def _kzg_recover(cs_handle, ctx, cell_indices, cells, want_proofs):
+    idx = [int(k) for k in cell_indices]
+    if any(not 0 <= k < 256 for k in idx):
+        raise ValueError("a cell index is a byte")
+    idx = np.array(idx, np.uint8)
+    cptr, rows, _kc = KzgSettings._bytes(ctx, cells, EIP7594_CELL_BYTES)
+    n = rows // idx.size if idx.size else 0
+    assert n * idx.size == rows
+    out, optr = KzgSettings._empty(ctx, _kc, (n, EIP7594_CELLS, EIP7594_CELL_BYTES))
+    proofs, pptr = KzgSettings._empty(ctx, _kc, (n, EIP7594_CELLS, 48)) if want_proofs else (None, None)
+    _check(load().zkw_kzg_recover_cells_blobs(cs_handle, ctx.handle, _np_ptr(idx) if idx.size else None, idx.size, cptr, n, optr, pptr))
+    return (out, proofs) if want_proofs else out
+
+
+def kzg_recover_cells(ctx, cell_indices, cells):
+    """zkw_kzg_recover_cells_blobs without proofs (no settings needed): all 128 cells of n blobs from any 64 or more of them; arguments as
+    for `KzgCellSettings.recover_cells_and_proofs`. Returns [n, 128, 2048] bytes: what `kzg_cells_blobs` gives for the blob, cells 0..63
+    being the blob in evaluation form. Arrays as for `KzgSettings`."""
+    return _kzg_recover(None, ctx, cell_indices, cells, False)
 
 
 def kzg_g1_fft(ctx, points, n, inverse=False):

@@ -864,7 +864,8 @@ int zkw_eip4844_prove_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8
    two from 1 to 128, natural order in and out: out[u] = sum_j w_n^(u j) in[j], w_n = 7^((r-1)/n); inverse != 0: w_n^-1 and the
    factor 1/n.  The points are checked as zkw_kzg_settings_create checks them (the point at infinity is allowed); a bad one is
    ZKW_ERR_INVALID naming its position and its transform, the outputs untouched.  At most 65 535 transforms per call.
-   Not offered: verification of cell proofs (it needs [tau^64] G2), recovery from half the cells, a Lagrange-basis setup. */
+   Not offered: verification of cell proofs (it needs [tau^64] G2), a Lagrange-basis setup.  Recovery from half the cells is
+   zkw_kzg_recover_cells_blobs below. */
 typedef struct zkw_kzg_cell_settings zkw_kzg_cell_settings;
 int zkw_kzg_cell_settings_create(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_cell_settings **out);
 void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings *cs);
@@ -876,6 +877,25 @@ int zkw_kzg_cell_proofs_blobs(const zkw_kzg_cell_settings *cs, zkw_ctx *ctx, con
                               size_t n, uint8_t *cells /*[n][128][2048] or NULL*/, uint8_t *proofs /*[n][128][48]*/);
 int zkw_eip4844_cell_proofs(const zkw_kzg_cell_settings *cs, zkw_ctx *ctx, const uint8_t *blobs /*[n][126976]*/, size_t n,
                             uint8_t *cells /*[n][128][2048] or NULL*/, uint8_t *proofs /*[n][128][48]*/);
+/* EIP-7594 recovery (recover_cells_and_kzg_proofs of the consensus specs): every cell, and with settings every cell proof, of
+   n blobs from any 64 or more of their 128 cells.  ONE index list serves every blob of the call (custody is by column, so the
+   blobs of a block arrive with the same cells present): cell_indices is n_cells bytes of HOST memory in both pointer modes,
+   strictly ascending, each below 128, 64 <= n_cells <= 128.  cells[b][i] is cell cell_indices[i] of blob b in the byte form
+   zkw_kzg_cells_blobs writes.  recovered is what zkw_kzg_cells_blobs would give for the blob (cells 0..63 are the blob in
+   evaluation form), proofs what zkw_kzg_cell_proofs_blobs would give; proofs may be NULL, and cs may then be NULL too.
+   The polynomial comes from the vanishing polynomial of the missing cells over a coset (three transforms of 4 096 elements a
+   blob, none of 8 192), the cells from zkw_kzg_cells_blobs' kernel and the proofs from FK20 as they are.  Every supplied cell is
+   then compared byte for byte with the recomputed one, so a set that lies on no polynomial of degree below 4096 (possible
+   only with more than 64 cells) is refused — naming the blob, not a cell: an inconsistent set has no single wrong cell.
+   ZKW_ERR_INVALID, named in zkw_last_error, with BOTH outputs untouched in both pointer modes: n_cells out of range; an index
+   of 128 or more or one that does not ascend (naming its position in the list); proofs without settings; settings and context
+   on different devices; more than 32 767 blobs; a supplied element not below r (naming blob, position in the list and
+   element); an inconsistent set.  One readback per call, ahead of every write to recovered or proofs (the results are staged
+   in context scratch and copied afterwards).  n = 0 is a no-op.  Not offered: a per-blob index list, verification of cell proofs. */
+int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings *cs /* may be NULL when proofs is NULL */, zkw_ctx *ctx,
+                                const uint8_t *cell_indices /*[n_cells], HOST memory in both pointer modes*/, size_t n_cells,
+                                const uint8_t *cells /*[n][n_cells][2048]*/, size_t n,
+                                uint8_t *recovered /*[n][128][2048]*/, uint8_t *proofs /*[n][128][48] or NULL*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
