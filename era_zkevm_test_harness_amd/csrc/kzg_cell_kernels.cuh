@@ -16,7 +16,7 @@
 //   k_kzg_cell_wpow       W^k, k < 4096
 //   k_kzg_cells           a workgroup per (blob, half): cells 64..127 = the blob's forward transform of the coefficients scaled by W^k;
 //                         cells 0..63 = the blob itself (copied) or the unscaled transform (pubdata form)
-//   k_kzg_cell_toeplitz   a wave per (offset i, blob): t_i from the coefficients, seven stages in LDS, C_i / 128 as scalar bytes [j][i]
+//   k_kzg_cell_toeplitz   a wave per (offset i, blob): t_i from the coefficients, kzg_fr_ntt128 in LDS, C_i / 128 as scalar bytes [j][i]
 //   k_kzg_cell_msm        a workgroup per (j, blob): the 64 x 32 digits of C_.[j] in LDS, a LANE per bucket d (it walks the digits for the next
 //                         one equal to d and adds the table entry), the 255 buckets through LDS into the eight bit sums of k_kzg_finish
 //   k_kzg_cell_horner     a lane per (j, blob): H[j] = sum_b 2^b sums[b], kept Jacobian
@@ -176,7 +176,7 @@ static __device__ __forceinline__ void k_kzg_cell_wpow(const VB& vb, bls::Fr* __
     const bls::Fr w = kzg_cell_w();
     bls::Fr pw = bls::one<bls::FrT>();
 #pragma unroll 1
-    for (int bit = 11; bit >= 0; bit--) {
+    for (int bit = 11; bit >= 0; bit--) {  // (kzg_fr_pow(w, k, 12) written out: see there)
         pw = bls::sqr(pw);
         const bls::Fr with = bls::mul<bls::FrT>(pw, w);
         pw = bls::select((k >> bit) & 1, with, pw);
@@ -185,7 +185,7 @@ static __device__ __forceinline__ void k_kzg_cell_wpow(const VB& vb, bls::Fr* __
 }
 
 // grid (n_blobs, 2), 512 lanes, KZG_NTT_LDS bytes of dynamic LDS. cells: [n_blobs][128][2048], any address. Half 1 (cells 64..127): element j
-// = p(W w^brp12(j)), k_kzg_blob_ntt's twelve stages on the coefficients scaled by W^k. Half 0 (cells 0..63): the blob's own evaluation form —
+// = p(W w^brp12(j)), kzg_fr_ntt4096 on the coefficients scaled by W^k. Half 0 (cells 0..63): the blob's own evaluation form —
 // copied from `evals` ([n_blobs][131072], any address) when that is given, else the same transform unscaled. The polynomial is read through
 // src (a blob of 31-byte elements or rows of 32 little-endian bytes), blob b at src.base + b * poly_stride
 static __device__ __forceinline__ void k_kzg_cells(const VB& vb, KzgSrc src, u32 poly_stride, const uint8_t* __restrict__ evals, const bls::Fr* __restrict__ tw,
@@ -214,35 +214,12 @@ static __device__ __forceinline__ void k_kzg_cells(const VB& vb, KzgSrc src, u32
         kzg_lds_put(x, k, c);
     }
     __syncthreads();
-#pragma unroll 1
-    for (u32 s = 0; s < 12; s++) {
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
-            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
-            kzg_lds_put(x, i0, bls::add(u, v));
-            bls::Fr d = bls::sub(u, v);
-            if (s < 11) d = bls::mul<bls::FrT>(d, tw[j << s]);  // (the last stage's only twiddle is 1)
-            kzg_lds_put(x, i1, d);
-        }
-        __syncthreads();
-    }
-#pragma unroll 1
-    for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {
-        const bls::Fr v = kzg_lds_get(x, i);
-        if (aligned) {
-            u32* o = reinterpret_cast<u32*>(out + 32 * (size_t)i);
-#pragma unroll
-            for (int m = 0; m < 8; m++) o[m] = __builtin_bswap32(v.w[7 - m]);
-        } else {
-            kzg_put_be32(out + 32 * (size_t)i, v);
-        }
-    }
+    kzg_fr_ntt4096(x, t, tw);
+    kzg_store_be32_rows(x, t, out, aligned);
 }
 
 // grid (16, n_blobs), 256 lanes: wave v of workgroup g takes offset i = 4 g + v. t_i[0] = p[4095 - i], t_i[1..65] = 0, t_i[66 + m] = p[127 - i + 64 m]
-// (m < 62); C_i = Fr_FFT_128(t_i) with w128 = w^32 (tw: k_kzg_twiddles' table of w^j), seven stages as in k_kzg_blob_ntt, times 1 / 128 — the
+// (m < 62); C_i = Fr_FFT_128(t_i) with w128 = w^32 (tw: k_kzg_twiddles' table of w^j) by kzg_fr_ntt128, times 1 / 128 — the
 // factor of the inverse G1 transform that follows the sums, taken here where it is one product in Fr. c: [n_blobs][128][64][32], the scalar
 // C_i[j] as 32 little-endian bytes at row j, column i: the 2 048 digit bytes of a sum H[j] are contiguous (32-byte aligned)
 static __device__ __forceinline__ void k_kzg_cell_toeplitz(const VB& vb, KzgSrc src, u32 poly_stride, const bls::Fr* __restrict__ tw, uint8_t* __restrict__ c) {
@@ -257,17 +234,7 @@ static __device__ __forceinline__ void k_kzg_cell_toeplitz(const VB& vb, KzgSrc 
     kzg_lds_put(x, l, lo);
     kzg_lds_put(x, 64 + l, hi);
     __syncthreads();
-#pragma unroll 1
-    for (u32 s = 0; s < 7; s++) {
-        const u32 half = 64u >> s;
-        const u32 j = l & (half - 1), i0 = ((l >> (6 - s)) << (7 - s)) | j, i1 = i0 + half;  // i1 <= 127
-        const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
-        kzg_lds_put(x, i0, bls::add(u, v));
-        bls::Fr d = bls::sub(u, v);
-        if (s < 6) d = bls::mul<bls::FrT>(d, tw[(j << s) * 32u]);  // w128^(j 2^s) = w^(32 j 2^s), index <= 32 * 63
-        kzg_lds_put(x, i1, d);
-        __syncthreads();
-    }
+    kzg_fr_ntt128(x, l, tw);
     // 1 / 128 in Montgomery form is 2^256 / 2^7 = 2^249, which is below r as it stands
     bls::Fr inv_width = bls::zero<bls::FrT>();
     inv_width.w[7] = 1u << 25;

@@ -17,6 +17,8 @@
 //   k_kzg_blob_challenge  a wave per blob: SHA-256 over "FSBLOBVERIFY_V1_" || 4096 || evaluation form || commitment (2 050 blocks),
 //                         reduced below r
 //   k_kzg_proofs_out      the 2 n compressed proofs into the n records
+// The transforms in Fr of this header and of kzg_cell_kernels.cuh and kzg_recover_kernels.cuh are written ONCE, here: kzg_fr_ntt4096 and
+// kzg_fr_intt4096 (the twelve stages and the twelve undone), kzg_fr_ntt128 (seven stages, a wave), kzg_fr_pow (the recovery kernels') and kzg_store_be32_rows.
 // As in k_kzg_tail, z and the twiddles are in Montgomery form and the running values PLAIN: mul(plain, Montgomery) is plain, so no
 // element is converted on the way in or out. Every kernel is a body for both launch forms (zkw_launch.h).
 #pragma once
@@ -60,6 +62,101 @@ static __device__ __forceinline__ void kzg_put_be32(uint8_t* out, const bls::Fr&
         out[4 * m + 1] = (uint8_t)(w >> 16);
         out[4 * m + 2] = (uint8_t)(w >> 8);
         out[4 * m + 3] = (uint8_t)w;
+    }
+}
+
+// ---- what the transforms in Fr share (this header, kzg_cell_kernels.cuh, kzg_recover_kernels.cuh) ---------------------------------------
+// base^e for e < 2^bits, by square-and-multiply with uniform control flow (Montgomery form). The recovery kernels call it; k_kzg_twiddles
+// and k_kzg_cell_wpow keep the same loop written out with a constant count: called through here the compiler counts their loop another way
+// (the same work in other instructions), and a refactor moves no instruction
+static __device__ __forceinline__ bls::Fr kzg_fr_pow(const bls::Fr& base, u32 e, int bits) {
+    bls::Fr pw = bls::one<bls::FrT>();
+#pragma unroll 1
+    for (int bit = bits - 1; bit >= 0; bit--) {
+        pw = bls::sqr(pw);
+        const bls::Fr with = bls::mul<bls::FrT>(pw, base);
+        pw = bls::select((e >> bit) & 1, with, pw);
+    }
+    return pw;
+}
+
+static __device__ __forceinline__ bls::Fr kzg_lds_get(const uint4* x, u32 i) {
+    const uint4 a = x[2 * i], b = x[2 * i + 1];
+    return bls::Fr{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+}
+static __device__ __forceinline__ void kzg_lds_put(uint4* x, u32 i, const bls::Fr& v) {
+    x[2 * i] = uint4{v.w[0], v.w[1], v.w[2], v.w[3]};
+    x[2 * i + 1] = uint4{v.w[4], v.w[5], v.w[6], v.w[7]};
+}
+
+// The twelve decimation-in-frequency stages over x[0 .. 4095] (plain elements in LDS, 16-byte aligned), lane t of KZG_NTT_THREADS, tw =
+// k_kzg_twiddles' table; every lane of the workgroup calls it, behind a barrier after the last write of x, and it ends on a barrier. Stage s
+// has half-width h = 2048 >> s and pairs x[i0] with x[i1 = i0 + h]: butterfly b < 2048 has j = b mod h and i0 = (b div h) 2 h + j, and
+// (u, v) -> (u + v, (u - v) w^(j 2048 / h)) = tw[j << s]. Natural order in, bit-reversed order out: position i holds the value at w^brp12(i)
+static __device__ __forceinline__ void kzg_fr_ntt4096(uint4* x, u32 t, const bls::Fr* __restrict__ tw) {
+#pragma unroll 1
+    for (u32 s = 0; s < 12; s++) {
+        const u32 half = 2048u >> s;
+#pragma unroll 1
+        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
+            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
+            const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
+            kzg_lds_put(x, i0, bls::add(u, v));
+            bls::Fr d = bls::sub(u, v);
+            if (s < 11) d = bls::mul<bls::FrT>(d, tw[j << s]);  // (the last stage's only twiddle is 1)
+            kzg_lds_put(x, i1, d);
+        }
+        __syncthreads();
+    }
+}
+// The same twelve stages undone last first, under the same conditions: bit-reversed order in, natural order out, every element 4 096 times
+// the inverse transform (the caller's one product by 1 / 4096). A forward stage sent (u, v) to (a, b) = (u + v, (u - v) w^e), e = j 2048 / h,
+// so (2 u, 2 v) = (a + b w^-e, a - b w^-e), and w^-e = -w^(2048 - e) (w^2048 = -1): the same table with add and sub exchanged, for e = 0
+// entry 0 with them as they are
+static __device__ __forceinline__ void kzg_fr_intt4096(uint4* x, u32 t, const bls::Fr* __restrict__ tw) {
+#pragma unroll 1
+    for (u32 s = 12; s-- > 0;) {
+        const u32 half = 2048u >> s;
+#pragma unroll 1
+        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
+            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
+            const bls::Fr u = kzg_lds_get(x, i0);
+            bls::Fr m = kzg_lds_get(x, i1);
+            if (s < 11) m = bls::mul<bls::FrT>(m, tw[(2048u - (j << s)) & 2047u]);  // (the first stage undone has no twiddle but 1)
+            const bls::Fr with = bls::add(u, m), without = bls::sub(u, m);
+            kzg_lds_put(x, i0, bls::select(j == 0, with, without));
+            kzg_lds_put(x, i1, bls::select(j == 0, without, with));
+        }
+        __syncthreads();
+    }
+}
+// The seven stages of the same form over x[0 .. 127], one wave, lane l < 64 a butterfly, with w128 = w^32 from the same table: natural
+// order in, position q = the value at w128^brp7(q) out. Every lane of the WORKGROUP calls it (each stage ends on the workgroup's barrier)
+static __device__ __forceinline__ void kzg_fr_ntt128(uint4* x, u32 l, const bls::Fr* __restrict__ tw) {
+#pragma unroll 1
+    for (u32 s = 0; s < 7; s++) {
+        const u32 half = 64u >> s;
+        const u32 j = l & (half - 1), i0 = ((l >> (6 - s)) << (7 - s)) | j, i1 = i0 + half;  // i1 <= 127
+        const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
+        kzg_lds_put(x, i0, bls::add(u, v));
+        bls::Fr d = bls::sub(u, v);
+        if (s < 6) d = bls::mul<bls::FrT>(d, tw[(j << s) * 32u]);  // w128^(j 2^s) = w^(32 j 2^s), index <= 32 * 63
+        kzg_lds_put(x, i1, d);
+        __syncthreads();
+    }
+}
+// x[0 .. 4095] out as rows of 32 big-endian bytes, lane t of KZG_NTT_THREADS: word stores when the rows are 4-byte aligned
+static __device__ __forceinline__ void kzg_store_be32_rows(const uint4* x, u32 t, uint8_t* out, bool aligned) {
+#pragma unroll 1
+    for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {
+        const bls::Fr v = kzg_lds_get(x, i);
+        if (aligned) {
+            u32* o = reinterpret_cast<u32*>(out + 32 * (size_t)i);
+#pragma unroll
+            for (int m = 0; m < 8; m++) o[m] = __builtin_bswap32(v.w[7 - m]);
+        } else {
+            kzg_put_be32(out + 32 * (size_t)i, v);
+        }
     }
 }
 
@@ -141,7 +238,7 @@ static __device__ __forceinline__ void k_kzg_twiddles(const VB& vb, bls::Fr* __r
     const bls::Fr w = kzg_omega();
     bls::Fr pw = bls::one<bls::FrT>();
 #pragma unroll 1
-    for (int bit = 10; bit >= 0; bit--) {
+    for (int bit = 10; bit >= 0; bit--) {  // (kzg_fr_pow(w, j, 11) written out: see there)
         pw = bls::sqr(pw);
         const bls::Fr with = bls::mul<bls::FrT>(pw, w);
         pw = bls::select((j >> bit) & 1, with, pw);
@@ -149,18 +246,9 @@ static __device__ __forceinline__ void k_kzg_twiddles(const VB& vb, bls::Fr* __r
     tw[j] = pw;
 }
 
-static __device__ __forceinline__ bls::Fr kzg_lds_get(const uint4* x, u32 i) {
-    const uint4 a = x[2 * i], b = x[2 * i + 1];
-    return bls::Fr{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-static __device__ __forceinline__ void kzg_lds_put(uint4* x, u32 i, const bls::Fr& v) {
-    x[2 * i] = uint4{v.w[0], v.w[1], v.w[2], v.w[3]};
-    x[2 * i + 1] = uint4{v.w[4], v.w[5], v.w[6], v.w[7]};
-}
-
 // grid n_blobs, 512 lanes, KZG_NTT_LDS bytes of dynamic LDS. evals: [n_blobs][4096][32] big-endian, element i = p(w^brp12(i)) for
-// p(X) = sum_i e_i X^(4095 - i). A stage of half-width h pairs x[i] with x[i + h]: (u, v) -> (u + v, (u - v) w^(j 2048 / h)), j = i mod h;
-// after the twelfth the array is the transform in bit-reversed order, which is the order the blob's evaluation form has
+// p(X) = sum_i e_i X^(4095 - i): kzg_fr_ntt4096 on the coefficients leaves the transform in bit-reversed order, which is the order the
+// blob's evaluation form has
 static __device__ __forceinline__ void k_kzg_blob_ntt(const VB& vb, const uint8_t* __restrict__ blobs, const bls::Fr* __restrict__ tw, uint8_t* __restrict__ evals) {
     extern __shared__ __attribute__((aligned(16))) uint4 kzg_ntt_lds[];
     uint4* x = kzg_ntt_lds;
@@ -169,33 +257,10 @@ static __device__ __forceinline__ void k_kzg_blob_ntt(const VB& vb, const uint8_
 #pragma unroll 1
     for (u32 k = t; k < 4096; k += KZG_NTT_THREADS) kzg_lds_put(x, k, kzg_coeff_from_top(src, src.base, 4095 - k));  // x[k]: the coefficient of X^k
     __syncthreads();
-#pragma unroll 1
-    for (u32 s = 0; s < 12; s++) {
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
-            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
-            kzg_lds_put(x, i0, bls::add(u, v));
-            bls::Fr d = bls::sub(u, v);
-            if (s < 11) d = bls::mul<bls::FrT>(d, tw[j << s]);  // (the last stage's only twiddle is 1)
-            kzg_lds_put(x, i1, d);
-        }
-        __syncthreads();
-    }
+    kzg_fr_ntt4096(x, t, tw);
     uint8_t* out = evals + (size_t)vb.x * KZG_EVAL_BYTES;
     const bool aligned = (reinterpret_cast<uintptr_t>(evals) & 3) == 0;  // (a caller's device pointer may be odd)
-#pragma unroll 1
-    for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {
-        const bls::Fr v = kzg_lds_get(x, i);
-        if (aligned) {
-            u32* o = reinterpret_cast<u32*>(out + 32 * (size_t)i);
-#pragma unroll
-            for (int m = 0; m < 8; m++) o[m] = __builtin_bswap32(v.w[7 - m]);
-        } else {
-            kzg_put_be32(out + 32 * (size_t)i, v);
-        }
-    }
+    kzg_store_be32_rows(x, t, out, aligned);
 }
 
 // 32 big-endian bytes as plain words: eight word loads when the address allows, byte loads otherwise
@@ -217,10 +282,8 @@ static __device__ __forceinline__ bls::Fr kzg_get_be32(const uint8_t* b, bool al
 
 // The way back: grid n_blobs, 512 lanes, KZG_NTT_LDS bytes of dynamic LDS. evals: [n_blobs][4096][32] big-endian, element i = p(w^brp12(i)),
 // any address. coeffs: [n_blobs][4096][32] little-endian, row k = the coefficient of X^k (KzgSrc{.., 4096, 0}: what k_kzg_quotient and
-// k_kzg_accumulate read), 16-byte aligned. The twelve stages of k_kzg_blob_ntt undone last first, on bit-reversed-order input with
-// natural-order output: a forward stage of half-width h sent (u, v) to (a, b) = (u + v, (u - v) w^e), e = j 2048 / h, so
-// (2 u, 2 v) = (a + b w^-e, a - b w^-e), and w^-e = -w^(2048 - e) (w^2048 = -1): the table of k_kzg_twiddles with add and sub exchanged,
-// for e = 0 entry 0 with them as they are. The twelve factors of two leave with one product by 1 / 4096 per element on the way out.
+// k_kzg_accumulate read), 16-byte aligned. kzg_fr_intt4096 on the evaluation form as it is (bit-reversed order in, natural order out); the
+// twelve factors of two leave with one product by 1 / 4096 per element on the way out.
 // status[blob]: 0, or 1 + e for the LOWEST element index e that is not below r (k_kzg_blob_eval's form); such a blob is not transformed.
 // points (may be null): [n_blobs][32] big-endian; status[n_blobs + blob] = 1 when the blob's point is not below r, else 0
 static __device__ __forceinline__ void k_kzg_blob_intt(const VB& vb, const uint8_t* __restrict__ evals, const bls::Fr* __restrict__ tw, uint8_t* __restrict__ coeffs,
@@ -244,21 +307,7 @@ static __device__ __forceinline__ void k_kzg_blob_intt(const VB& vb, const uint8
     const u32 bad = s_bad;  // (the same for every lane: all leave, or none)
     if (t == 0) status[vb.x] = bad + 1u;
     if (bad != ~0u) return;
-#pragma unroll 1
-    for (u32 s = 12; s-- > 0;) {
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
-            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0);
-            bls::Fr m = kzg_lds_get(x, i1);
-            if (s < 11) m = bls::mul<bls::FrT>(m, tw[(2048u - (j << s)) & 2047u]);  // (the first stage undone has no twiddle but 1)
-            const bls::Fr with = bls::add(u, m), without = bls::sub(u, m);
-            kzg_lds_put(x, i0, bls::select(j == 0, with, without));
-            kzg_lds_put(x, i1, bls::select(j == 0, without, with));
-        }
-        __syncthreads();
-    }
+    kzg_fr_intt4096(x, t, tw);
     // 1 / 4096 in Montgomery form is 2^256 / 2^12 = 2^244, which is below r (a number of 255 bits) as it stands
     bls::Fr inv_width = bls::zero<bls::FrT>();
     inv_width.w[7] = 1u << 20;

@@ -7,14 +7,14 @@
 // (degree <= 64) and Z(X) = z(X^64): Z vanishes on the missing cells, E Z is known at all 8 192 points (zero where a cell is absent), and its
 // interpolant D = P Z has degree below 8 192. P = D / Z is taken on the coset s w^i, s = 7, where Z has no zero (s^8192 != 1) and takes only
 // 64 different values, z(s^64 w128^(2 u)), u = brp12(i') mod 64. No transform of 8 192 points is formed (it would not fit the LDS):
-//   k_kzg_recover_vanish    a wave per call: the <= 65 coefficients of z, then two transforms of 128 points in the way of
-//                           k_kzg_cell_toeplitz: z(w128^brp7(k)) = z(c_k) comes out at position k, the factor of cell k; on the coefficients
+//   k_kzg_recover_vanish    a wave per call: the <= 65 coefficients of z, then two transforms of 128 points (kzg_fr_ntt128,
+//                           kzg_open_kernels.cuh): z(w128^brp7(k)) = z(c_k) comes out at position k, the factor of cell k; on the coefficients
 //                           scaled by s^(64 m), z(s^64 w128^(2 u)) comes out at position brp6(u) < 64, inverted a lane each (Fermat)
 //   k_kzg_recover_halves    a workgroup per (blob, half h): positions 4096 h .. 4096 h + 4095 of E Z (range-checked while they are loaded),
-//                           k_kzg_blob_intt's twelve stages undone; half 0 is a = D mod (X^4096 - 1), half 1 after the unscaling by W^-i
+//                           the twelve stages undone (kzg_fr_intt4096); half 0 is a = D mod (X^4096 - 1), half 1 after the unscaling by W^-i
 //                           (= -W^(4096 - i): k_kzg_cell_wpow's table backwards, the sign changed) is b = D mod (X^4096 + 1)
-//   k_kzg_recover_quotient  a workgroup per blob: F = D mod (X^4096 - s^4096) = a (1 + s^4096) / 2 + b (1 - s^4096) / 2, scaled by s^i, twelve
-//                           stages forward (position i' then holds F(s w^brp12(i'))), times 1 / Z there — inverse number brp6(i' >> 6), 64
+//   k_kzg_recover_quotient  a workgroup per blob: F = D mod (X^4096 - s^4096) = a (1 + s^4096) / 2 + b (1 - s^4096) / 2, scaled by s^i, kzg_fr_ntt4096
+//                           (position i' then holds F(s w^brp12(i'))), times 1 / Z there — inverse number brp6(i' >> 6), 64
 //                           neighbours share one —, the twelve stages undone, unscaled by s^-i: the coefficients of P as rows of 32
 //                           little-endian bytes (KzgSrc form 0). No permutation pass anywhere.
 //   k_kzg_recover_check     after k_kzg_cells on those coefficients: every supplied cell against the recomputed one, byte for byte. Equal
@@ -52,37 +52,10 @@ static __device__ __forceinline__ bls::Fr kzg_recover_fold_b() {
     return bls::Fr{{0x3aec2d0du, 0x19af57dbu, 0x512dd8a4u, 0xcc6af47eu, 0x504bf99bu, 0xc6b94594u, 0x21d9b730u, 0x61ac311du}};
 }
 
-// base^e for e < 2^bits, by square-and-multiply with uniform control flow (Montgomery form)
-static __device__ __forceinline__ bls::Fr kzg_recover_pow(const bls::Fr& base, u32 e, int bits) {
-    bls::Fr pw = bls::one<bls::FrT>();
-#pragma unroll 1
-    for (int bit = bits - 1; bit >= 0; bit--) {
-        pw = bls::sqr(pw);
-        const bls::Fr with = bls::mul<bls::FrT>(pw, base);
-        pw = bls::select((e >> bit) & 1, with, pw);
-    }
-    return pw;
-}
 static __device__ __forceinline__ bls::Fr kzg_recover_sqr_n(bls::Fr v, int n) {  // v^(2^n)
 #pragma unroll 1
     for (int k = 0; k < n; k++) v = bls::sqr(v);
     return v;
-}
-
-// the seven stages of k_kzg_cell_toeplitz on 128 elements in LDS, lane l < 64 a butterfly: natural order in, position q = the value at
-// w128^brp7(q) out
-static __device__ __forceinline__ void kzg_recover_fft128(uint4* x, u32 l, const bls::Fr* __restrict__ tw) {
-#pragma unroll 1
-    for (u32 s = 0; s < 7; s++) {
-        const u32 half = 64u >> s;
-        const u32 j = l & (half - 1), i0 = ((l >> (6 - s)) << (7 - s)) | j, i1 = i0 + half;  // i1 <= 127
-        const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
-        kzg_lds_put(x, i0, bls::add(u, v));
-        bls::Fr d = bls::sub(u, v);
-        if (s < 6) d = bls::mul<bls::FrT>(d, tw[(j << s) * 32u]);  // w128^(j 2^s) = w^(32 j 2^s), index <= 32 * 63
-        kzg_lds_put(x, i1, d);
-        __syncthreads();
-    }
 }
 
 // grid 1, 64 lanes. zc: [128], zc[k] = z(c_k) — zero exactly on the missing cells; zinv: [64], zinv[u] = 1 / z(s^64 w128^(2 u)) (both in
@@ -114,23 +87,23 @@ static __device__ __forceinline__ void k_kzg_recover_vanish(const VB& vb, const 
     const bls::Fr hi = l == 0 && missing == 64 ? bls::one<bls::FrT>() : bls::zero<bls::FrT>();
     kzg_lds_put(x, 64 + l, hi);
     __syncthreads();
-    kzg_recover_fft128(x, l, tw);
+    kzg_fr_ntt128(x, l, tw);
     zc[l] = kzg_lds_get(x, l);  // position k: z(w128^brp7(k)) = z(c_k)
     zc[64 + l] = kzg_lds_get(x, 64 + l);
     __syncthreads();
     const bls::Fr s64 = kzg_recover_sqr_n(kzg_recover_s(), 6);
-    const bls::Fr pl = kzg_recover_pow(s64, l, 6);  // s^(64 l)
+    const bls::Fr pl = kzg_fr_pow(s64, l, 6);  // s^(64 l)
     kzg_lds_put(x, l, bls::mul<bls::FrT>(lo, pl));
     kzg_lds_put(x, 64 + l, bls::mul<bls::FrT>(hi, bls::mul<bls::FrT>(pl, kzg_recover_sqr_n(s64, 6))));  // s^(64 (64 + l))
     __syncthreads();
-    kzg_recover_fft128(x, l, tw);
+    kzg_fr_ntt128(x, l, tw);
     // position q < 64: z(s^64 w128^brp7(q)) and brp7(q) = 2 brp6(q). Never zero: s^64 w128^e is no 128th root of unity
     zinv[kzg_brp(l, 6)] = bls::fr_inv(kzg_lds_get(x, l));
 }
 
 // grid (n_blobs, 2), 512 lanes, KZG_NTT_LDS bytes of dynamic LDS. cells: [n_blobs][n_cells][2048] big-endian, any address, the cells of the
 // list in its order (slots.slot[k] < n_cells wherever it is not absent). Half h = vb.y: x[i] = E[4096 h + i] z(c_k), k = 64 h + (i >> 6), zero
-// for an absent cell; then the stages of k_kzg_blob_intt. ab: [n_blobs][2][4096] plain elements (32-byte aligned): 4096 a and 4096 b.
+// for an absent cell; then kzg_fr_intt4096. ab: [n_blobs][2][4096] plain elements (32-byte aligned): 4096 a and 4096 b.
 // status[2 blob + h]: 0, or 1 + the LOWEST 64 (position in the list) + element of a supplied element that is not below r (the values
 // written are then meaningless; the caller refuses the call)
 static __device__ __forceinline__ void k_kzg_recover_halves(const VB& vb, const KzgSlots& slots, const uint8_t* __restrict__ cells, u32 n_cells,
@@ -158,21 +131,7 @@ static __device__ __forceinline__ void k_kzg_recover_halves(const VB& vb, const 
     }
     __syncthreads();
     if (t == 0) status[2 * vb.x + h] = s_bad + 1u;
-#pragma unroll 1
-    for (u32 s = 12; s-- > 0;) {
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 b = t; b < 2048; b += KZG_NTT_THREADS) {
-            const u32 j = b & (half - 1), i0 = ((b >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0);
-            bls::Fr m = kzg_lds_get(x, i1);
-            if (s < 11) m = bls::mul<bls::FrT>(m, tw[(2048u - (j << s)) & 2047u]);  // (the first stage undone has no twiddle but 1)
-            const bls::Fr with = bls::add(u, m), without = bls::sub(u, m);
-            kzg_lds_put(x, i0, bls::select(j == 0, with, without));
-            kzg_lds_put(x, i1, bls::select(j == 0, without, with));
-        }
-        __syncthreads();
-    }
+    kzg_fr_intt4096(x, t, tw);
     // half 1 holds the coefficients of D(W X) mod (X^4096 - 1), b_i W^i: W^-i = W^(8192 - i) = -W^(4096 - i) for i >= 1 (W^4096 = -1)
     uint4* out = reinterpret_cast<uint4*>(ab + ((size_t)vb.x * 2 + h) * KZG_EVAL_BYTES);
 #pragma unroll 1
@@ -196,7 +155,7 @@ static __device__ __forceinline__ void k_kzg_recover_quotient(const VB& vb, cons
     const uint4* b = reinterpret_cast<const uint4*>(ab + ((size_t)vb.x * 2 + 1) * KZG_EVAL_BYTES);
     {
         const bls::Fr fa = kzg_recover_fold_a(), fb = kzg_recover_fold_b(), s = kzg_recover_s(), step = kzg_recover_sqr_n(s, 9);
-        bls::Fr sp = kzg_recover_pow(s, t, 9);
+        bls::Fr sp = kzg_fr_pow(s, t, 9);
 #pragma unroll 1
         for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {  // F_i s^i
             const bls::Fr f = bls::add(bls::mul<bls::FrT>(kzg_lds_get(a, i), fa), bls::mul<bls::FrT>(kzg_lds_get(b, i), fb));
@@ -205,42 +164,15 @@ static __device__ __forceinline__ void k_kzg_recover_quotient(const VB& vb, cons
         }
     }
     __syncthreads();
-#pragma unroll 1
-    for (u32 s = 0; s < 12; s++) {  // k_kzg_blob_ntt's stages: position i' <- F(s w^brp12(i'))
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 q = t; q < 2048; q += KZG_NTT_THREADS) {
-            const u32 j = q & (half - 1), i0 = ((q >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0), v = kzg_lds_get(x, i1);
-            kzg_lds_put(x, i0, bls::add(u, v));
-            bls::Fr d = bls::sub(u, v);
-            if (s < 11) d = bls::mul<bls::FrT>(d, tw[j << s]);  // (the last stage's only twiddle is 1)
-            kzg_lds_put(x, i1, d);
-        }
-        __syncthreads();
-    }
+    kzg_fr_ntt4096(x, t, tw);  // position i' <- F(s w^brp12(i'))
 #pragma unroll 1
     for (u32 i = t; i < 4096; i += KZG_NTT_THREADS)  // Z(s w^e) = z(s^64 w128^(2 (e mod 64))), and brp12(i') mod 64 = brp6(i' >> 6)
         kzg_lds_put(x, i, bls::mul<bls::FrT>(kzg_lds_get(x, i), zinv[kzg_brp(i >> 6, 6)]));
     __syncthreads();
-#pragma unroll 1
-    for (u32 s = 12; s-- > 0;) {  // k_kzg_blob_intt's
-        const u32 half = 2048u >> s;
-#pragma unroll 1
-        for (u32 q = t; q < 2048; q += KZG_NTT_THREADS) {
-            const u32 j = q & (half - 1), i0 = ((q >> (11 - s)) << (12 - s)) | j, i1 = i0 + half;  // i1 <= 4095
-            const bls::Fr u = kzg_lds_get(x, i0);
-            bls::Fr m = kzg_lds_get(x, i1);
-            if (s < 11) m = bls::mul<bls::FrT>(m, tw[(2048u - (j << s)) & 2047u]);
-            const bls::Fr with = bls::add(u, m), without = bls::sub(u, m);
-            kzg_lds_put(x, i0, bls::select(j == 0, with, without));
-            kzg_lds_put(x, i1, bls::select(j == 0, without, with));
-        }
-        __syncthreads();
-    }
+    kzg_fr_intt4096(x, t, tw);
     uint4* out = reinterpret_cast<uint4*>(coeffs + (size_t)vb.x * KZG_EVAL_BYTES);
     const bls::Fr s_inv = kzg_recover_s_inv(), step = kzg_recover_sqr_n(s_inv, 9);
-    bls::Fr sp = kzg_recover_pow(s_inv, t, 9);
+    bls::Fr sp = kzg_fr_pow(s_inv, t, 9);
 #pragma unroll 1
     for (u32 i = t; i < 4096; i += KZG_NTT_THREADS) {  // P_i s^i -> P_i
         kzg_lds_put(out, i, bls::mul<bls::FrT>(kzg_lds_get(x, i), sp));

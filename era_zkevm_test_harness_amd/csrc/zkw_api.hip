@@ -1520,7 +1520,7 @@ extern "C" int zkw_ram_witness_get(const zkw_ram_witness* w, int what, void* dst
     if (dst_bytes < bytes) return fail(ZKW_ERR_INVALID, "zkw_ram_witness_get: need %zu bytes, got %zu", bytes, dst_bytes);
     zkw_ctx* ctx = w->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(dst, src, bytes));
     return ctx->sync_if_host();
 }
 
@@ -1585,7 +1585,7 @@ extern "C" int zkw_trace_get(const zkw_trace* t, size_t slot, uint32_t first_col
     zkw_ctx* ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const u64* src = t->data + slot * t->slot_elems() + (size_t)first_col * t->n_rows;
-    HIP_TRY(ctx->copy_async(dst, src, (size_t)n_cols * t->n_rows * sizeof(u64), ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(dst, src, (size_t)n_cols * t->n_rows * sizeof(u64)));
     return ctx->sync_if_host();
 }
 

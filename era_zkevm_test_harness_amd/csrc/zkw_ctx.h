@@ -4,7 +4,7 @@
 // units (zkw_block.hip, zkw_comm.hip, zkw_recursion.hip, zkw_vm_trace.hip) are written against include/zkw.h and zkw_internal.h.
 // Kernels live in the *.cuh headers with internal linkage: a unit includes the ones it launches. A launch is ONE statement that opens its
 // profiling span, launches and checks the launch: ZKW_LAUNCH* for a kernel body (zkw_launch.h), launch_direct for a raw __global__ kernel
-// on the context's stream; launch_check by hand only behind a launch on another stream (docs/KERNELS.md 3.29).
+// on the context's stream. A launch beside the context's stream is the same statement with on_side(ctx, side) in front (docs/KERNELS.md 3.29).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -259,6 +259,11 @@ struct zkw_ctx {
         HIP_TRY(copy_async(dst, dev, count * sizeof(T), hipMemcpyDeviceToHost));
         return ZKW_OK;
     }
+    // a result kept in device scratch (so that a refused call writes nothing of the caller's) to the caller's pointer, in either pointer mode
+    int copy_out(void* dst, const void* dev, size_t bytes) {
+        HIP_TRY(copy_async(dst, dev, bytes, ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        return ZKW_OK;
+    }
     int sync_if_host() {
         if (ptr_mode == ZKW_PTR_HOST) HIP_TRY(sync_stream());
         return ZKW_OK;
@@ -317,25 +322,42 @@ static inline int launch_check(const char* what) {
 // The first argument of every launch form: the context, and the profiling span the launch opens. A plain `ctx` is the usual case — a span
 // of weight 1 under the kernel's name; span_as(ctx, name, weight) names or weighs it differently (one kernel timed under two names, a
 // merged launch that counts as two); no_span(ctx) opens none (the inner launches of radix_sort and of the prefix scans, which run under
-// the caller's Prof).
+// the caller's Prof). on_side(ctx, side) launches on `side`, a stream forked off the context's (zkw_ctx::side_fork), not on ctx->stream:
+// it opens no span (a span's events are recorded on ctx->stream) and is not for a context of a batch (which has one stream) — go() refuses
+// a side-stream launch that is either.
 struct LaunchAt {
     zkw_ctx* ctx;
     const char* span;  // nullptr: the kernel's name
     unsigned weight;   // 0: no span
+    hipStream_t stream = nullptr;  // nullptr: ctx->stream
     LaunchAt(zkw_ctx* c, const char* s = nullptr, unsigned w = 1) : ctx(c), span(s), weight(w) {}
 };
 static inline LaunchAt span_as(zkw_ctx* ctx, const char* name, unsigned weight = 1) { return LaunchAt(ctx, name, weight); }
 static inline LaunchAt no_span(zkw_ctx* ctx) { return LaunchAt(ctx, nullptr, 0); }
+static inline LaunchAt on_side(zkw_ctx* ctx, hipStream_t side) {
+    LaunchAt at(ctx, nullptr, 0);
+    at.stream = side;
+    return at;
+}
+// side_fork, and *at from then on launches beside the context's stream (until the caller's side_join)
+static inline int side_fork_at(zkw_ctx* ctx, LaunchAt* at) {
+    hipStream_t side = nullptr;
+    ZKW_TRY(ctx->side_fork(&side));
+    *at = on_side(ctx, side);
+    return ZKW_OK;
+}
 
-// Launch of a kernel BODY (zkw_launch.h) with a grid of gx x gy workgroups of BS threads: on the context's stream, or — a context of a
-// batch — left with the batch to travel with the other blocks' launches of the same kernel. Arguments convert to the body's parameter types.
-// `name` serves the span, the error message and the batch descriptor. An empty grid launches nothing but still records its span.
+// Launch of a kernel BODY (zkw_launch.h) with a grid of gx x gy workgroups of BS threads: on the context's stream (or the side stream `at`
+// names), or — a context of a batch — left with the batch to travel with the other blocks' launches of the same kernel. Arguments convert
+// to the body's parameter types. `name` serves the span, the error message and the batch descriptor. An empty grid launches nothing but
+// still records its span.
 template <auto Body, int BS>
 struct Launcher {
     using S = LaunchSig<decltype(Body)>;
     template <class... A>
     static int go(const LaunchAt& at, const char* name, dim3 grid, size_t lds_bytes, const A&... a) {
         zkw_ctx* ctx = at.ctx;
+        if (at.stream && (at.weight || ctx->batched())) return fail(ZKW_ERR_INVALID, "launch of %s beside the context's stream: not with a span, not on a context of a batch", name);
         Prof _p(ctx, at.span ? at.span : name, at.weight);
         if (grid.x == 0 || grid.y == 0 || grid.z == 0) return ZKW_OK;
         if (ctx->batched()) {
@@ -344,7 +366,7 @@ struct Launcher {
             zkw_batch_launch(ctx->batch, S::template desc<Body, BS>(name), grid, lds_bytes, &t);
             return ZKW_OK;
         }
-        S::template single<Body, BS>(ctx->stream, grid, lds_bytes, a...);
+        S::template single<Body, BS>(at.stream ? at.stream : ctx->stream, grid, lds_bytes, a...);
         return launch_check(name);
     }
     // more than the default 64 KB of dynamic LDS for both launch forms of the kernel (once per device is enough; cheap to repeat)
@@ -355,7 +377,7 @@ struct Launcher {
     }
 };
 // One statement per launch: span, launch and error check; it returns the error from the calling function. `at` is ctx, span_as(ctx, ...)
-// or no_span(ctx).
+// no_span(ctx) or on_side(ctx, side).
 #define ZKW_LAUNCH(at, kernel, gx, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, #kernel, dim3((unsigned)(gx)), 0, __VA_ARGS__)))
 #define ZKW_LAUNCH_2D(at, kernel, gx, gy, bs, ...) ZKW_TRY((Launcher<&kernel, bs>::go(at, #kernel, dim3((unsigned)(gx), (unsigned)(gy)), 0, __VA_ARGS__)))
 // the same for a template kernel (the name has commas): ZKW_LAUNCH_T(ctx, (k_foo<A, B>), "k_foo", ...)
@@ -477,7 +499,7 @@ static int witness_get(const W* w, int what, void* dst, size_t dst_bytes, const 
     if (bytes == 0) return ZKW_OK;
     zkw_ctx* ctx = w->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->copy_async(dst, src, bytes, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(dst, src, bytes));
     return ctx->sync_if_host();
 }
 template <class W>

@@ -8,6 +8,8 @@
 // zkw_eip4844_cell_proofs, and the way back from any half of the cells, zkw_kzg_recover_cells_blobs (the reference has no counterpart).
 // Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh,
 // kzg_recover_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
+// What the calls share is written once, ahead of them: the handles' owner logic (KzgHandle), the blob limit, the 128 KiB of dynamic LDS of
+// the five transform kernels, and the twiddles.
 #include "zkw_ctx.h"
 #include "kzg_kernels.cuh"
 #include "kzg_open_kernels.cuh"
@@ -29,10 +31,38 @@ static_assert(sizeof(zkw_eip4844_proof_record) == KZG_PRF_BYTES && offsetof(zkw_
               "kzg_open_kernels.cuh writes zkw_eip4844_proof_record by byte offset");
 static_assert(sizeof(bls::G1Aff) == 96 && sizeof(bls::G1Jac) == 144, "table entries are 96 bytes, bucket sums 144");
 
-struct zkw_kzg_settings {
+// What the three handles (zkw_kzg_settings, zkw_kzg_verifier, zkw_kzg_cell_settings) share: one table in device memory, read by any context of
+// the device, and the context it was built on, which the handle keeps alive. *_create validates, makes the handle (kzg_handle_new), runs its
+// own kernels and on a failure drops it (kzg_handle_drop); *_free is witness_free (zkw_ctx.h: set device, sync, release, release the context).
+template <class T> struct KzgHandle {
     zkw_ctx* ctx = nullptr;
-    size_t n = 0, bytes = 0;
-    bls::G1Aff* table = nullptr;  // [32][n]: table[w * n + k] = 2^(8 w) S[k]
+    size_t bytes = 0;
+    T* table = nullptr;
+    void release() { dev_free(table); }
+};
+template <class H> static int kzg_handle_drop(H* h, int rc) {
+    (void)h->ctx->sync_stream();  // nothing queued may still write the table
+    if (h->table) dev_free(h->table);
+    delete h;
+    return rc;
+}
+// a handle of ctx with `bytes` of table (and `slack` bytes behind it); on an error nothing is left, and the caller words the refusal
+template <class H> static hipError_t kzg_handle_new(zkw_ctx* ctx, size_t bytes, size_t slack, H** out) {
+    H* h = new H();
+    h->ctx = ctx;
+    h->bytes = bytes;
+    const hipError_t e = dev_malloc(&h->table, bytes + slack);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)kzg_handle_drop(h, 0);
+        h = nullptr;
+    }
+    *out = h;
+    return e;
+}
+
+struct zkw_kzg_settings : KzgHandle<bls::G1Aff> {  // table: [32][n], table[w * n + k] = 2^(8 w) S[k]
+    size_t n = 0;
 };
 
 static const char* kzg_reason(u32 status) {
@@ -55,21 +85,12 @@ extern "C" int zkw_kzg_settings_create(zkw_ctx* ctx, const uint8_t* g1_monomial,
     ZKW_TRY(ctx->in("kzg_in_points", g1_monomial, n_points * 48, &d_in));
     u32* d_status = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("kzg_status", n_points, &d_status));
-    zkw_kzg_settings* s = new zkw_kzg_settings();
-    s->ctx = ctx;
+    zkw_kzg_settings* s = nullptr;
+    const size_t bytes = (size_t)KZG_WINDOWS * n_points * sizeof(bls::G1Aff);
+    const hipError_t e = kzg_handle_new(ctx, bytes, 64, &s);
+    if (e != hipSuccess) return fail(ZKW_ERR_OOM, "zkw_kzg_settings_create: %zu points need %zu bytes of device memory: %s", n_points, bytes, hipGetErrorString(e));
     s->n = n_points;
-    s->bytes = (size_t)KZG_WINDOWS * n_points * sizeof(bls::G1Aff);
-    auto drop = [&](int rc) {
-        (void)ctx->sync_stream();  // nothing queued may still write the table
-        if (s->table) dev_free(s->table);
-        delete s;
-        return rc;
-    };
-    const hipError_t e = dev_malloc(&s->table, s->bytes + 64);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return drop(fail(ZKW_ERR_OOM, "zkw_kzg_settings_create: %zu points need %zu bytes of device memory: %s", n_points, s->bytes, hipGetErrorString(e)));
-    }
+    auto drop = [&](int rc) { return kzg_handle_drop(s, rc); };
     std::vector<u32> status(n_points);
     int rc = [&]() -> int {
         ZKW_LAUNCH(ctx, k_kzg_decompress, blocks_for(n_points, 64), 64, d_in, (u32)n_points, s->table, d_status);
@@ -89,15 +110,7 @@ extern "C" int zkw_kzg_settings_create(zkw_ctx* ctx, const uint8_t* g1_monomial,
     return ZKW_OK;
 }
 
-extern "C" void zkw_kzg_settings_free(zkw_kzg_settings* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->ctx->device);
-    (void)s->ctx->sync_stream();
-    dev_free(s->table);
-    zkw_ctx* owner = s->ctx;
-    delete s;
-    ctx_release(owner);
-}
+extern "C" void zkw_kzg_settings_free(zkw_kzg_settings* s) { witness_free(s); }
 extern "C" size_t zkw_kzg_settings_num_points(const zkw_kzg_settings* s) { return s ? s->n : 0; }
 extern "C" size_t zkw_kzg_settings_bytes(const zkw_kzg_settings* s) { return s ? s->bytes : 0; }
 
@@ -115,6 +128,41 @@ static int kzg_commit_device(const zkw_kzg_settings* s, zkw_ctx* ctx, KzgSrc src
 static int kzg_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
     if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
     if (n > 65535) return fail(ZKW_ERR_INVALID, "%s: at most 65535 polynomials per call, not %zu", who, n);
+    return ZKW_OK;
+}
+
+// a call takes at most 32 767 blobs: zkw_eip4844_prove makes two polynomials of each, and 65 535 are a grid's rows
+enum : size_t { KZG_MAX_BLOBS = 32767 };
+static int kzg_blob_limit(const char* who, size_t n) {
+    if (n > KZG_MAX_BLOBS) return fail(ZKW_ERR_INVALID, "%s: at most 32767 blobs per call, not %zu", who, n);
+    return ZKW_OK;
+}
+
+// 128 KiB of dynamic LDS, more than the default 64, for the five kernels that keep 4 096 elements of Fr there: once per device, and the
+// first call that needs one of them pays for all five
+static int kzg_allow_ntt_lds(zkw_ctx* ctx) {
+    static bool attr_set[16] = {};
+    if (attr_set[ctx->device & 15]) return ZKW_OK;
+    ZKW_TRY((Launcher<&k_kzg_blob_ntt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+    ZKW_TRY((Launcher<&k_kzg_blob_intt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+    ZKW_TRY((Launcher<&k_kzg_cells, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+    ZKW_TRY((Launcher<&k_kzg_recover_halves, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+    ZKW_TRY((Launcher<&k_kzg_recover_quotient, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
+    attr_set[ctx->device & 15] = true;
+    return ZKW_OK;
+}
+
+// w^j (j < 2048) and, with d_wpow, W^k (k < 4096) into context scratch, launched at `at` (the context's stream or beside it)
+static int kzg_twiddles_device(const LaunchAt& at, const bls::Fr** d_tw, const bls::Fr** d_wpow = nullptr) {
+    bls::Fr *tw = nullptr, *wpow = nullptr;
+    ZKW_TRY(at.ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &tw));
+    ZKW_LAUNCH(at, k_kzg_twiddles, 8, 256, tw);
+    *d_tw = tw;
+    if (d_wpow) {
+        ZKW_TRY(at.ctx->scratch_t<bls::Fr>("kzg_cell_wpow", 4096, &wpow));
+        ZKW_LAUNCH(at, k_kzg_cell_wpow, 16, 256, wpow);
+        *d_wpow = wpow;
+    }
     return ZKW_OK;
 }
 
@@ -157,14 +205,9 @@ extern "C" int zkw_eip4844_witness(const zkw_kzg_settings* s, zkw_ctx* ctx, cons
     // the blob's sponge depends on nothing the commitment writes: beside it on a stream of the pool, joined ahead of z. (A context of a
     // batch has one stream; under zkw_profile the kernels run one after another so that every span times its own kernel.)
     const bool beside = !ctx->batched() && !ctx->profiling;
-    if (beside) {
-        hipStream_t side = nullptr;
-        ZKW_TRY(ctx->side_fork(&side));
-        Launcher<&k_kzg_linear_hash, 64>::S::template single<&k_kzg_linear_hash, 64>(side, dim3((unsigned)n_blobs), 0, d_b, rec + KZG_REC_LINEAR, (u32)KZG_REC_BYTES);
-        ZKW_TRY(launch_check("k_kzg_linear_hash"));
-    } else {
-        ZKW_LAUNCH(ctx, k_kzg_linear_hash, n_blobs, 64, d_b, rec + KZG_REC_LINEAR, (u32)KZG_REC_BYTES);
-    }
+    LaunchAt at = ctx;
+    if (beside) ZKW_TRY(side_fork_at(ctx, &at));
+    ZKW_LAUNCH(at, k_kzg_linear_hash, n_blobs, 64, d_b, rec + KZG_REC_LINEAR, (u32)KZG_REC_BYTES);
     ZKW_TRY(kzg_commit_device(s, ctx, KzgSrc{d_b, (u32)KZG_BLOB_ELEMENTS, 1}, (u32)KZG_BLOB_BYTES, n_blobs, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES));
     if (beside) ZKW_TRY(ctx->side_join());
     ZKW_LAUNCH(ctx, k_kzg_tail, n_blobs, KZG_TAIL_THREADS, d_b, rec);
@@ -206,24 +249,15 @@ extern "C" int zkw_kzg_open(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8
     return ctx->sync_if_host();
 }
 
-template <auto Body, int BS, class... A> static int kzg_launch_on(hipStream_t st, const char* name, unsigned blocks, size_t lds, const A&... a) {
-    Launcher<Body, BS>::S::template single<Body, BS>(st, dim3(blocks), lds, a...);
-    return launch_check(name);
-}
-
 extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* blobs, size_t n_blobs, const zkw_eip4844_record* records,
                                  zkw_eip4844_proof_record* out, uint8_t* blob_evaluations) {
     if (!s || !ctx || (n_blobs && (!blobs || !records || !out))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: null argument");
     if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: a blob has 4096 elements, the settings hold %zu points", s->n);
-    if (n_blobs > 32767) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: at most 32767 blobs per call (two polynomials each), not %zu", n_blobs);
+    if (n_blobs > KZG_MAX_BLOBS) return fail(ZKW_ERR_INVALID, "zkw_eip4844_prove: at most 32767 blobs per call (two polynomials each), not %zu", n_blobs);
     ZKW_TRY(kzg_check_call("zkw_eip4844_prove", s, ctx, 2 * n_blobs));
     if (n_blobs == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    static bool attr_set[16] = {};
-    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
-        ZKW_TRY((Launcher<&k_kzg_blob_ntt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
-        attr_set[ctx->device & 15] = true;
-    }
+    ZKW_TRY(kzg_allow_ntt_lds(ctx));
     const uint8_t* d_b = nullptr;
     ZKW_TRY(ctx->in("kzg_in_blobs", blobs, n_blobs * KZG_BLOB_BYTES, &d_b));
     const zkw_eip4844_record* d_rec = nullptr;
@@ -234,8 +268,7 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
     uint8_t *prf = reinterpret_cast<uint8_t*>(d_out), *d_ev = nullptr, *d_rows = nullptr, *d_proofs = nullptr;
     if (blob_evaluations) ZKW_TRY(ctx->out("kzg_evals", blob_evaluations, n_blobs * KZG_EVAL_BYTES, &d_ev));
     else ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_evals", n_blobs * KZG_EVAL_BYTES, &d_ev));  // the challenge hashes it either way
-    bls::Fr* d_tw = nullptr;
-    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
+    const bls::Fr* d_tw = nullptr;
     // blob j's two quotients side by side: rows 2 j (at the record's z) and 2 j + 1 (at the challenge), so are their proofs
     constexpr u32 ROWS = (KZG_BLOB_ELEMENTS - 1) * 32;
     ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_quotient_rows", 2 * n_blobs * ROWS, &d_rows));
@@ -245,18 +278,11 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
     // the evaluation form and its sponge depend on nothing the opening at z writes: beside it on a stream of the pool, joined ahead of the
     // opening at the challenge. (A context of a batch has one stream; under zkw_profile every span times its own kernel.)
     const bool beside = !ctx->batched() && !ctx->profiling;
-    if (beside) {
-        hipStream_t side = nullptr;
-        ZKW_TRY(ctx->side_fork(&side));
-        ZKW_TRY((kzg_launch_on<&k_kzg_twiddles, 256>(side, "k_kzg_twiddles", 8, 0, d_tw)));
-        ZKW_TRY((kzg_launch_on<&k_kzg_blob_ntt, KZG_NTT_THREADS>(side, "k_kzg_blob_ntt", nb, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev)));
-        ZKW_TRY((kzg_launch_on<&k_kzg_blob_challenge, 64>(side, "k_kzg_blob_challenge", nb, 0, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES,
-                                                               prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES)));
-    } else {
-        ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
-        ZKW_LAUNCH_D(ctx, k_kzg_blob_ntt, "k_kzg_blob_ntt", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, d_b, (const bls::Fr*)d_tw, d_ev);
-        ZKW_LAUNCH(ctx, k_kzg_blob_challenge, nb, 64, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES, prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES);
-    }
+    LaunchAt at = ctx;
+    if (beside) ZKW_TRY(side_fork_at(ctx, &at));
+    ZKW_TRY(kzg_twiddles_device(at, &d_tw));
+    ZKW_LAUNCH_D(at, k_kzg_blob_ntt, "k_kzg_blob_ntt", dim3(nb), KZG_NTT_THREADS, KZG_NTT_LDS, d_b, d_tw, d_ev);
+    ZKW_LAUNCH(at, k_kzg_blob_challenge, nb, 64, (const uint8_t*)d_ev, rec + KZG_REC_COMMITMENT, (u32)KZG_REC_BYTES, prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES);
     ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, rec + KZG_REC_Z, (u32)KZG_REC_BYTES, (u32)KZG_Z_BE16, d_rows, 2 * ROWS, (uint8_t*)nullptr, 0u, 0u);
     if (beside) ZKW_TRY(ctx->side_join());
     ZKW_LAUNCH(ctx, k_kzg_quotient, nb, KZG_QUO_THREADS, blob_src, (u32)KZG_BLOB_BYTES, (const uint8_t*)prf + KZG_PRF_CHALLENGE, (u32)KZG_PRF_BYTES, (u32)KZG_Z_BE32, d_rows + ROWS, 2 * ROWS, prf + KZG_PRF_VALUE, (u32)KZG_PRF_BYTES, 1u);
@@ -270,7 +296,7 @@ extern "C" int zkw_eip4844_prove(const zkw_kzg_settings* s, zkw_ctx* ctx, const 
 // ---- the producers from a blob in evaluation form: back to the coefficients in Fr, then the kernels above as they are ------------------
 static int kzg_blobs_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
     if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "%s: a blob has 4096 elements, the settings hold %zu points", who, s->n);
-    if (n > 32767) return fail(ZKW_ERR_INVALID, "%s: at most 32767 blobs per call, not %zu", who, n);
+    ZKW_TRY(kzg_blob_limit(who, n));
     return kzg_check_call(who, s, ctx, n);
 }
 
@@ -278,20 +304,15 @@ static int kzg_blobs_check_call(const char* who, const zkw_kzg_settings* s, zkw_
 // d_points, the n flags of the points. The coefficients ([n][4096][32], zkw_kzg_commit's form) are left in context scratch, so that a
 // refused call has written nothing of the caller's
 static int kzg_blob_coefficients_device(const char* who, zkw_ctx* ctx, const uint8_t* d_ev, const uint8_t* d_points, size_t n, const uint8_t** d_coeffs) {
-    static bool attr_set[16] = {};
-    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
-        ZKW_TRY((Launcher<&k_kzg_blob_intt, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
-        attr_set[ctx->device & 15] = true;
-    }
-    bls::Fr* d_tw = nullptr;
+    ZKW_TRY(kzg_allow_ntt_lds(ctx));
+    const bls::Fr* d_tw = nullptr;
     uint8_t* d_c = nullptr;
     u32* d_st = nullptr;
     const size_t words = d_points ? 2 * n : n;
-    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
     ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_blob_coeffs", n * KZG_EVAL_BYTES, &d_c));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_intt_status", words, &d_st));
-    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
-    ZKW_LAUNCH_D(ctx, k_kzg_blob_intt, "k_kzg_blob_intt", dim3((unsigned)n), KZG_NTT_THREADS, KZG_NTT_LDS, d_ev, (const bls::Fr*)d_tw, d_c, d_points, (u32)n, d_st);
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw));
+    ZKW_LAUNCH_D(ctx, k_kzg_blob_intt, "k_kzg_blob_intt", dim3((unsigned)n), KZG_NTT_THREADS, KZG_NTT_LDS, d_ev, d_tw, d_c, d_points, (u32)n, d_st);
     std::vector<u32> st(words);
     ZKW_TRY(ctx->read_small(st.data(), d_st, words * sizeof(u32)));
     for (size_t j = 0; j < n; j++)
@@ -304,13 +325,13 @@ static int kzg_blob_coefficients_device(const char* who, zkw_ctx* ctx, const uin
 
 extern "C" int zkw_kzg_blob_coefficients(zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* coeffs) {
     if (!ctx || (n && (!blob_evaluations || !coeffs))) return fail(ZKW_ERR_INVALID, "zkw_kzg_blob_coefficients: null argument");
-    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_kzg_blob_coefficients: at most 32767 blobs per call, not %zu", n);
+    ZKW_TRY(kzg_blob_limit("zkw_kzg_blob_coefficients", n));
     if (n == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const uint8_t *d_ev = nullptr, *d_c = nullptr;
     ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
     ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_blob_coefficients", ctx, d_ev, nullptr, n, &d_c));
-    HIP_TRY(ctx->copy_async(coeffs, d_c, n * KZG_EVAL_BYTES, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(coeffs, d_c, n * KZG_EVAL_BYTES));
     return ctx->sync_if_host();
 }
 
@@ -373,13 +394,9 @@ extern "C" int zkw_eip4844_prove_blobs(const zkw_kzg_settings* s, zkw_ctx* ctx, 
     // the sponge depends on nothing the transform writes: beside it on a stream of the pool, joined ahead of the quotient. (A context of a
     // batch has one stream; under zkw_profile every span times its own kernel.)
     const bool beside = !ctx->batched() && !ctx->profiling;
-    if (beside) {
-        hipStream_t side = nullptr;
-        ZKW_TRY(ctx->side_fork(&side));
-        ZKW_TRY((kzg_launch_on<&k_kzg_blob_challenge, 64>(side, "k_kzg_blob_challenge", (unsigned)n, 0, d_ev, d_cm, 48u, d_open, 64u)));
-    } else {
-        ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, d_cm, 48u, d_open, 64u);
-    }
+    LaunchAt at = ctx;
+    if (beside) ZKW_TRY(side_fork_at(ctx, &at));
+    ZKW_LAUNCH(at, k_kzg_blob_challenge, n, 64, d_ev, d_cm, 48u, d_open, 64u);
     const int rc = kzg_blob_coefficients_device("zkw_eip4844_prove_blobs", ctx, d_ev, nullptr, n, &d_c);
     if (beside) ZKW_TRY(ctx->side_join());  // (after a refusal too: the sponge of this call is not left to run into the next one's scratch)
     if (rc != ZKW_OK) return rc;
@@ -387,27 +404,21 @@ extern "C" int zkw_eip4844_prove_blobs(const zkw_kzg_settings* s, zkw_ctx* ctx, 
     ZKW_TRY(ctx->out("kzg_out", proofs, n * 48, &d_proofs));
     ZKW_TRY(kzg_open_coefficients_device(s, ctx, d_c, d_open, 64u, n, d_proofs, d_open + 32, 64u));
     ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * 48));
-    if (openings) HIP_TRY(ctx->copy_async(openings, d_open, n * 64, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (openings) ZKW_TRY(ctx->copy_out(openings, d_open, n * 64));
     return ctx->sync_if_host();
 }
 
 // ---- the check: a verifier is the prepared lines of -G2 and [tau] G2; a call is two kernels and reads nothing back ----------------------
 static_assert(sizeof(bls::G2Line) == 192, "a line is two elements of Fq2");
 
-struct zkw_kzg_verifier {
-    zkw_ctx* ctx = nullptr;
-    size_t bytes = 0;
-    bls::G2Line* lines = nullptr;  // [2][68]: -G2, [tau] G2
-};
+struct zkw_kzg_verifier : KzgHandle<bls::G2Line> {};  // table: the lines [2][68] of -G2 and [tau] G2
 
 static const char* kzg_g2_reason(u32 status) {
     switch (status) {
-        case bls::G1_NOT_COMPRESSED: return "bit 7 of its first byte is clear (not a compressed point)";
-        case bls::G1_BAD_INFINITY: return "the infinity flag is set with other bits";
         case bls::G1_X_TOO_LARGE: return "a coordinate of x is not below p";
         case bls::G1_NOT_ON_CURVE: return "x has no y on y^2 = x^3 + 4 (1 + u)";
         case KZG_G2_INFINITY: return "it is the point at infinity";
-        default: return "the point is outside the order-r subgroup";
+        default: return kzg_reason(status);  // the flags and the subgroup: G1's words
     }
 }
 
@@ -420,23 +431,14 @@ extern "C" int zkw_kzg_verifier_create(zkw_ctx* ctx, const uint8_t* tau_g2, zkw_
     ZKW_TRY(ctx->in("kzg_in_points", tau_g2, 96, &d_in));
     u32* d_status = nullptr;
     ZKW_TRY(ctx->scratch_t<u32>("kzg_status", 2, &d_status));
-    zkw_kzg_verifier* v = new zkw_kzg_verifier();
-    v->ctx = ctx;
-    v->bytes = 2 * (size_t)bls::G2_LINES * sizeof(bls::G2Line);
-    auto drop = [&](int rc) {
-        (void)ctx->sync_stream();  // nothing queued may still write the lines
-        if (v->lines) dev_free(v->lines);
-        delete v;
-        return rc;
-    };
-    const hipError_t e = dev_malloc(&v->lines, v->bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return drop(fail(ZKW_ERR_OOM, "zkw_kzg_verifier_create: %zu bytes of device memory: %s", v->bytes, hipGetErrorString(e)));
-    }
+    zkw_kzg_verifier* v = nullptr;
+    const size_t bytes = 2 * (size_t)bls::G2_LINES * sizeof(bls::G2Line);
+    const hipError_t e = kzg_handle_new(ctx, bytes, 0, &v);
+    if (e != hipSuccess) return fail(ZKW_ERR_OOM, "zkw_kzg_verifier_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
+    auto drop = [&](int rc) { return kzg_handle_drop(v, rc); };
     u32 status[2] = {0, 0};
     const int rc = [&]() -> int {
-        ZKW_LAUNCH(ctx, k_kzg_g2_prepare, 1, 64, d_in, v->lines, d_status);
+        ZKW_LAUNCH(ctx, k_kzg_g2_prepare, 1, 64, d_in, v->table, d_status);
         return ctx->read_small(status, d_status, sizeof status);  // (synchronises: other contexts read the lines without any ordering with this stream)
     }();
     if (rc != ZKW_OK) return drop(rc);
@@ -447,15 +449,7 @@ extern "C" int zkw_kzg_verifier_create(zkw_ctx* ctx, const uint8_t* tau_g2, zkw_
     return ZKW_OK;
 }
 
-extern "C" void zkw_kzg_verifier_free(zkw_kzg_verifier* v) {
-    if (!v) return;
-    (void)hipSetDevice(v->ctx->device);
-    (void)v->ctx->sync_stream();
-    dev_free(v->lines);
-    zkw_ctx* owner = v->ctx;
-    delete v;
-    ctx_release(owner);
-}
+extern "C" void zkw_kzg_verifier_free(zkw_kzg_verifier* v) { witness_free(v); }
 extern "C" size_t zkw_kzg_verifier_bytes(const zkw_kzg_verifier* v) { return v ? v->bytes : 0; }
 
 // the two kernels over n >= 1 claims; d_verdicts: n bytes on the device
@@ -465,7 +459,7 @@ static int kzg_verify_device(const zkw_kzg_verifier* v, zkw_ctx* ctx, const KzgC
     ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_verify_points", 2 * n, &d_pts));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_verify_status", n, &d_status));
     ZKW_LAUNCH(ctx, k_kzg_verify_points, blocks_for(n, 64), 64, claims, (u32)n, d_pts, d_status);
-    ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v->lines, (u32)n, d_verdicts);
+    ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v->table, (u32)n, d_verdicts);
     return ZKW_OK;
 }
 
@@ -514,34 +508,33 @@ extern "C" int zkw_eip4844_verify(const zkw_kzg_verifier* v, zkw_ctx* ctx, const
 // ---- the check from the blob itself: challenge and value are recomputed, nothing the prover wrote down is taken on trust ----------------
 extern "C" int zkw_kzg_evaluate_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* points, size_t n, uint8_t* values) {
     if (!ctx || (n && (!blob_evaluations || !points || !values))) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: null argument");
-    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: at most 32767 blobs per call, not %zu", n);
+    ZKW_TRY(kzg_blob_limit("zkw_kzg_evaluate_blobs", n));
     if (n == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const uint8_t *d_ev = nullptr, *d_z = nullptr;
     ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
     ZKW_TRY(ctx->in("kzg_in_points", points, n * 32, &d_z));
-    bls::Fr* d_tw = nullptr;
+    const bls::Fr* d_tw = nullptr;
     uint8_t* d_y = nullptr;  // (scratch in both pointer modes: a refused call leaves `values` untouched)
     u32* d_st = nullptr;
-    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
     ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_eval_values", n * 32, &d_y));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
-    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
-    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, d_z, 32u, (const bls::Fr*)d_tw, d_y, 32u, d_st);
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw));
+    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, d_z, 32u, d_tw, d_y, 32u, d_st);
     std::vector<u32> st(n);
     ZKW_TRY(ctx->read_small(st.data(), d_st, n * sizeof(u32)));
     for (size_t j = 0; j < n; j++) {
         if (st[j] == KZG_EVAL_BAD_POINT) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: the point of blob %zu is not below r", j);
         if (st[j] != KZG_EVAL_OK) return fail(ZKW_ERR_INVALID, "zkw_kzg_evaluate_blobs: element %u of blob %zu is not below r", (unsigned)(st[j] - 1), j);
     }
-    HIP_TRY(ctx->copy_async(values, d_y, n * 32, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(values, d_y, n * 32));
     return ctx->sync_if_host();
 }
 
 extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx, const uint8_t* blob_evaluations, const uint8_t* commitments,
                                         const uint8_t* proofs, size_t n, uint8_t* verdicts, uint8_t* openings) {
     if (!v || !ctx || (n && (!blob_evaluations || !commitments || !proofs || !verdicts))) return fail(ZKW_ERR_INVALID, "zkw_eip4844_verify_blobs: null argument");
-    if (n > 32767) return fail(ZKW_ERR_INVALID, "zkw_eip4844_verify_blobs: at most 32767 blobs per call, not %zu", n);
+    ZKW_TRY(kzg_blob_limit("zkw_eip4844_verify_blobs", n));
     ZKW_TRY(kzg_verify_check_call("zkw_eip4844_verify_blobs", v, ctx, n));
     if (n == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -554,14 +547,13 @@ extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx,
     ZKW_TRY(ctx->out("kzg_verdicts", verdicts, n, &d_verdicts));
     if (openings) ZKW_TRY(ctx->out("kzg_openings", openings, n * 64, &d_open));
     else ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_openings", n * 64, &d_open));  // the check reads them either way
-    bls::Fr* d_tw = nullptr;
+    const bls::Fr* d_tw = nullptr;
     u32* d_st = nullptr;
-    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &d_tw));
     ZKW_TRY(ctx->scratch_t<u32>("kzg_eval_status", n, &d_st));
     // one after another on the context's stream: the evaluation needs the challenge, the points kernel needs both
-    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, d_tw);
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw));
     ZKW_LAUNCH(ctx, k_kzg_blob_challenge, n, 64, d_ev, cl.commitments, 48u, d_open, 64u);
-    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, (const uint8_t*)d_open, 64u, (const bls::Fr*)d_tw, d_open + 32, 64u, d_st);
+    ZKW_LAUNCH(ctx, k_kzg_blob_eval, n, KZG_EVAL_THREADS, d_ev, (const uint8_t*)d_open, 64u, d_tw, d_open + 32, 64u, d_st);
     cl.points = d_open;
     cl.values = d_open + 32;
     cl.pre = d_st;
@@ -574,11 +566,7 @@ extern "C" int zkw_eip4844_verify_blobs(const zkw_kzg_verifier* v, zkw_ctx* ctx,
 // ---- EIP-7594: the 128 cells of a blob and their proofs (kzg_cell_kernels.cuh) ----------------------------------------------------------
 static_assert(KZG_CELL_POINTS == 64 * KZG_CELLS && KZG_CELLS_BYTES == 2 * KZG_EVAL_BYTES, "64 offsets of 128 points; the extended blob is two blobs long");
 
-struct zkw_kzg_cell_settings {
-    zkw_ctx* ctx = nullptr;
-    size_t bytes = 0;
-    bls::G1Aff* table = nullptr;  // [32][8192]: table[w * 8192 + j * 64 + i] = 2^(8 w) X_i[j], X_i = G1_FFT_128(x_i)
-};
+struct zkw_kzg_cell_settings : KzgHandle<bls::G1Aff> {};  // table: [32][8192], table[w * 8192 + j * 64 + i] = 2^(8 w) X_i[j], X_i = G1_FFT_128(x_i)
 
 // n_ffts transforms of 2^log_n Jacobian points each on the context's stream (d_in == d_out is fine)
 static int kzg_g1_fft_device(zkw_ctx* ctx, const bls::G1Jac* d_in, bls::G1Jac* d_out, u32 log_n, size_t n_ffts, bool inverse, bool scale, bool upper_inf) {
@@ -598,20 +586,10 @@ extern "C" int zkw_kzg_cell_settings_create(const zkw_kzg_settings* s, zkw_ctx* 
     *out = nullptr;
     bls::G1Jac* d_x = nullptr;
     ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_setup", KZG_CELL_POINTS, &d_x));
-    zkw_kzg_cell_settings* cs = new zkw_kzg_cell_settings();
-    cs->ctx = ctx;
-    cs->bytes = (size_t)KZG_WINDOWS * KZG_CELL_POINTS * sizeof(bls::G1Aff);
-    auto drop = [&](int rc) {
-        (void)ctx->sync_stream();  // nothing queued may still write the table
-        if (cs->table) dev_free(cs->table);
-        delete cs;
-        return rc;
-    };
-    const hipError_t e = dev_malloc(&cs->table, cs->bytes + 64);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return drop(fail(ZKW_ERR_OOM, "zkw_kzg_cell_settings_create: %zu bytes of device memory: %s", cs->bytes, hipGetErrorString(e)));
-    }
+    zkw_kzg_cell_settings* cs = nullptr;
+    const size_t bytes = (size_t)KZG_WINDOWS * KZG_CELL_POINTS * sizeof(bls::G1Aff);
+    const hipError_t e = kzg_handle_new(ctx, bytes, 64, &cs);
+    if (e != hipSuccess) return fail(ZKW_ERR_OOM, "zkw_kzg_cell_settings_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
     const int rc = [&]() -> int {
         ZKW_LAUNCH(ctx, k_kzg_cell_setup_x, blocks_for(KZG_CELL_POINTS, 64), 64, (const bls::G1Aff*)s->table, d_x);
         ZKW_TRY(kzg_g1_fft_device(ctx, d_x, d_x, 7, 64, false, false, false));
@@ -620,21 +598,13 @@ extern "C" int zkw_kzg_cell_settings_create(const zkw_kzg_settings* s, zkw_ctx* 
         HIP_TRY(ctx->sync_stream());  // other contexts read the table without any ordering with this stream
         return ZKW_OK;
     }();
-    if (rc != ZKW_OK) return drop(rc);
+    if (rc != ZKW_OK) return kzg_handle_drop(cs, rc);
     ctx_retain(ctx);
     *out = cs;
     return ZKW_OK;
 }
 
-extern "C" void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings* cs) {
-    if (!cs) return;
-    (void)hipSetDevice(cs->ctx->device);
-    (void)cs->ctx->sync_stream();
-    dev_free(cs->table);
-    zkw_ctx* owner = cs->ctx;
-    delete cs;
-    ctx_release(owner);
-}
+extern "C" void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings* cs) { witness_free(cs); }
 extern "C" size_t zkw_kzg_cell_settings_bytes(const zkw_kzg_cell_settings* cs) { return cs ? cs->bytes : 0; }
 
 extern "C" int zkw_kzg_g1_fft(zkw_ctx* ctx, const uint8_t* points, size_t n, size_t n_ffts, int inverse, uint8_t* out) {
@@ -668,27 +638,9 @@ extern "C" int zkw_kzg_g1_fft(zkw_ctx* ctx, const uint8_t* points, size_t n, siz
     return ctx->sync_if_host();
 }
 
-// w^j (j < 2048) and W^k (k < 4096) into context scratch on the context's stream
-static int kzg_cell_twiddles_device(zkw_ctx* ctx, const bls::Fr** d_tw, const bls::Fr** d_wpow) {
-    bls::Fr *tw = nullptr, *wpow = nullptr;
-    ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_twiddles", 2048, &tw));
-    ZKW_LAUNCH(ctx, k_kzg_twiddles, 8, 256, tw);
-    *d_tw = tw;
-    if (d_wpow) {
-        ZKW_TRY(ctx->scratch_t<bls::Fr>("kzg_cell_wpow", 4096, &wpow));
-        ZKW_LAUNCH(ctx, k_kzg_cell_wpow, 16, 256, wpow);
-        *d_wpow = wpow;
-    }
-    return ZKW_OK;
-}
-
 // the cells of n >= 1 polynomials read through src; d_evals: their evaluation forms, when the caller has them (cells 0..63 are a copy)
 static int kzg_cells_device(zkw_ctx* ctx, KzgSrc src, u32 poly_stride, const uint8_t* d_evals, const bls::Fr* d_tw, const bls::Fr* d_wpow, size_t n, uint8_t* d_cells) {
-    static bool attr_set[16] = {};
-    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
-        ZKW_TRY((Launcher<&k_kzg_cells, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
-        attr_set[ctx->device & 15] = true;
-    }
+    ZKW_TRY(kzg_allow_ntt_lds(ctx));
     ZKW_LAUNCH_D(ctx, k_kzg_cells, "k_kzg_cells", dim3((unsigned)n, 2), KZG_NTT_THREADS, KZG_NTT_LDS, src, poly_stride, d_evals, d_tw, d_wpow, d_cells);
     return ZKW_OK;
 }
@@ -712,8 +664,7 @@ static int kzg_cell_proofs_device(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx,
 
 static int kzg_cells_check_call(const char* who, const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, size_t n) {
     if (cs && ctx->device != cs->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, cs->ctx->device, ctx->device);
-    if (n > 32767) return fail(ZKW_ERR_INVALID, "%s: at most 32767 blobs per call, not %zu", who, n);
-    return ZKW_OK;
+    return kzg_blob_limit(who, n);
 }
 
 extern "C" int zkw_kzg_cells_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations, size_t n, uint8_t* cells) {
@@ -725,7 +676,7 @@ extern "C" int zkw_kzg_cells_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations
     ZKW_TRY(ctx->in("kzg_in_evals", blob_evaluations, n * KZG_EVAL_BYTES, &d_ev));
     ZKW_TRY(kzg_blob_coefficients_device("zkw_kzg_cells_blobs", ctx, d_ev, nullptr, n, &d_c));
     const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
-    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, &d_wpow));
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw, &d_wpow));
     uint8_t* d_cells = nullptr;
     ZKW_TRY(ctx->out("kzg_cells", cells, n * KZG_CELLS_BYTES, &d_cells));
     ZKW_TRY(kzg_cells_device(ctx, KzgSrc{d_c, (u32)KZG_BLOB_ELEMENTS, 0}, (u32)KZG_EVAL_BYTES, d_ev, d_tw, d_wpow, n, d_cells));
@@ -736,7 +687,7 @@ extern "C" int zkw_kzg_cells_blobs(zkw_ctx* ctx, const uint8_t* blob_evaluations
 // the routine both proof calls share: it starts at the coefficients (src), on the device
 static int kzg_cells_and_proofs(const zkw_kzg_cell_settings* cs, zkw_ctx* ctx, KzgSrc src, u32 poly_stride, const uint8_t* d_evals, size_t n, uint8_t* cells, uint8_t* proofs) {
     const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
-    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, cells ? &d_wpow : nullptr));
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw, cells ? &d_wpow : nullptr));
     uint8_t *d_cells = nullptr, *d_proofs = nullptr;
     if (cells) {
         ZKW_TRY(ctx->out("kzg_cells", cells, n * KZG_CELLS_BYTES, &d_cells));
@@ -791,16 +742,11 @@ extern "C" int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings* cs, zkw_
     ZKW_TRY(kzg_cells_check_call(who, cs, ctx, n));
     if (n == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    static bool attr_set[16] = {};
-    if (!attr_set[ctx->device & 15]) {  // 128 KiB of dynamic LDS: more than the default 64
-        ZKW_TRY((Launcher<&k_kzg_recover_halves, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
-        ZKW_TRY((Launcher<&k_kzg_recover_quotient, KZG_NTT_THREADS>::allow_dynamic_lds(KZG_NTT_LDS)));
-        attr_set[ctx->device & 15] = true;
-    }
+    ZKW_TRY(kzg_allow_ntt_lds(ctx));
     const uint8_t* d_in = nullptr;
     ZKW_TRY(ctx->in("kzg_in_cells", cells, n * n_cells * KZG_CELL_BYTES, &d_in));
     const bls::Fr *d_tw = nullptr, *d_wpow = nullptr;
-    ZKW_TRY(kzg_cell_twiddles_device(ctx, &d_tw, &d_wpow));
+    ZKW_TRY(kzg_twiddles_device(ctx, &d_tw, &d_wpow));
     bls::Fr* d_z = nullptr;  // z(c_k), k < 128, then the 64 inverses of Z on the coset
     uint8_t *d_ab = nullptr, *d_c = nullptr, *d_full = nullptr;
     u32* d_st = nullptr;  // [n][2] range words, then [n] consistency words
@@ -827,7 +773,7 @@ extern "C" int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings* cs, zkw_
     }
     for (size_t j = 0; j < n; j++)
         if (st[2 * n + j]) return fail(ZKW_ERR_INVALID, "%s: the %zu cells of blob %zu do not lie on one polynomial of degree below 4096", who, n_cells, j);
-    HIP_TRY(ctx->copy_async(recovered, d_full, n * KZG_CELLS_BYTES, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    ZKW_TRY(ctx->copy_out(recovered, d_full, n * KZG_CELLS_BYTES));
     if (proofs) {
         uint8_t* d_proofs = nullptr;
         ZKW_TRY(ctx->out("kzg_out", proofs, n * KZG_CELLS * 48, &d_proofs));

@@ -1069,16 +1069,14 @@ int nlcf_begin(zkw_ctx* ctx, int circuit_type, const typename T::Inst* d_inst, s
     ZKW_TRY(ctx->upload(jobs_name, jobs, &call->d_jobs));
     call->n = jobs.size();
     if (jobs.empty()) return ZKW_OK;
-    if (ctx->batched() || on_main_stream) {  // a context of a batch has one stream: the sponges of all the group's blocks travel as one launch, behind the fills
-                                             // (on_main_stream: the caller's own fork is open — ECRecover's EC section)
-        ZKW_LAUNCH_D(no_span(ctx), (k_nlcf_sponges<T>), "k_nlcf_sponges", dim3((unsigned)jobs.size()), 256, 0, *d, d_inst, (const NlcfJob*)call->d_jobs, S->g, n_rows, (u64)nlcf_first_row(circuit_type, S, cycles));
-        return ZKW_OK;
+    LaunchAt at = no_span(ctx);
+    if (!(ctx->batched() || on_main_stream)) {  // a context of a batch has one stream: the sponges of all the group's blocks travel as one launch, behind the fills
+                                                // (on_main_stream: the caller's own fork is open — ECRecover's EC section)
+        ZKW_TRY(side_fork_at(ctx, &at));
+        call->forked = true;
     }
-    hipStream_t side = nullptr;
-    ZKW_TRY(ctx->side_fork(&side));
-    call->forked = true;
-    Launcher<&k_nlcf_sponges<T>, 256>::S::template single<&k_nlcf_sponges<T>, 256>(side, dim3((unsigned)jobs.size()), 0, *d, d_inst, call->d_jobs, S->g, n_rows, (u64)nlcf_first_row(circuit_type, S, cycles));
-    return launch_check("k_nlcf_sponges");
+    ZKW_LAUNCH_D(at, (k_nlcf_sponges<T>), "k_nlcf_sponges", dim3((unsigned)jobs.size()), 256, 0, *d, d_inst, (const NlcfJob*)call->d_jobs, S->g, n_rows, (u64)nlcf_first_row(circuit_type, S, cycles));
+    return ZKW_OK;
 }
 int nlcf_end(zkw_ctx* ctx, int circuit_type, const NlcfCall& call, u32 cycles, size_t n_rows) {
     if (call.n == 0) return ZKW_OK;
