@@ -1249,38 +1249,126 @@ std::vector<NlInstance> nl_instances(size_t first_instance, size_t n_instances, 
     }
     return v;
 }
-}  // namespace
-
-// ZkSyncBaseLayerCircuit::synthesis for Keccak256RoundFunction (type 5): 86 + 3 x 14 columns, Xor8 / And8 / ByteSplit<1..4>
-extern "C" int zkw_keccak_round_synthesize(zkw_ctx* ctx, zkw_precompile_witness* w, size_t first_instance, size_t n_instances,
-                                           zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_keccak_round_synthesize: bad argument");
-    if (w->kind != ZKW_PRECOMPILE_KECCAK256) return fail(ZKW_ERR_INVALID, "zkw_keccak_round_synthesize: not a keccak256 witness");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
+// ---- what the synthesis entries of the six netlist circuits share: the argument refusals, the bracket around the engine, the check entry
+int nl_refuse_range(size_t first_instance, size_t n_instances, size_t n_all) {
+    if (first_instance + n_instances > n_all) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
+    return ZKW_OK;
+}
+int nl_refuse_trace(const char* circuit, int cols, size_t n_instances, const zkw_trace* t) {
     if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (t->n_cols < KC_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the Keccak256RoundFunction circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, KC_COLS);
+    if (t->n_cols < (size_t)cols) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the %s circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, circuit, cols);
+    return ZKW_OK;
+}
+// the refusals a witness-taking entry starts with (`wrong_kind`: what the entry takes, "a keccak256", when the witness is of another kind). The return
+// of an empty call and hipSetDevice stay with the entry: StorageApplication and ECRecover have one more refusal before them
+template <class W>
+int nl_refuse(const char* entry, const char* circuit, int cols, zkw_ctx* ctx, const W* w, const char* wrong_kind, size_t first_instance, size_t n_instances, const zkw_trace* t) {
+    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "%s: bad argument", entry);
+    if (wrong_kind) return fail(ZKW_ERR_INVALID, "%s: not %s witness", entry, wrong_kind);
+    ZKW_TRY(nl_refuse_range(first_instance, n_instances, w->n_instances));
+    return nl_refuse_trace(circuit, cols, n_instances, t);
+}
+
+// the bracket around the engine: `netlist` calls nl_synthesize[_with] with the after-fill hook (the closed-form sponges fork there, next to the
+// fills) and the claims it is handed; `queues` launches the queue section; the ties come last, and the slots' tags are committed after them
+template <class T, class Netlist, class Queues>
+int nl_sections(zkw_ctx* ctx, int circuit_type, const typename T::Inst* d_inst, size_t first_index, const std::vector<NlInstance>& inst, u32 cycles, size_t n_rows,
+                Netlist&& netlist, Queues&& queues) {
+    NlcfCall cf;
+    SlotClaims claims;
+    ZKW_TRY(netlist([&] { return nlcf_begin<T>(ctx, circuit_type, d_inst, first_index, inst, cycles, n_rows, &cf); }, &claims));
+    ZKW_TRY(queues());
+    return claims.commit_if(nlcf_end(ctx, circuit_type, cf, cycles, n_rows));
+}
+
+// the two queues of the precompile-style circuits: the requests are popped (the head runs through the states their pushes left), the memory queries pushed
+NlqQueues nl_pop_push_queues(const void* requests, const u64* request_tails, u64 n_requests, const void* mem_q, const u64* mem_tails, u64 n_mem, const zkw_queue_state12& mem_in, const RoundOps* round_ops) {
+    NlqQueues Q{};
+    Q.q[0] = NlqQueueIn{requests, request_tails, {0}, n_requests};
+    Q.q[1] = NlqQueueIn{mem_q, mem_tails, {0}, n_mem};
+    memcpy(Q.q[1].init, mem_in.tail, sizeof mem_in.tail);
+    Q.round_ops = round_ops;
+    return Q;
+}
+NlqQueues precompile_queues(const zkw_precompile_witness* w) { return nl_pop_push_queues(w->requests, w->req_tails, w->n_requests, w->mem_q, w->mem_tails, w->n_queries, w->mem_in, w->round_ops); }
+
+// the three circuits whose cycles are the rounds of the witness's records (types 5, 6, 3): what differs between them
+struct PrecompileRound {
+    using W = zkw_precompile_witness;
+    static bool any(const W* w) { return w->n_requests != 0; }
+    static int public_inputs(zkw_ctx* ctx, W* w) { return zkw_precompile_closed_forms(ctx, w, nullptr, nullptr); }  // of the block's instances (a20), once
+    static NlqQueues queues(const W* w) { return precompile_queues(w); }
+};
+struct KcRound : PrecompileRound {  // Keccak256RoundFunction: 86 + 3 x 14 columns, Xor8 / And8 / ByteSplit<1..4>
+    using Cf = CfPrecompile<ZKW_PRECOMPILE_KECCAK256>;
+    static constexpr int TYPE = 5, COLS = KC_COLS;
+    static constexpr bool SHA_LIKE = false;
+    static constexpr const char *ENTRY = "zkw_keccak_round_synthesize", *CIRCUIT = "Keccak256RoundFunction";
+    static const char* wrong_kind(const W* w) { return w->kind != ZKW_PRECOMPILE_KECCAK256 ? "a keccak256" : nullptr; }
+    static const void* rounds(const W* w) { return w->keccak_rounds; }
+};
+struct ScRound : PrecompileRound {  // Sha256RoundFunction: 116 + 4 x 9 columns, TriXor4 / Ch4 / Maj4 / Split4BitChunk<1, 2>
+    using Cf = CfPrecompile<ZKW_PRECOMPILE_SHA256>;
+    static constexpr int TYPE = 6, COLS = SC_COLS;
+    static constexpr bool SHA_LIKE = true;
+    static constexpr const char *ENTRY = "zkw_sha256_round_synthesize", *CIRCUIT = "Sha256RoundFunction";
+    static const char* wrong_kind(const W* w) { return w->kind != ZKW_PRECOMPILE_SHA256 ? "a sha256" : nullptr; }
+    static const void* rounds(const W* w) { return w->sha256_rounds; }
+};
+struct DcRound {  // CodeDecommitter: the SHA-256 netlist on 108 + 4 x 11 columns, one cycle per round of the unpacked bytecodes (BeginNew shares the cycle of a bytecode's first round)
+    using W = zkw_decommitter_witness;
+    using Cf = CfDecommitter;
+    static constexpr int TYPE = 3, COLS = DC_COLS;
+    static constexpr bool SHA_LIKE = true;
+    static constexpr const char *ENTRY = "zkw_code_decommitter_synthesize", *CIRCUIT = "CodeDecommitter";
+    static const char* wrong_kind(const W*) { return nullptr; }  // (one kind of witness)
+    static bool any(const W*) { return true; }
+    static int public_inputs(zkw_ctx* ctx, W* w) { return w->cf_pi ? ZKW_OK : closed_form_public_inputs<CfDecommitter>(ctx, w->instances, w->n_instances, &w->cf_pi); }
+    static const void* rounds(const W* w) { return w->sha256_rounds; }
+    static NlqQueues queues(const W* w) {  // the decommit requests are popped, the code words written to memory
+        return nl_pop_push_queues(w->requests, w->dedup_tails, w->n_requests, w->mem_q, w->mem_tails, w->total_words, w->mem_in, w->round_ops);
+    }
+};
+// ZkSyncBaseLayerCircuit::synthesis for the circuit C
+template <class C>
+int nl_round_synthesize(zkw_ctx* ctx, typename C::W* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
+    ZKW_TRY(nl_refuse(C::ENTRY, C::CIRCUIT, C::COLS, ctx, w, w ? C::wrong_kind(w) : nullptr, first_instance, n_instances, t));
     if (n_instances == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    ZKW_TRY(zkw_precompile_closed_forms(ctx, w, nullptr, nullptr));  // public inputs of the block's instances (a20), once
-    const std::vector<NlInstance> inst = nl_instances(first_instance, n_instances, w->capacity, w->n_requests != 0, w->total_rounds, w->cf_pi, w->n_instances, t, first_slot);
-    NlcfCall cf;  // the closed-form section: sponges next to the fills, the ties after them
-    SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize(ctx, 5, false, w->keccak_rounds, inst, w->capacity, t->n_rows, [&] {
-        return nlcf_begin<CfPrecompile<ZKW_PRECOMPILE_KECCAK256>>(ctx, 5, w->instances, first_instance, inst, w->capacity, t->n_rows, &cf);
-    }, &claims));
-    NlqQueues Q{};  // the precompile calls are popped, the memory queries (unaligned reads, the digest write) pushed
-    Q.q[0] = NlqQueueIn{w->requests, w->req_tails, {0}, w->n_requests};
-    Q.q[1] = NlqQueueIn{w->mem_q, w->mem_tails, {0}, w->n_queries};
-    memcpy(Q.q[1].init, w->mem_in.tail, sizeof w->mem_in.tail);
-    Q.round_ops = w->round_ops;
-    ZKW_TRY(nlq_synthesize(ctx, 5, Q, inst, w->capacity, t->n_rows));
-    return claims.commit_if(nlcf_end(ctx, 5, cf, w->capacity, t->n_rows));
+    ZKW_TRY(C::public_inputs(ctx, w));
+    const std::vector<NlInstance> inst = nl_instances(first_instance, n_instances, w->capacity, C::any(w), w->total_rounds, w->cf_pi, w->n_instances, t, first_slot);
+    return nl_sections<typename C::Cf>(ctx, C::TYPE, w->instances, first_instance, inst, w->capacity, t->n_rows,
+        [&](const NlAfterFill& after_fill, SlotClaims* claims) { return nl_synthesize(ctx, C::TYPE, C::SHA_LIKE, C::rounds(w), inst, w->capacity, t->n_rows, after_fill, claims); },
+        [&] { return nlq_synthesize(ctx, C::TYPE, C::queues(w), inst, w->capacity, t->n_rows); });
 }
-extern "C" int zkw_keccak_round_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_keccak_round_check_satisfied: bad argument");
-    return nl_check(ctx, 5, t, slot, capacity, n_violations, first_bad);
+
+// check_if_satisfied of a netlist circuit's slot; `cycles`: what the entry's capacity is in cycles
+int nl_check_entry(const char* name, int circuit_type, u32 cycles, zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
+    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0) return fail(ZKW_ERR_INVALID, "%s: bad argument", name);
+    return nl_check(ctx, circuit_type, t, slot, cycles, n_violations, first_bad);
 }
+}  // namespace
+
+extern "C" int zkw_keccak_round_synthesize(zkw_ctx* ctx, zkw_precompile_witness* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
+    return nl_round_synthesize<KcRound>(ctx, w, first_instance, n_instances, t, first_slot);
+}
+extern "C" int zkw_sha256_round_synthesize(zkw_ctx* ctx, zkw_precompile_witness* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
+    return nl_round_synthesize<ScRound>(ctx, w, first_instance, n_instances, t, first_slot);
+}
+extern "C" int zkw_code_decommitter_synthesize(zkw_ctx* ctx, zkw_decommitter_witness* w, size_t first_instance, size_t n_instances, zkw_trace* t, size_t first_slot) {
+    return nl_round_synthesize<DcRound>(ctx, w, first_instance, n_instances, t, first_slot);
+}
+#define NL_CHECK_ENTRY(stem, type, cycles)                                                                                                                            \
+    extern "C" int zkw_##stem##_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) { \
+        return nl_check_entry("zkw_" #stem "_check_satisfied", type, cycles, ctx, t, slot, capacity, n_violations, first_bad);                                      \
+    }
+NL_CHECK_ENTRY(code_decommitter, 3, capacity)
+NL_CHECK_ENTRY(keccak_round, 5, capacity)
+NL_CHECK_ENTRY(sha256_round, 6, capacity)
+NL_CHECK_ENTRY(ecrecover, 7, capacity)
+NL_CHECK_ENTRY(storage_application, 10, capacity * SA_CYCLES_PER_WALK)
+NL_CHECK_ENTRY(linear_hasher, 13, ZKW_LINEAR_HASHER_CYCLES(capacity))
+#undef NL_CHECK_ENTRY
 
 // ZkSyncBaseLayerCircuit::synthesis for ECRecover (type 7): 80 + 3 x 16 columns, Xor8 / And8 / 8 x 32 FixedBaseMul / ByteSplit<1..4> =
 // 197 632 table rows (base_layer/ecrecover.rs:30-41,138-176). One cycle per request (ecrecover.rs:143-178: four reads, two writes):
@@ -1298,11 +1386,10 @@ static int ecrecover_synthesize_many(zkw_ctx* ctx, zkw_precompile_witness* const
         zkw_precompile_witness* w = ws[k];
         if (!w || w->kind != ZKW_PRECOMPILE_ECRECOVER) return fail(ZKW_ERR_INVALID, "zkw_ecrecover_synthesize: not an ecrecover witness");
         if (w->ctx->device != ctx->device || w->capacity != capacity) return fail(ZKW_ERR_INVALID, "zkw_ecrecover_synthesize: witnesses of another device or capacity");
-        if (first[k] + count[k] > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
+        ZKW_TRY(nl_refuse_range(first[k], count[k], w->n_instances));
         total += count[k];
     }
-    if (total > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", total, t->n_slots);
-    if (t->n_cols < EK_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the ECRecover circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, EK_COLS);
+    ZKW_TRY(nl_refuse_trace("ECRecover", EK_COLS, total, t));
     if (total == 0) return ZKW_OK;
     if (ec_used_rows(capacity) > n_rows) return fail(ZKW_ERR_INVALID, "capacity %u needs %zu rows, trace has %zu", capacity, ec_used_rows(capacity), n_rows);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1379,13 +1466,8 @@ static int ecrecover_synthesize_many(zkw_ctx* ctx, zkw_precompile_witness* const
     for (size_t k = 0; k < n_ws; k++) {  // the queue sections: per witness (its request and memory queues)
         if (start_of[k + 1] == start_of[k]) continue;
         zkw_precompile_witness* w = ws[k];
-        NlqQueues Q{};
-        Q.q[0] = NlqQueueIn{w->requests, w->req_tails, {0}, w->n_requests};
-        Q.q[1] = NlqQueueIn{w->mem_q, w->mem_tails, {0}, w->n_queries};
-        memcpy(Q.q[1].init, w->mem_in.tail, sizeof w->mem_in.tail);
-        Q.round_ops = w->round_ops;
         const std::vector<NlInstance> sub(inst.begin() + start_of[k], inst.begin() + start_of[k + 1]);
-        ZKW_TRY(nlq_synthesize(ctx, 7, Q, sub, capacity, n_rows));
+        ZKW_TRY(nlq_synthesize(ctx, 7, precompile_queues(w), sub, capacity, n_rows));
         NlcfCall cf;  // the closed-form section (a 34-word FSM: eight dependent permutations) on the main stream: the side stream is the EC section's
         char name[32];
         snprintf(name, sizeof name, "nlcf_jobs_%zu", k % 64);
@@ -1417,74 +1499,6 @@ extern "C" int zkw_ecrecover_synthesize_multi(zkw_ctx* ctx, zkw_precompile_witne
     }
     return ecrecover_synthesize_many(ctx, witnesses, first.data(), count.data(), n_witnesses, t, first_slot);
 }
-extern "C" int zkw_ecrecover_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_ecrecover_check_satisfied: bad argument");
-    return nl_check(ctx, 7, t, slot, capacity, n_violations, first_bad);
-}
-
-// ZkSyncBaseLayerCircuit::synthesis for Sha256RoundFunction (type 6): 116 + 4 x 9 columns, TriXor4 / Ch4 / Maj4 / Split4BitChunk<1, 2>
-extern "C" int zkw_sha256_round_synthesize(zkw_ctx* ctx, zkw_precompile_witness* w, size_t first_instance, size_t n_instances,
-                                           zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_sha256_round_synthesize: bad argument");
-    if (w->kind != ZKW_PRECOMPILE_SHA256) return fail(ZKW_ERR_INVALID, "zkw_sha256_round_synthesize: not a sha256 witness");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (t->n_cols < SC_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the Sha256RoundFunction circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, SC_COLS);
-    if (n_instances == 0) return ZKW_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ZKW_TRY(zkw_precompile_closed_forms(ctx, w, nullptr, nullptr));
-    const std::vector<NlInstance> inst = nl_instances(first_instance, n_instances, w->capacity, w->n_requests != 0, w->total_rounds, w->cf_pi, w->n_instances, t, first_slot);
-    NlcfCall cf;
-    SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize(ctx, 6, true, w->sha256_rounds, inst, w->capacity, t->n_rows, [&] {
-        return nlcf_begin<CfPrecompile<ZKW_PRECOMPILE_SHA256>>(ctx, 6, w->instances, first_instance, inst, w->capacity, t->n_rows, &cf);
-    }, &claims));
-    NlqQueues Q{};  // the precompile calls are popped (the head runs through the states their pushes left), the memory queries pushed
-    Q.q[0] = NlqQueueIn{w->requests, w->req_tails, {0}, w->n_requests};
-    Q.q[1] = NlqQueueIn{w->mem_q, w->mem_tails, {0}, w->n_queries};
-    memcpy(Q.q[1].init, w->mem_in.tail, sizeof w->mem_in.tail);
-    Q.round_ops = w->round_ops;
-    ZKW_TRY(nlq_synthesize(ctx, 6, Q, inst, w->capacity, t->n_rows));
-    return claims.commit_if(nlcf_end(ctx, 6, cf, w->capacity, t->n_rows));
-}
-extern "C" int zkw_sha256_round_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_sha256_round_check_satisfied: bad argument");
-    return nl_check(ctx, 6, t, slot, capacity, n_violations, first_bad);
-}
-
-// ------------------------------------------------------------------------------------------------ CodeDecommitter synthesis
-// ZkSyncBaseLayerCircuit::synthesis for CodeDecommitter (type 3): the SHA-256 netlist on 108 + 4 x 11 columns, one cycle per round
-// of the unpacked bytecodes (a cycle is one round: BeginNew shares the cycle of a bytecode's first round)
-extern "C" int zkw_code_decommitter_synthesize(zkw_ctx* ctx, zkw_decommitter_witness* w, size_t first_instance, size_t n_instances,
-                                               zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_code_decommitter_synthesize: bad argument");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (t->n_cols < DC_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the CodeDecommitter circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, DC_COLS);
-    if (n_instances == 0) return ZKW_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!w->cf_pi) ZKW_TRY(closed_form_public_inputs<CfDecommitter>(ctx, w->instances, w->n_instances, &w->cf_pi));
-    const std::vector<NlInstance> inst = nl_instances(first_instance, n_instances, w->capacity, true, w->total_rounds, w->cf_pi, w->n_instances, t, first_slot);
-    NlcfCall cf;
-    SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize(ctx, 3, true, w->sha256_rounds, inst, w->capacity, t->n_rows, [&] {
-        return nlcf_begin<CfDecommitter>(ctx, 3, w->instances, first_instance, inst, w->capacity, t->n_rows, &cf);
-    }, &claims));
-    NlqQueues Q{};  // the decommit requests are popped, the code words written to memory
-    Q.q[0] = NlqQueueIn{w->requests, w->dedup_tails, {0}, w->n_requests};
-    Q.q[1] = NlqQueueIn{w->mem_q, w->mem_tails, {0}, w->total_words};
-    memcpy(Q.q[1].init, w->mem_in.tail, sizeof w->mem_in.tail);
-    Q.round_ops = w->round_ops;
-    ZKW_TRY(nlq_synthesize(ctx, 3, Q, inst, w->capacity, t->n_rows));
-    return claims.commit_if(nlcf_end(ctx, 3, cf, w->capacity, t->n_rows));
-}
-extern "C" int zkw_code_decommitter_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_code_decommitter_check_satisfied: bad argument");
-    return nl_check(ctx, 3, t, slot, capacity, n_violations, first_bad);
-}
 
 // ------------------------------------------------------------------------------------------------ StorageApplication synthesis
 // ZkSyncBaseLayerCircuit::synthesis for StorageApplication (type 10): the Merkle walks of the instance's tree queries as Blake2s
@@ -1492,10 +1506,7 @@ extern "C" int zkw_code_decommitter_check_satisfied(zkw_ctx* ctx, const zkw_trac
 // cycles (leaf hash + 256 levels); capacity = cycles_per_storage_application walks (a read is one walk, a write two).
 extern "C" int zkw_storage_application_synthesize(zkw_ctx* ctx, zkw_storage_application_witness* w, size_t first_instance, size_t n_instances,
                                                   zkw_trace* t, size_t first_slot) {
-    if (!ctx || !w || !t || w->ctx != ctx || t->ctx->device != ctx->device) return fail(ZKW_ERR_INVALID, "zkw_storage_application_synthesize: bad argument");
-    if (first_instance + n_instances > w->n_instances) return fail(ZKW_ERR_INVALID, "instance range out of bounds");
-    if (n_instances > t->n_slots) return fail(ZKW_ERR_INVALID, "more instances (%zu) than trace slots (%zu)", n_instances, t->n_slots);
-    if (t->n_cols < SA_COLS) return fail(ZKW_ERR_INVALID, "trace has %zu columns, the StorageApplication circuit needs %d (zkw_trace_create_with_columns)", t->n_cols, SA_COLS);
+    ZKW_TRY(nl_refuse("zkw_storage_application_synthesize", "StorageApplication", SA_COLS, ctx, w, nullptr, first_instance, n_instances, t));
     if (w->capacity > SAP_WALK_MAX) return fail(ZKW_ERR_INVALID, "capacity %u: at most %u walks per instance", w->capacity, SAP_WALK_MAX);
     if (n_instances == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1505,10 +1516,8 @@ extern "C" int zkw_storage_application_synthesize(zkw_ctx* ctx, zkw_storage_appl
     std::vector<NlInstance> inst(n_instances);
     for (size_t k = 0; k < n_instances; k++)
         inst[k] = NlInstance{rec[k].first_item, (u32)rec[k].num_items, w->cf_pi + COMPACT_FORM_LEN * w->n_instances + 4 * (first_instance + k), t, (first_slot + k) % t->n_slots, true};
-    const u32 capacity = w->capacity;
-    NlcfCall cf;
-    SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize_with(ctx, 10, [&](std::vector<NlPrepJob>& prep) -> int {
+    const u32 capacity = w->capacity, cycles = capacity * SA_CYCLES_PER_WALK;
+    const NlPrepare walks = [&](std::vector<NlPrepJob>& prep) -> int {
         std::vector<SapWalkJob> jobs(prep.size());
         for (size_t k = 0; k < prep.size(); k++)
             jobs[k] = SapWalkJob{w->items, w->keys, w->paths, w->walk_hashes, w->n ? prep[k].first_round : 0, w->n ? prep[k].n_active : 0, prep[k].hdr_bits, prep[k].free_elems, prep[k].state_before,
@@ -1518,15 +1527,10 @@ extern "C" int zkw_storage_application_synthesize(zkw_ctx* ctx, zkw_storage_appl
         ZKW_TRY(ctx->upload("sap_walk_jobs", jobs, &d_jobs));
         ZKW_LAUNCH_2D(ctx, k_sap_walk_cycles, (capacity * SAP_WALK_CYCLES + 256) / 256, (unsigned)jobs.size(), 256, d_jobs, capacity);
         return ZKW_OK;
-    }, inst, capacity * SA_CYCLES_PER_WALK, t->n_rows, [&] {
-        return nlcf_begin<CfStorageApplication>(ctx, 10, w->instances, first_instance, inst, capacity * SA_CYCLES_PER_WALK, t->n_rows, &cf);
-    }, &claims));
-    return claims.commit_if(nlcf_end(ctx, 10, cf, capacity * SA_CYCLES_PER_WALK, t->n_rows));
-}
-extern "C" int zkw_storage_application_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_storage_application_check_satisfied: bad argument");
-    return nl_check(ctx, 10, t, slot, capacity * SA_CYCLES_PER_WALK, n_violations, first_bad);
+    };
+    return nl_sections<CfStorageApplication>(ctx, 10, w->instances, first_instance, inst, cycles, t->n_rows,
+        [&](const NlAfterFill& after_fill, SlotClaims* claims) { return nl_synthesize_with(ctx, 10, walks, inst, cycles, t->n_rows, after_fill, claims); },
+        [] { return ZKW_OK; });  // (no queue section)
 }
 
 // LinearHasher (type 13): the Keccak-f netlist over the sponge of the serialized L2 -> L1 messages (compute_linear_keccak256,
@@ -1583,10 +1587,9 @@ extern "C" int zkw_linear_hasher_synthesize_batch_with_tails(zkw_ctx* ctx, const
     ZKW_LAUNCH(ctx, k_commit_encodings, blocks_for(n_queues, 64), 64, d_cf, n_queues, (u32)COMPACT_FORM_LEN, d_pi);
     std::vector<NlInstance> inst(n_queues);
     for (size_t b = 0; b < n_queues; b++) inst[b] = NlInstance{roff[b], (u32)(roff[b + 1] - roff[b]), d_pi + 4 * b, t, first_slot + b, true};
-    NlcfCall cf;
-    SlotClaims claims;  // the slots' tags: committed after the closed-form section's last launch
-    ZKW_TRY(nl_synthesize(ctx, 13, false, d_rounds, inst, cycles, n_rows, [&] { return nlcf_begin<CfLinearHasher>(ctx, 13, d_rec, 0, inst, cycles, n_rows, &cf); }, &claims));
-    {   // the queue section: every message is popped (Poseidon2 rows below the netlist, include/zkw_netlist_queue.h)
+    const auto netlist = [&](const NlAfterFill& after_fill, SlotClaims* claims) { return nl_synthesize(ctx, 13, false, d_rounds, inst, cycles, n_rows, after_fill, claims); };
+    ZKW_TRY(nl_sections<CfLinearHasher>(ctx, 13, d_rec, 0, inst, cycles, n_rows, netlist, [&]() -> int {
+        // the queue section: every message is popped (Poseidon2 rows below the netlist, include/zkw_netlist_queue.h)
         const u64* d_tails = nullptr;
         if (total && message_tails) ZKW_TRY(ctx->in("lh_tails", message_tails, total * 4, &d_tails));
         else if (total) {
@@ -1609,9 +1612,8 @@ extern "C" int zkw_linear_hasher_synthesize_batch_with_tails(zkw_ctx* ctx, const
             per[b].q[0] = NlqQueueIn{d_q ? d_q + moff[b] : nullptr, d_tails ? d_tails + 4 * moff[b] : nullptr, {0}, moff[b + 1] - moff[b]};
             memcpy(per[b].q[0].init, queue_states[b].head, 32);
         }
-        ZKW_TRY(nlq_synthesize(ctx, 13, per[0], inst, cycles, n_rows, &per));
-    }
-    ZKW_TRY(claims.commit_if(nlcf_end(ctx, 13, cf, cycles, n_rows)));
+        return nlq_synthesize(ctx, 13, per[0], inst, cycles, n_rows, &per);
+    }));
     memcpy(records_out, recv.data(), n_queues * sizeof recv[0]);
     if (public_inputs_out) ZKW_TRY(ctx->read_small(public_inputs_out, d_pi, 32 * n_queues));
     return ZKW_OK;
@@ -1630,10 +1632,3 @@ extern "C" int zkw_linear_hasher_synthesize(zkw_ctx* ctx, const zkw_log_query* m
     const uint64_t offsets[2] = {0, n};
     return zkw_linear_hasher_synthesize_batch(ctx, messages, offsets, 1, queue_state, capacity, t, slot, record_out, public_input_out);
 }
-
-extern "C" int zkw_linear_hasher_check_satisfied(zkw_ctx* ctx, const zkw_trace* t, size_t slot, uint32_t capacity, uint64_t* n_violations, uint64_t* first_bad) {
-    if (!ctx || !t || t->ctx->device != ctx->device || slot >= t->n_slots || !n_violations || capacity == 0)
-        return fail(ZKW_ERR_INVALID, "zkw_linear_hasher_check_satisfied: bad argument");
-    return nl_check(ctx, 13, t, slot, ZKW_LINEAR_HASHER_CYCLES(capacity), n_violations, first_bad);
-}
-

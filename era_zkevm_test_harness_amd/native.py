@@ -305,6 +305,12 @@ def _check(rc):
         raise ZkwError(rc, load().zkw_last_error().decode())
 
 
+def _violations(bad, first):
+    """what a zkw_*_check_satisfied call wrote, decoded: (violations, (kind, index, row) of the first)"""
+    v = first.value
+    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+
+
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -1492,12 +1498,6 @@ class Context:
                                                      _np_ptr(nd), C.byref(w.handle)))
         return w
 
-    def synthesize_ram(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-        """ZkSyncBaseLayerCircuit::synthesis for RAMPermutation instances (base_layer/mod.rs:286-323):
-        fills trace slots (first_slot + k) % n_slots with instances first_instance + k."""
-        n = witness.num_instances - first_instance if n_instances is None else n_instances
-        _check(load().zkw_ram_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
     def synthesize(self, circuit_type, witness, trace, first_instance=0, n_instances=1, first_slot=0):
         """zkw_synthesize: ZkSyncBaseLayerCircuit::synthesis as ONE entry point over the circuit types (base_layer/mod.rs:286-323);
         `witness` = the witness object of the type (its .handle is passed) or a raw handle"""
@@ -1508,15 +1508,13 @@ class Context:
         """zkw_check_satisfied: (violations, (kind, index, row) of the first) for a slot holding `circuit_type`"""
         bad, first = C.c_uint64(0), C.c_uint64(0)
         _check(load().zkw_check_satisfied(self.handle, circuit_type, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-        v = first.value
-        return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+        return _violations(bad, first)
 
     def check_if_satisfied_ram(self, trace, slot, capacity):
         """check_if_satisfied (src/tests/mod.rs:130-259): (violations, (kind, index, row) of the first)."""
         bad, first = C.c_uint64(0), C.c_uint64(0)
         _check(load().zkw_ram_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-        v = first.value
-        return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+        return _violations(bad, first)
 
     def compute_decommitts_sorter_circuit_snapshots(self, queries, deduplicator_circuit_capacity, dedup_in=None):
         """compute_decommitts_sorter_circuit_snapshots (sort_decommit_requests.rs:20-420) -> DecommitWitness."""
@@ -1743,87 +1741,13 @@ def circuit_geometry(circuit_type: int):
     return g[0]
 
 
-def _ctx_synthesize_decommit_sorter(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::CodeDecommittmentsSorter synthesis for instances of a DecommitWitness."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_decommit_sorter_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_decommit_sorter(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_decommit_sorter_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_decommit_sorter = _ctx_synthesize_decommit_sorter
-Context.check_if_satisfied_decommit_sorter = _ctx_check_if_satisfied_decommit_sorter
-
-
-def _ctx_synthesize_events_sorter(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::{EventsSorter, L1MessagesSorter} synthesis for instances of an EventsWitness."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_events_sorter_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_events_sorter(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_events_sorter_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_events_sorter = _ctx_synthesize_events_sorter
-
-
-def _ctx_synthesize_log_demux(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::LogDemuxer synthesis for instances of a DemuxWitness (the trace needs 151 columns)."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_log_demux_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_log_demux(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_log_demux_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_log_demux = _ctx_synthesize_log_demux
-
-
+# the trace widths of the netlist circuits (include/zkw_*_circuit_spec.h)
 KC_COLS, LH_COLS = 129, 145  # 86 + 3 x 14 + 1, 66 + 3 x 26 + 1 (include/zkw_keccak_circuit_spec.h, zkw_linear_hasher_circuit_spec.h)
-
-
-def _ctx_synthesize_keccak_round_function(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::Keccak256RoundFunction synthesis ("zkw trace v4") for instances of a keccak256
-    PrecompileWitness (the trace needs KC_COLS columns and at least 132 096 rows: the stacked tables)."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_keccak_round_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_keccak_round_function(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_keccak_round_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
 EK_COLS = 129  # 80 + 3 x 16 + 1 (include/zkw_ecrecover_circuit_spec.h)
-
-
-def _ctx_synthesize_ecrecover(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::ECRecover synthesis for instances of an ecrecover PrecompileWitness (the trace needs EK_COLS columns and
-    at least 197 632 rows: the stacked tables)"""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_ecrecover_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_ecrecover(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_ecrecover_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+SC_COLS = 153  # 116 + 4 x 9 + 1 (include/zkw_sha256_circuit_spec.h)
+DC_COLS = 153  # 108 + 4 x 11 + 1 (include/zkw_code_decommitter_circuit_spec.h)
+SA_COLS = 139  # 60 + 3 x 26 + 1 (include/zkw_storage_application_circuit_spec.h)
+SA_CYCLES_PER_WALK = 257
 
 
 def linear_hasher_cycles(capacity):
@@ -1866,108 +1790,65 @@ def _ctx_synthesize_linear_hasher_batch(self, queues, queue_states, capacity, tr
     return rec, pi
 
 
-SC_COLS = 153  # 116 + 4 x 9 + 1 (include/zkw_sha256_circuit_spec.h)
-
-
-def _ctx_synthesize_sha256_round_function(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::Sha256RoundFunction synthesis ("zkw trace v4") for instances of a sha256 PrecompileWitness
-    (the trace needs SC_COLS columns)."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_sha256_round_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_sha256_round_function(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_sha256_round_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-DC_COLS = 153  # 108 + 4 x 11 + 1 (include/zkw_code_decommitter_circuit_spec.h)
-
-
-def _ctx_synthesize_code_decommitter(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::CodeDecommitter synthesis ("zkw trace v4": the SHA-256 netlist on 108 + 4 x 11 columns) for
-    instances of a DecommitterWitness (the trace needs DC_COLS columns)."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_code_decommitter_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_code_decommitter(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_code_decommitter_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_code_decommitter = _ctx_synthesize_code_decommitter
-
-SA_COLS = 139  # 60 + 3 x 26 + 1 (include/zkw_storage_application_circuit_spec.h)
-SA_CYCLES_PER_WALK = 257
-
-
-def _ctx_synthesize_storage_application(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::StorageApplication synthesis ("zkw trace v4": the Merkle walks of the instance's tree queries as
-    Blake2s compressions on 60 + 3 x 26 columns) for instances of a StorageApplicationWitness (the trace needs SA_COLS columns)."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_storage_application_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_storage_application(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_storage_application_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_storage_application = _ctx_synthesize_storage_application
-Context.check_if_satisfied_storage_application = _ctx_check_if_satisfied_storage_application
-Context.check_if_satisfied_code_decommitter = _ctx_check_if_satisfied_code_decommitter
-Context.synthesize_sha256_round_function = _ctx_synthesize_sha256_round_function
-Context.check_if_satisfied_sha256_round_function = _ctx_check_if_satisfied_sha256_round_function
 def _ctx_check_copy_permutation(self, trace, slot, sigma):
     """zkw_check_copy_permutation: (violations, (kind, column, row)) of trace[cell] == trace[sigma[cell]]"""
     sg = np.ascontiguousarray(sigma, dtype=np.uint64)
     bad, first = C.c_uint64(0), C.c_uint64(0)
     _check(load().zkw_check_copy_permutation(self.handle, trace.handle, slot, _np_ptr(sg), sg.shape[0], C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+    return _violations(bad, first)
 
 
-def _ctx_check_if_satisfied_linear_hasher(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_linear_hasher_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
+# Context.synthesize_<suffix>(witness, trace, first_instance=0, n_instances=None: the rest, first_slot=0) -> zkw_<stem>_synthesize and
+# Context.check_if_satisfied_<suffix>(trace, slot, capacity) -> zkw_<stem>_check_satisfied: (method suffix, C symbol stem, synthesis docstring;
+# None: the type's synthesis is written out above, or its check in the class)
+_PER_TYPE = [
+    ("ram", "ram", """ZkSyncBaseLayerCircuit::synthesis for RAMPermutation instances (base_layer/mod.rs:286-323):
+    fills trace slots (first_slot + k) % n_slots with instances first_instance + k."""),
+    ("decommit_sorter", "decommit_sorter", """ZkSyncBaseLayerCircuit::CodeDecommittmentsSorter synthesis for instances of a DecommitWitness."""),
+    ("events_sorter", "events_sorter", """ZkSyncBaseLayerCircuit::{EventsSorter, L1MessagesSorter} synthesis for instances of an EventsWitness."""),
+    ("log_demux", "log_demux", """ZkSyncBaseLayerCircuit::LogDemuxer synthesis for instances of a DemuxWitness (the trace needs 151 columns)."""),
+    ("storage_sorter", "storage_sorter", """ZkSyncBaseLayerCircuit::StorageSorter synthesis for instances of a StorageWitness."""),
+    ("keccak_round_function", "keccak_round", """ZkSyncBaseLayerCircuit::Keccak256RoundFunction synthesis ("zkw trace v4") for instances of a keccak256
+    PrecompileWitness (the trace needs KC_COLS columns and at least 132 096 rows: the stacked tables)."""),
+    ("sha256_round_function", "sha256_round", """ZkSyncBaseLayerCircuit::Sha256RoundFunction synthesis ("zkw trace v4") for instances of a sha256 PrecompileWitness
+    (the trace needs SC_COLS columns)."""),
+    ("ecrecover", "ecrecover", """ZkSyncBaseLayerCircuit::ECRecover synthesis for instances of an ecrecover PrecompileWitness (the trace needs EK_COLS columns and
+    at least 197 632 rows: the stacked tables)"""),
+    ("code_decommitter", "code_decommitter", """ZkSyncBaseLayerCircuit::CodeDecommitter synthesis ("zkw trace v4": the SHA-256 netlist on 108 + 4 x 11 columns) for
+    instances of a DecommitterWitness (the trace needs DC_COLS columns)."""),
+    ("storage_application", "storage_application", """ZkSyncBaseLayerCircuit::StorageApplication synthesis ("zkw trace v4": the Merkle walks of the instance's tree queries as
+    Blake2s compressions on 60 + 3 x 26 columns) for instances of a StorageApplicationWitness (the trace needs SA_COLS columns)."""),
+    ("linear_hasher", "linear_hasher", None),
+]
 
 
-Context.check_if_satisfied_linear_hasher = _ctx_check_if_satisfied_linear_hasher
+def _synthesize_method(suffix, stem, doc):
+    def synthesize(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
+        n = witness.num_instances - first_instance if n_instances is None else n_instances
+        _check(getattr(load(), f"zkw_{stem}_synthesize")(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
+
+    synthesize.__name__, synthesize.__doc__ = f"synthesize_{suffix}", doc
+    return synthesize
+
+
+def _check_method(suffix, stem):
+    def check_if_satisfied(self, trace, slot, capacity):
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        _check(getattr(load(), f"zkw_{stem}_check_satisfied")(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
+        return _violations(bad, first)
+
+    check_if_satisfied.__name__ = f"check_if_satisfied_{suffix}"
+    return check_if_satisfied
+
+
+for _suffix, _stem, _doc in _PER_TYPE:
+    if _doc is not None:
+        setattr(Context, f"synthesize_{_suffix}", _synthesize_method(_suffix, _stem, _doc))
+    if _suffix != "ram":  # (check_if_satisfied_ram: in the class)
+        setattr(Context, f"check_if_satisfied_{_suffix}", _check_method(_suffix, _stem))
 Context.check_copy_permutation = _ctx_check_copy_permutation
 Context.synthesize_linear_hasher = _ctx_synthesize_linear_hasher
-Context.synthesize_ecrecover = _ctx_synthesize_ecrecover
-Context.check_if_satisfied_ecrecover = _ctx_check_if_satisfied_ecrecover
 Context.synthesize_linear_hasher_batch = _ctx_synthesize_linear_hasher_batch
-Context.synthesize_keccak_round_function = _ctx_synthesize_keccak_round_function
-Context.check_if_satisfied_keccak_round_function = _ctx_check_if_satisfied_keccak_round_function
-
-
-def _ctx_synthesize_storage_sorter(self, witness, trace, first_instance=0, n_instances=None, first_slot=0):
-    """ZkSyncBaseLayerCircuit::StorageSorter synthesis for instances of a StorageWitness."""
-    n = witness.num_instances - first_instance if n_instances is None else n_instances
-    _check(load().zkw_storage_sorter_synthesize(self.handle, witness.handle, first_instance, n, trace.handle, first_slot))
-
-
-def _ctx_check_if_satisfied_storage_sorter(self, trace, slot, capacity):
-    bad, first = C.c_uint64(0), C.c_uint64(0)
-    _check(load().zkw_storage_sorter_check_satisfied(self.handle, trace.handle, slot, capacity, C.byref(bad), C.byref(first)))
-    v = first.value
-    return bad.value, (v >> 56, (v >> 32) & 0xFFFFFF, v & 0xFFFFFFFF)
-
-
-Context.synthesize_storage_sorter = _ctx_synthesize_storage_sorter
-Context.check_if_satisfied_storage_sorter = _ctx_check_if_satisfied_storage_sorter
-Context.check_if_satisfied_log_demux = _ctx_check_if_satisfied_log_demux
-Context.check_if_satisfied_events_sorter = _ctx_check_if_satisfied_events_sorter
 
 
 # ---- MainVM instance slicing (include/zkw_types.h: zkw_vm_instance & co) ------------------------------------------------
