@@ -1110,29 +1110,29 @@ struct zkw_ram_witness {
 extern "C" void zkw_ram_witness_free(zkw_ram_witness* w);
 static inline size_t ram_gp_groups(uint32_t capacity) { return ((size_t)capacity + 63) / 64; }  // checkpoints per instance
 static inline size_t ram_nd_tiles(uint32_t capacity) { return ((size_t)capacity + 255) / 256; }  // tiles of 256 cycles per instance
-static int ram_alloc(zkw_ram_witness* w, size_t n_blocks) {
+static int ram_alloc(Building<zkw_ram_witness>& w, size_t n_blocks) {
     const size_t t = w->total, ni = w->n_instances;
-    HIP_TRY(dev_malloc((void**)&w->perm, (t + 1) * sizeof(u32)));
-    HIP_TRY(dev_malloc((void**)&w->unsorted_caps, (t + 1) * 4 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->sorted_caps, (t + 1) * 4 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->unsorted_marks, (ni + 1) * 12 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->sorted_marks, (ni + 1) * 12 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->challenges, (n_blocks + 1) * 18 * sizeof(u64)));
+    HIP_TRY(w.alloc(&w->perm, (t + 1) * sizeof(u32), 0));
+    HIP_TRY(w.alloc(&w->unsorted_caps, (t + 1) * 4 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->sorted_caps, (t + 1) * 4 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->unsorted_marks, (ni + 1) * 12 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->sorted_marks, (ni + 1) * 12 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->challenges, (n_blocks + 1) * 18 * sizeof(u64), 0));
     {   // window of the sorted queries: whole blocks, 192 MB, at least the largest block
         size_t max_block = 0;
         for (size_t b = 0; b + 1 < w->offsets.size(); b++) max_block = std::max(max_block, (size_t)(w->offsets[b + 1] - w->offsets[b]));
         size_t sq_window = (size_t)1 << 22;
         if (const char* e = getenv("ZKW_Z_WINDOW_ITEMS")) sq_window = (size_t)strtoull(e, nullptr, 10);  // tests: force small groups
         w->sqcap = std::max(max_block, std::min(t, sq_window));
-        HIP_TRY(dev_malloc((void**)&w->sq_win, (w->sqcap + 1) * sizeof(zkw_mem_query)));
+        HIP_TRY(w.alloc(&w->sq_win, (w->sqcap + 1) * sizeof(zkw_mem_query), 0));
     }
-    HIP_TRY(dev_malloc((void**)&w->gp_ckpt, (ni * ram_gp_groups(w->capacity) + 1) * 4 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->gp_total, (n_blocks + 1) * 4 * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->nd_prefix, (ni * ram_nd_tiles(w->capacity) + 1) * sizeof(u32)));
-    HIP_TRY(dev_malloc((void**)&w->instances, (ni + 1) * sizeof(zkw_ram_instance)));
-    HIP_TRY(dev_malloc((void**)&w->nondet_counts, (ni + 1) * sizeof(u32)));
-    HIP_TRY(dev_malloc((void**)&w->compact_forms, (ni + 1) * COMPACT_FORM_LEN * sizeof(u64)));
-    HIP_TRY(dev_malloc((void**)&w->public_inputs, (ni + 1) * 4 * sizeof(u64)));
+    HIP_TRY(w.alloc(&w->gp_ckpt, (ni * ram_gp_groups(w->capacity) + 1) * 4 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->gp_total, (n_blocks + 1) * 4 * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->nd_prefix, (ni * ram_nd_tiles(w->capacity) + 1) * sizeof(u32), 0));
+    HIP_TRY(w.alloc(&w->instances, (ni + 1) * sizeof(zkw_ram_instance), 0));
+    HIP_TRY(w.alloc(&w->nondet_counts, (ni + 1) * sizeof(u32), 0));
+    HIP_TRY(w.alloc(&w->compact_forms, (ni + 1) * COMPACT_FORM_LEN * sizeof(u64), 0));
+    HIP_TRY(w.alloc(&w->public_inputs, (ni + 1) * 4 * sizeof(u64), 0));
     return ZKW_OK;
 }
 
@@ -1361,34 +1361,22 @@ extern "C" int zkw_ram_build_instances_batch(zkw_ctx* ctx, const zkw_mem_query* 
         w = nullptr;
         *out = nullptr;
     }
+    std::optional<Building<zkw_ram_witness>> fresh;  // a reused witness is the caller's: never dropped here, and it already holds its reference
     if (!w) {
-        w = new zkw_ram_witness();
-        w->ctx = ctx;
+        fresh.emplace(ctx);
+        w = fresh->w;
         w->offsets = offs;
         w->inst_offsets = ioffs;
         w->capacity = capacity;
         w->total = total;
         w->n_instances = ioffs[n_blocks];
-        int rc = ram_alloc(w, n_blocks);
-        if (rc != ZKW_OK) {
-            w->release();
-            delete w;
-            return rc;
-        }
+        ZKW_TRY(ram_alloc(*fresh, n_blocks));
     }
     const zkw_mem_query* d_q = nullptr;
-    int rc = ctx->in("ram_q", q + base, total, &d_q);
-    if (rc == ZKW_OK) rc = ram_run(ctx, w, d_q, n_nondet);
-    if (rc == ZKW_OK) rc = ctx->sync_if_host();
-    if (rc != ZKW_OK) {
-        if (!*out) {
-            w->release();
-            delete w;
-        }
-        return rc;
-    }
-    if (!*out) ctx_retain(ctx);  // a reused witness already holds its reference
-    *out = w;
+    ZKW_TRY(ctx->in("ram_q", q + base, total, &d_q));
+    ZKW_TRY(ram_run(ctx, w, d_q, n_nondet));
+    ZKW_TRY(ctx->sync_if_host());
+    if (fresh) fresh->commit(out);
     return ZKW_OK;
 }
 

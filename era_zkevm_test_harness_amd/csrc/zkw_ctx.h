@@ -14,6 +14,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <thread>
 
 #include <cstdarg>
@@ -512,6 +513,42 @@ static void witness_free(W* w) {
     delete w;
     ctx_release(owner);
 }
+// A handle under construction: any W with `zkw_ctx* ctx` and `void release()` (the witness structs, zkw_storage_tree). A builder entry makes
+// one, fills it, and commits it to the caller as its last step; until then EVERY return — a refusal, ZKW_TRY, HIP_TRY, a ZKW_LAUNCH* —
+// drops it the way witness_free does, minus the reference a committed handle holds: the stream is synchronised first (nothing queued may
+// still write a buffer the cache hands to somebody else), and the message of the refusal that led here stays the thread's last error.
+template <class W>
+struct Building {
+    W* w;
+    hipError_t err = hipSuccess;  // the first failed alloc
+    explicit Building(zkw_ctx* ctx) : w(new W()) { w->ctx = ctx; }
+    Building(Building&& o) : w(o.w), err(o.err) { o.w = nullptr; }
+    Building(const Building&) = delete;
+    Building& operator=(const Building&) = delete;
+    ~Building() {
+        if (!w) return;
+        const std::string refusal = zkw_last_error();
+        (void)w->ctx->sync_stream();
+        (void)fail(ZKW_OK, "%s", refusal.c_str());
+        w->release();
+        delete w;
+    }
+    W* operator->() const { return w; }
+    // `bytes + pad` from the allocation cache (the builders' arrays carry 64 bytes of slack); after a failure the rest are not tried
+    template <class T>
+    hipError_t alloc(T** p, size_t bytes, size_t pad = 64) {
+        if (err == hipSuccess) err = dev_malloc(p, bytes + pad);
+        return err;
+    }
+    int oom(const char* entry) const {
+        return err == hipSuccess ? ZKW_OK : fail(ZKW_ERR_OOM, "%s: hipMalloc failed: %s", entry, hipGetErrorString(err));
+    }
+    void commit(W** out) {
+        ctx_retain(w->ctx);
+        *out = w;
+        w = nullptr;
+    }
+};
 
 
 // device-level steps (zkw_api.hip): every builder's queue chains, challenges and grand products go through these

@@ -62,6 +62,20 @@ extern "C" int zkw_decommitter_memory_queries(zkw_ctx* ctx, const zkw_decommit_q
     return ctx->sync_if_host();
 }
 
+// The states of a slice of the memory queue (decommitter, precompiles) are given or hashed here: given when the caller has already hashed
+// the whole memory queue the slice belongs to (zkw_block_run), else one chain from `mem_in`, uploaded to the scratch `in_name`.
+static int mem_queue_tails(zkw_ctx* ctx, const char* in_name, const zkw_queue_state12& mem_in, const uint64_t* given, u64* enc, u64* tails, size_t n) {
+    zkw_queue_state12* d_min = nullptr;
+    std::vector<zkw_queue_state12> minv(1, mem_in);
+    ZKW_TRY(ctx->upload(in_name, minv, &d_min));
+    if (given) {
+        HIP_TRY(ctx->copy_async(tails, given, n * 96, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        return ZKW_OK;
+    }
+    std::vector<ChainJob> chains(1, ChainJob{enc, tails, d_min->tail, n});
+    return dev_chains(ctx, chains);
+}
+
 extern "C" int zkw_decommitter_build_with_tails(zkw_ctx* ctx, const zkw_decommit_query* requests, const uint64_t* dedup_tails,
                                      size_t n_requests, const uint32_t* words, const uint64_t* word_offsets,
                                      uint32_t capacity, const zkw_queue_state12* mem_in, const uint64_t* given_mem_tails,
@@ -75,56 +89,41 @@ extern "C" int zkw_decommitter_build_with_tails(zkw_ctx* ctx, const zkw_decommit
         if (word_offsets[k + 1] <= word_offsets[k]) return fail(ZKW_ERR_INVALID, "request %zu has no bytecode (decommit_code.rs:236)", k);
         roff[k + 1] = roff[k] + (woff[k + 1] - woff[k] + 1) / 2;
     }
-    zkw_decommitter_witness* w = new zkw_decommitter_witness();
-    w->ctx = ctx;
+    Building<zkw_decommitter_witness> w(ctx);
     w->n_requests = n_requests;
     w->total_words = woff[n_requests];
     w->total_rounds = roff[n_requests];
     w->n_instances = (w->total_rounds + capacity - 1) / capacity;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->mem_q, w->total_words * sizeof(zkw_mem_query));
-    alloc((void**)&w->mem_enc, w->total_words * 64);
-    alloc((void**)&w->mem_tails, w->total_words * 96);
-    alloc((void**)&w->round_states, w->total_rounds * 32);
-    alloc((void**)&w->sha256_rounds, w->total_rounds * sizeof(zkw_sha256_round_record));
-    alloc((void**)&w->requests, n_requests * sizeof(zkw_decommit_query));
-    alloc((void**)&w->dedup_tails, n_requests * 96);
-    alloc((void**)&w->round_ops, w->total_rounds * sizeof(RoundOps));
+    w.alloc(&w->mem_q, w->total_words * sizeof(zkw_mem_query));
+    w.alloc(&w->mem_enc, w->total_words * 64);
+    w.alloc(&w->mem_tails, w->total_words * 96);
+    w.alloc(&w->round_states, w->total_rounds * 32);
+    w.alloc(&w->sha256_rounds, w->total_rounds * sizeof(zkw_sha256_round_record));
+    w.alloc(&w->requests, n_requests * sizeof(zkw_decommit_query));
+    w.alloc(&w->dedup_tails, n_requests * 96);
+    w.alloc(&w->round_ops, w->total_rounds * sizeof(RoundOps));
     w->mem_in = *mem_in;
     w->capacity = capacity;
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_decommitter_instance));
-    auto bail = [&](int rc) { w->release(); delete w; return rc; };
-    if (e != hipSuccess) return bail(fail(ZKW_ERR_OOM, "zkw_decommitter_build: hipMalloc failed: %s", hipGetErrorString(e)));
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_decommitter_instance));
+    ZKW_TRY(w.oom("zkw_decommitter_build"));
     const zkw_decommit_query* d_req = nullptr;
     const u64* d_dt = nullptr;
     const u32* d_words = nullptr;
     u64 *d_woff = nullptr, *d_roff = nullptr;
     u32* d_viol = nullptr;
-    int rc = ctx->in("dcm_req", requests, n_requests, &d_req);
-    if (rc == ZKW_OK) rc = ctx->in("dcm_dt", dedup_tails, n_requests * 12, &d_dt);
-    if (rc == ZKW_OK) rc = ctx->in("dcm_words", words + 8 * word_offsets[0], w->total_words * 8, &d_words);
-    if (rc == ZKW_OK) rc = ctx->upload("dcm_woff", woff, &d_woff);
-    if (rc == ZKW_OK) rc = ctx->upload("dcm_roff", roff, &d_roff);
-    if (rc == ZKW_OK) rc = ctx->scratch_t<u32>("dcm_viol", 1, &d_viol);
-    if (rc != ZKW_OK) return bail(rc);
-    if (ctx->memset_async(d_viol, 0, 4) != hipSuccess) return bail(fail(ZKW_ERR_HIP, "memset failed"));
-    if (ctx->copy_async(w->requests, d_req, n_requests * sizeof(zkw_decommit_query), hipMemcpyDeviceToDevice) != hipSuccess ||
-        ctx->copy_async(w->dedup_tails, d_dt, n_requests * 96, hipMemcpyDeviceToDevice) != hipSuccess)
-        return bail(fail(ZKW_ERR_HIP, "copy of the decommit requests failed"));
+    ZKW_TRY(ctx->in("dcm_req", requests, n_requests, &d_req));
+    ZKW_TRY(ctx->in("dcm_dt", dedup_tails, n_requests * 12, &d_dt));
+    ZKW_TRY(ctx->in("dcm_words", words + 8 * word_offsets[0], w->total_words * 8, &d_words));
+    ZKW_TRY(ctx->upload("dcm_woff", woff, &d_woff));
+    ZKW_TRY(ctx->upload("dcm_roff", roff, &d_roff));
+    ZKW_TRY(ctx->scratch_t<u32>("dcm_viol", 1, &d_viol));
+    HIP_TRY(ctx->memset_async(d_viol, 0, 4));
+    HIP_TRY(ctx->copy_async(w->requests, d_req, n_requests * sizeof(zkw_decommit_query), hipMemcpyDeviceToDevice));
+    HIP_TRY(ctx->copy_async(w->dedup_tails, d_dt, n_requests * 96, hipMemcpyDeviceToDevice));
     DecommitterJob job{d_req, d_words, d_woff, d_roff, w->round_states, w->mem_q, w->mem_enc, d_viol, n_requests, w->sha256_rounds, w->round_ops};
     ZKW_LAUNCH(ctx, k_decommitter_sha, blocks_for(n_requests, 64), 64, job);
     ZKW_LAUNCH(ctx, k_decommitter_mem_queries, blocks_for(w->total_words, 256), 256, job, (u64)w->total_words);
-    zkw_queue_state12* d_min = nullptr;
-    std::vector<zkw_queue_state12> minv(1, *mem_in);
-    if ((rc = ctx->upload("dcm_mem_in", minv, &d_min)) != ZKW_OK) return bail(rc);
-    if (given_mem_tails) {  // the caller has already hashed the memory queue this slice belongs to (zkw_block_run)
-        if (ctx->copy_async(w->mem_tails, given_mem_tails, w->total_words * 96, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(ZKW_ERR_HIP, "copy of the given memory-queue states failed"));
-    } else {
-        std::vector<ChainJob> chains(1, ChainJob{w->mem_enc, w->mem_tails, d_min->tail, w->total_words});
-        if ((rc = dev_chains(ctx, chains)) != ZKW_OK) return bail(rc);
-    }
+    ZKW_TRY(mem_queue_tails(ctx, "dcm_mem_in", *mem_in, given_mem_tails, w->mem_enc, w->mem_tails, w->total_words));
     std::vector<DecommitterBlock> blk(1);
     blk[0].job = job;
     blk[0].dedup_tails = d_dt;
@@ -135,15 +134,13 @@ extern "C" int zkw_decommitter_build_with_tails(zkw_ctx* ctx, const zkw_decommit
     blk[0].total_words = w->total_words;
     blk[0].capacity = capacity;
     DecommitterBlock* d_blk = nullptr;
-    if ((rc = ctx->upload("dcm_block", blk, &d_blk)) != ZKW_OK) return bail(rc);
+    ZKW_TRY(ctx->upload("dcm_block", blk, &d_blk));
     ZKW_LAUNCH(ctx, k_decommitter_instances, blocks_for(w->n_instances, 64), 64, d_blk);
     u32 viol = 0;
-    if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
-        return bail(fail(ZKW_ERR_HIP, "readback failed"));
-    if (viol) return bail(fail(ZKW_ERR_CHECK_FAILED, "%u bytecodes do not match their decommit request (length parity, word count or "
-                                                     "SHA-256 digest, decommit_code.rs:241-244, 323-337)", viol));
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(ctx->read_small(&viol, d_viol, 4));
+    if (viol) return fail(ZKW_ERR_CHECK_FAILED, "%u bytecodes do not match their decommit request (length parity, word count or "
+                                                "SHA-256 digest, decommit_code.rs:241-244, 323-337)", viol);
+    w.commit(out);
     return ZKW_OK;
 }
 
@@ -260,8 +257,7 @@ extern "C" int zkw_precompile_build_with_tails(zkw_ctx* ctx, int kind, const zkw
         if (meta[1] != n_queries)
             return fail(ZKW_ERR_INVALID, "the requests need %llu memory queries, %zu given", (unsigned long long)meta[1], n_queries);
     }
-    zkw_precompile_witness* w = new zkw_precompile_witness();
-    w->ctx = ctx;
+    Building<zkw_precompile_witness> w(ctx);
     w->n_requests = n_requests;
     w->n_queries = n_queries;
     w->total_rounds = meta[0];
@@ -269,44 +265,30 @@ extern "C" int zkw_precompile_build_with_tails(zkw_ctx* ctx, int kind, const zkw
     w->n_instances = n_requests ? (w->total_rounds + capacity - 1) / capacity : 1;
     w->kind = kind;
     w->capacity = capacity;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->mem_enc, n_queries * 64);
-    alloc((void**)&w->mem_tails, n_queries * 96);
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_precompile_instance));
-    if (kind == ZKW_PRECOMPILE_KECCAK256) alloc((void**)&w->keccak_rounds, w->total_rounds * sizeof(zkw_keccak_round_record));
-    if (kind == ZKW_PRECOMPILE_SHA256) alloc((void**)&w->sha256_rounds, w->total_rounds * sizeof(zkw_sha256_round_record));
-    alloc((void**)&w->requests, n_requests * sizeof(zkw_log_query));  // (the queue sections of the three circuits)
-    alloc((void**)&w->req_tails, n_requests * 32);
-    alloc((void**)&w->mem_q, n_queries * sizeof(zkw_mem_query));
-    alloc((void**)&w->round_ops, w->total_rounds * sizeof(RoundOps));
+    w.alloc(&w->mem_enc, n_queries * 64);
+    w.alloc(&w->mem_tails, n_queries * 96);
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_precompile_instance));
+    if (kind == ZKW_PRECOMPILE_KECCAK256) w.alloc(&w->keccak_rounds, w->total_rounds * sizeof(zkw_keccak_round_record));
+    if (kind == ZKW_PRECOMPILE_SHA256) w.alloc(&w->sha256_rounds, w->total_rounds * sizeof(zkw_sha256_round_record));
+    w.alloc(&w->requests, n_requests * sizeof(zkw_log_query));  // (the queue sections of the three circuits)
+    w.alloc(&w->req_tails, n_requests * 32);
+    w.alloc(&w->mem_q, n_queries * sizeof(zkw_mem_query));
+    w.alloc(&w->round_ops, w->total_rounds * sizeof(RoundOps));
     w->mem_in = *mem_in;
-    auto bail = [&](int rc) { w->release(); delete w; return rc; };
-    if (e != hipSuccess) return bail(fail(ZKW_ERR_OOM, "zkw_precompile_build: hipMalloc failed: %s", hipGetErrorString(e)));
-    int rc = ZKW_OK;
+    ZKW_TRY(w.oom("zkw_precompile_build"));
     PrecompileSnap* d_snaps = nullptr;
     u32* d_viol = nullptr;
-    if ((rc = ctx->scratch_t<u32>("pc_viol", 1, &d_viol)) != ZKW_OK) return bail(rc);
-    if (ctx->memset_async(d_viol, 0, 4) != hipSuccess) return bail(fail(ZKW_ERR_HIP, "memset failed"));
+    ZKW_TRY(ctx->scratch_t<u32>("pc_viol", 1, &d_viol));
+    HIP_TRY(ctx->memset_async(d_viol, 0, 4));
     if (n_requests) {
-        if ((rc = ctx->scratch_t<PrecompileSnap>("pc_snaps", w->n_instances, &d_snaps)) != ZKW_OK) return bail(rc);
+        ZKW_TRY(ctx->scratch_t<PrecompileSnap>("pc_snaps", w->n_instances, &d_snaps));
         if (n_queries) {
-            if ((rc = dev_encode(ctx, d_mq, n_queries, w->mem_enc)) != ZKW_OK) return bail(rc);
-            zkw_queue_state12* d_min = nullptr;
-            std::vector<zkw_queue_state12> minv(1, *mem_in);
-            if ((rc = ctx->upload("pc_mem_in", minv, &d_min)) != ZKW_OK) return bail(rc);
-            if (given_mem_tails) {  // already hashed by the caller as part of the whole memory queue (zkw_block_run)
-                if (ctx->copy_async(w->mem_tails, given_mem_tails, n_queries * 96, ctx->ptr_mode == ZKW_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
-                    return bail(fail(ZKW_ERR_HIP, "copy of the given memory-queue states failed"));
-            } else {
-                std::vector<ChainJob> chains(1, ChainJob{w->mem_enc, w->mem_tails, d_min->tail, n_queries});
-                if ((rc = dev_chains(ctx, chains)) != ZKW_OK) return bail(rc);
-            }
+            ZKW_TRY(dev_encode(ctx, d_mq, n_queries, w->mem_enc));
+            ZKW_TRY(mem_queue_tails(ctx, "pc_mem_in", *mem_in, given_mem_tails, w->mem_enc, w->mem_tails, n_queries));
         }
-        if ((ctx->copy_async(w->requests, d_req, n_requests * sizeof(zkw_log_query), hipMemcpyDeviceToDevice) != hipSuccess ||
-             ctx->copy_async(w->req_tails, d_rt, n_requests * 32, hipMemcpyDeviceToDevice) != hipSuccess ||
-             (n_queries && ctx->copy_async(w->mem_q, d_mq, n_queries * sizeof(zkw_mem_query), hipMemcpyDeviceToDevice) != hipSuccess)))
-            return bail(fail(ZKW_ERR_HIP, "copy of the precompile calls failed"));
+        HIP_TRY(ctx->copy_async(w->requests, d_req, n_requests * sizeof(zkw_log_query), hipMemcpyDeviceToDevice));
+        HIP_TRY(ctx->copy_async(w->req_tails, d_rt, n_requests * 32, hipMemcpyDeviceToDevice));
+        if (n_queries) HIP_TRY(ctx->copy_async(w->mem_q, d_mq, n_queries * sizeof(zkw_mem_query), hipMemcpyDeviceToDevice));
         PrecompileJob job{kind, d_req, d_mq, d_roff, d_qoff, d_rdoff, d_snaps, d_viol, n_requests, w->total_rounds, capacity, w->keccak_rounds, w->sha256_rounds, w->round_ops};
         ZKW_LAUNCH(ctx, k_precompile_walk, blocks_for(n_requests, 64), 64, job);
     }
@@ -322,15 +304,13 @@ extern "C" int zkw_precompile_build_with_tails(zkw_ctx* ctx, int kind, const zkw
     blk[0].n_instances = w->n_instances;
     blk[0].capacity = capacity;
     PrecompileBlock* d_blk = nullptr;
-    if ((rc = ctx->upload("pc_block", blk, &d_blk)) != ZKW_OK) return bail(rc);
+    ZKW_TRY(ctx->upload("pc_block", blk, &d_blk));
     ZKW_LAUNCH(ctx, k_precompile_instances, blocks_for(w->n_instances, 64), 64, d_blk);
     u32 viol = 0;
-    if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
-        return bail(fail(ZKW_ERR_HIP, "readback failed"));
-    if (viol) return bail(fail(ZKW_ERR_CHECK_FAILED, "%u requests whose memory queries do not fit their ABI (read/write flags, word "
-                                                     "index or count: the asserts of the round walks)", viol));
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(ctx->read_small(&viol, d_viol, 4));
+    if (viol) return fail(ZKW_ERR_CHECK_FAILED, "%u requests whose memory queries do not fit their ABI (read/write flags, word "
+                                                "index or count: the asserts of the round walks)", viol);
+    w.commit(out);
     return ZKW_OK;
 }
 
@@ -385,21 +365,16 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
         return fail(ZKW_ERR_INVALID, "zkw_storage_application_build: bad argument");
     if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "too many storage queries");
     HIP_TRY(hipSetDevice(ctx->device));
-    zkw_storage_application_witness* w = new zkw_storage_application_witness();
-    w->ctx = ctx;
+    Building<zkw_storage_application_witness> w(ctx);
     w->n = n;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->keys, n * 32);
-    alloc((void**)&w->paths, n * 256 * 32);
-    alloc((void**)&w->roots, n * 32);
-    alloc((void**)&w->leaf_indexes, n * 8);
-    alloc((void**)&w->items, n * sizeof(SapItem));
-    alloc((void**)&w->walk_hashes, n * 2 * 257 * 32);
+    w.alloc(&w->keys, n * 32);
+    w.alloc(&w->paths, n * 256 * 32);
+    w.alloc(&w->roots, n * 32);
+    w.alloc(&w->leaf_indexes, n * 8);
+    w.alloc(&w->items, n * sizeof(SapItem));
+    w.alloc(&w->walk_hashes, n * 2 * 257 * 32);
     w->capacity = capacity;
-    auto bail = [&](int rc) { w->release(); delete w; return rc; };
-    if (e != hipSuccess) return bail(fail(ZKW_ERR_OOM, "zkw_storage_application_build: hipMalloc failed: %s", hipGetErrorString(e)));
-    int rc = ZKW_OK;
+    ZKW_TRY(w.oom("zkw_storage_application_build"));
     SapJob job;
     memset(&job, 0, sizeof job);
     const u64* d_qt = nullptr;
@@ -407,39 +382,37 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
     u64 *d_snap = nullptr, *d_meta = nullptr;
     uint8_t* d_hash = nullptr;
     u32* d_viol = nullptr;
-    auto TRY = [&](int r) { if (rc == ZKW_OK) rc = r; };
     if (n) {
-        TRY(ctx->in("sap_q", queries, n, &job.queries));
-        TRY(ctx->in("sap_qt", query_tails, n * 4, &d_qt));
-        TRY(ctx->in("sap_ii", init_leaf_indexes, n, &job.init_index));
-        TRY(ctx->in("sap_ip", init_merkle_paths, n * 256 * 32, &d_ip));
+        ZKW_TRY(ctx->in("sap_q", queries, n, &job.queries));
+        ZKW_TRY(ctx->in("sap_qt", query_tails, n * 4, &d_qt));
+        ZKW_TRY(ctx->in("sap_ii", init_leaf_indexes, n, &job.init_index));
+        ZKW_TRY(ctx->in("sap_ip", init_merkle_paths, n * 256 * 32, &d_ip));
     }
     job.init_paths = reinterpret_cast<const u32*>(d_ip);
     job.keys = w->keys; job.paths = w->paths; job.roots = w->roots; job.walk_hashes = w->walk_hashes;
-    TRY(ctx->scratch_t<u64>("sap_newidx", n + 1, &job.new_index));
-    TRY(ctx->scratch_t<u32>("sap_prevw", n + 1, &job.prev_write));
-    TRY(ctx->scratch_t<u32>("sap_chunk", n + 1, &job.chunk_of));
-    TRY(ctx->scratch_t<u32>("sap_fwu", n + 1, &job.first_writes_upto));
-    TRY(ctx->scratch_t<u64>("sap_cend", n + 2, &job.chunk_end));
-    TRY(ctx->scratch_t<u32>("sap_jstar", (n + 1) * 256, &job.jstar));
-    TRY(ctx->scratch_t<u32>("sap_A0", (n + 1) * 8, &job.A0));
-    TRY(ctx->scratch_t<u32>("sap_A1", (n + 1) * 8, &job.A1));
-    TRY(ctx->scratch_t<u32>("sap_C0", (n + 1) * 8, &job.C0));
-    TRY(ctx->scratch_t<u32>("sap_C1", (n + 1) * 8, &job.C1));
-    TRY(ctx->scratch_t<u32>("sap_R0", (n + 1) * 8, &job.R0));
-    TRY(ctx->scratch_t<u32>("sap_R1", (n + 1) * 8, &job.R1));
-    TRY(ctx->scratch_t<u32>("sap_viol", 1, &d_viol));
-    TRY(ctx->scratch_t<u64>("sap_meta", 2, &d_meta));
-    TRY(ctx->scratch_t<u64>("sap_snap", (n + 1) * 25, &d_snap));
-    TRY(ctx->scratch_t<uint8_t>("sap_hash", 32, &d_hash));
-    if (rc != ZKW_OK) return bail(rc);
+    ZKW_TRY(ctx->scratch_t<u64>("sap_newidx", n + 1, &job.new_index));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_prevw", n + 1, &job.prev_write));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_chunk", n + 1, &job.chunk_of));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_fwu", n + 1, &job.first_writes_upto));
+    ZKW_TRY(ctx->scratch_t<u64>("sap_cend", n + 2, &job.chunk_end));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_jstar", (n + 1) * 256, &job.jstar));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_A0", (n + 1) * 8, &job.A0));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_A1", (n + 1) * 8, &job.A1));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_C0", (n + 1) * 8, &job.C0));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_C1", (n + 1) * 8, &job.C1));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_R0", (n + 1) * 8, &job.R0));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_R1", (n + 1) * 8, &job.R1));
+    ZKW_TRY(ctx->scratch_t<u32>("sap_viol", 1, &d_viol));
+    ZKW_TRY(ctx->scratch_t<u64>("sap_meta", 2, &d_meta));
+    ZKW_TRY(ctx->scratch_t<u64>("sap_snap", (n + 1) * 25, &d_snap));
+    ZKW_TRY(ctx->scratch_t<uint8_t>("sap_hash", 32, &d_hash));
     job.violations = d_viol;
     job.meta = d_meta;
     job.n = n;
     job.next_enumeration_index = initial_next_enumeration_index;
     memcpy(job.initial_root, initial_root, 32);
     job.capacity = capacity;
-    if (ctx->memset_async(d_viol, 0, 4) != hipSuccess) return bail(fail(ZKW_ERR_HIP, "memset failed"));
+    HIP_TRY(ctx->memset_async(d_viol, 0, 4));
     u64 meta[2] = {1, initial_next_enumeration_index};
     if (n) {
         const unsigned g64 = blocks_for(n, 64);
@@ -452,17 +425,15 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
         if (n <= SAP_PERSISTENT_MAX) {
             ZKW_LAUNCH(ctx, k_sap_levels, 1, SAP_PERSISTENT_THREADS, job);
         } else {
-            for (int L = 0; L < ZKW_STORAGE_TREE_DEPTH && rc == ZKW_OK; L++) ZKW_LAUNCH(ctx, k_sap_level, g64, 64, job, L);
+            for (int L = 0; L < ZKW_STORAGE_TREE_DEPTH; L++) ZKW_LAUNCH(ctx, k_sap_level, g64, 64, job, L);
         }
         ZKW_LAUNCH(ctx, k_sap_roots, g64, 64, job);
-        if (rc != ZKW_OK) return bail(rc);
-        if (ctx->copy_async(w->leaf_indexes, job.init_index, n * 8, hipMemcpyDeviceToDevice) != hipSuccess ||
-            ctx->read_small(meta, d_meta, sizeof meta) != ZKW_OK)
-            return bail(fail(ZKW_ERR_HIP, "readback failed"));
+        HIP_TRY(ctx->copy_async(w->leaf_indexes, job.init_index, n * 8, hipMemcpyDeviceToDevice));
+        ZKW_TRY(ctx->read_small(meta, d_meta, sizeof meta));
     }
     w->n_instances = n ? (size_t)meta[0] : 1;
-    if (dev_malloc((void**)&w->instances, w->n_instances * sizeof(zkw_storage_application_instance) + 64) != hipSuccess)
-        return bail(fail(ZKW_ERR_OOM, "zkw_storage_application_build: hipMalloc failed"));
+    if (w.alloc(&w->instances, w->n_instances * sizeof(zkw_storage_application_instance)) != hipSuccess)
+        return fail(ZKW_ERR_OOM, "zkw_storage_application_build: hipMalloc failed");
     SapKeccakOut ko{d_snap, d_hash};
     ZKW_LAUNCH(ctx, k_sap_keccak, 1, 64, job, ko);
     std::vector<SapBlock> blk(1);
@@ -473,18 +444,14 @@ extern "C" int zkw_storage_application_build(zkw_ctx* ctx, const zkw_log_query* 
     blk[0].instances = w->instances;
     blk[0].n_instances = w->n_instances;
     SapBlock* d_blk = nullptr;
-    TRY(ctx->upload("sap_block", blk, &d_blk));
-    if (rc != ZKW_OK) return bail(rc);
+    ZKW_TRY(ctx->upload("sap_block", blk, &d_blk));
     ZKW_LAUNCH(ctx, k_sap_instances, blocks_for(w->n_instances, 64), 64, d_blk);
-    if (rc != ZKW_OK) return bail(rc);
     u32 viol = 0;
-    if (ctx->read_small(&viol, d_viol, 4) != ZKW_OK)
-        return bail(fail(ZKW_ERR_HIP, "readback failed"));
-    if (viol) return bail(fail(ZKW_ERR_CHECK_FAILED, "%u storage queries contradict the tree: the pre-state proof does not lead to the "
-                                                     "initial root, the read value is not the leaf's (storage_application.rs:221,276), "
-                                                     "or a slot occurs twice", viol));
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(ctx->read_small(&viol, d_viol, 4));
+    if (viol) return fail(ZKW_ERR_CHECK_FAILED, "%u storage queries contradict the tree: the pre-state proof does not lead to the "
+                                                "initial root, the read value is not the leaf's (storage_application.rs:221,276), "
+                                                "or a slot occurs twice", viol);
+    w.commit(out);
     return ZKW_OK;
 }
 

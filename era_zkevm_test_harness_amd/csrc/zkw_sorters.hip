@@ -123,38 +123,25 @@ extern "C" int zkw_decommit_sorter_prepare(zkw_ctx* ctx, const zkw_decommit_quer
     if (n == 0) return fail(ZKW_ERR_INVALID, "VM should have made some code decommits (sort_decommit_requests.rs:38-41)");
     if (n >= (1ull << 32)) return fail(ZKW_ERR_INVALID, "too many requests");
     HIP_TRY(hipSetDevice(ctx->device));
-    zkw_decommit_witness* w = new zkw_decommit_witness();
-    w->ctx = ctx;
+    Building<zkw_decommit_witness> w(ctx);
     w->n = n;
     w->capacity = capacity;
     w->n_instances = (n + capacity - 1) / capacity;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->sorted_q, n * sizeof(zkw_decommit_query));
-    alloc((void**)&w->dedup_q, n * sizeof(zkw_decommit_query));
-    alloc((void**)&w->unsorted_enc, n * 64); alloc((void**)&w->sorted_enc, n * 64); alloc((void**)&w->dedup_enc, n * 64);
-    alloc((void**)&w->unsorted_tails, n * 96); alloc((void**)&w->sorted_tails, n * 96); alloc((void**)&w->dedup_tails, n * 96);
-    alloc((void**)&w->challenges, 18 * 8); alloc((void**)&w->lhs_z, n * 16); alloc((void**)&w->rhs_z, n * 16);
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_decommit_sorter_instance));
-    alloc((void**)&w->compact_forms, w->n_instances * COMPACT_FORM_LEN * 8);
-    alloc((void**)&w->public_inputs, w->n_instances * 32);
-    if (e != hipSuccess) {
-        w->release();
-        delete w;
-        return fail(ZKW_ERR_OOM, "zkw_decommit_sorter_prepare: hipMalloc failed: %s", hipGetErrorString(e));
-    }
+    w.alloc(&w->sorted_q, n * sizeof(zkw_decommit_query));
+    w.alloc(&w->dedup_q, n * sizeof(zkw_decommit_query));
+    w.alloc(&w->unsorted_enc, n * 64); w.alloc(&w->sorted_enc, n * 64); w.alloc(&w->dedup_enc, n * 64);
+    w.alloc(&w->unsorted_tails, n * 96); w.alloc(&w->sorted_tails, n * 96); w.alloc(&w->dedup_tails, n * 96);
+    w.alloc(&w->challenges, 18 * 8); w.alloc(&w->lhs_z, n * 16); w.alloc(&w->rhs_z, n * 16);
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_decommit_sorter_instance));
+    w.alloc(&w->compact_forms, w->n_instances * COMPACT_FORM_LEN * 8);
+    w.alloc(&w->public_inputs, w->n_instances * 32);
+    ZKW_TRY(w.oom("zkw_decommit_sorter_prepare"));
     memset(&w->dedup_in, 0, sizeof w->dedup_in);
     if (dedup_in) w->dedup_in = *dedup_in;
     const zkw_decommit_query* d_q = nullptr;
-    int rc = ctx->in("dec_q", q, n, &d_q);
-    if (rc == ZKW_OK) rc = decommit_prepare(ctx, w, d_q);
-    if (rc != ZKW_OK) {
-        w->release();
-        delete w;
-        return rc;
-    }
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(ctx->in("dec_q", q, n, &d_q));
+    ZKW_TRY(decommit_prepare(ctx, w.w, d_q));
+    w.commit(out);
     return ZKW_OK;
 }
 
@@ -226,6 +213,18 @@ extern "C" int zkw_decommit_witness_get(const zkw_decommit_witness* w, int what,
     return witness_get<dec_array>(w, what, dst, dst_bytes, "zkw_decommit_witness_get", ZKW_DEC_PUBLIC_INPUTS, true);
 }
 extern "C" void zkw_decommit_witness_free(zkw_decommit_witness* w) { witness_free(w); }
+
+// The one dummy instance of an EMPTY queue (events and storage sorters). The circuit derives its challenges whatever the queue holds (the
+// trace's closed-form section does): those of two empty queues.
+template <class Inst>
+static int empty_queue_instance(zkw_ctx* ctx, const Inst& inst, Inst* d_instances, u64* d_challenges) {
+    u64* d_zero = nullptr;
+    ZKW_TRY(ctx->scratch_t<u64>("empty_queue_tail", 4, &d_zero));
+    HIP_TRY(hipMemcpy(d_instances, &inst, sizeof inst, hipMemcpyHostToDevice));
+    HIP_TRY(ctx->memset_async(d_zero, 0, 4 * sizeof(u64)));
+    std::vector<FsJob> fs(1, FsJob{d_zero, d_zero, 0u, 0u, d_challenges});
+    return dev_fs(ctx, fs, 4, 21);
+}
 
 // ------------------------------------------------------------------------------------------------ events sorter
 struct zkw_events_witness {
@@ -306,32 +305,24 @@ extern "C" int zkw_events_sorter_build(zkw_ctx* ctx, const zkw_log_query* q, siz
     if (!ctx || !out || capacity == 0 || (n && !q)) return fail(ZKW_ERR_INVALID, "zkw_events_sorter_build: bad argument");
     if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "too many log queries");
     HIP_TRY(hipSetDevice(ctx->device));
-    zkw_events_witness* w = new zkw_events_witness();
-    w->ctx = ctx;
+    Building<zkw_events_witness> w(ctx);
     w->n = n;
     w->capacity = capacity;
     w->n_instances = n ? (n + capacity - 1) / capacity : 1;
     const size_t m = n ? n : 1;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->sorted_q, m * sizeof(zkw_log_query));
-    alloc((void**)&w->result_q, m * sizeof(zkw_log_query));
-    alloc((void**)&w->enc_all, 3 * m * 160);
-    alloc((void**)&w->tails_all, 5 * m * 32);
-    alloc((void**)&w->challenges, 42 * 8);
-    alloc((void**)&w->lhs_z, m * 16);
-    alloc((void**)&w->rhs_z, m * 16);
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_events_sorter_instance));
-    if (e != hipSuccess) {
-        w->release();
-        delete w;
-        return fail(ZKW_ERR_OOM, "zkw_events_sorter_build: hipMalloc failed: %s", hipGetErrorString(e));
-    }
+    w.alloc(&w->sorted_q, m * sizeof(zkw_log_query));
+    w.alloc(&w->result_q, m * sizeof(zkw_log_query));
+    w.alloc(&w->enc_all, 3 * m * 160);
+    w.alloc(&w->tails_all, 5 * m * 32);
+    w.alloc(&w->challenges, 42 * 8);
+    w.alloc(&w->lhs_z, m * 16);
+    w.alloc(&w->rhs_z, m * 16);
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_events_sorter_instance));
+    ZKW_TRY(w.oom("zkw_events_sorter_build"));
     zkw_queue_state4 rin;
     memset(&rin, 0, sizeof rin);
     if (result_in) rin = *result_in;
     w->result_in = rin;
-    int rc = ZKW_OK;
     if (n == 0) {  // events_sort_dedup.rs:27-76: one dummy instance, accumulators forced to ONE
         zkw_events_sorter_instance inst;
         memset(&inst, 0, sizeof inst);
@@ -340,30 +331,15 @@ extern "C" int zkw_events_sorter_build(zkw_ctx* ctx, const zkw_log_query* q, siz
             inst.hidden_fsm_input.lhs_accumulator[r] = inst.hidden_fsm_input.rhs_accumulator[r] = 1;
             inst.hidden_fsm_output.lhs_accumulator[r] = inst.hidden_fsm_output.rhs_accumulator[r] = 1;
         }
-        // the circuit derives its challenges whatever the queue holds (the trace's closed-form section does): those of two empty queues
-        u64* d_zero = nullptr;
-        rc = ctx->scratch_t<u64>("empty_queue_tail", 4, &d_zero);
-        if (rc == ZKW_OK && (hipMemcpy(w->instances, &inst, sizeof inst, hipMemcpyHostToDevice) != hipSuccess ||
-                             ctx->memset_async(d_zero, 0, 4 * sizeof(u64)) != hipSuccess))
-            rc = fail(ZKW_ERR_HIP, "copy failed");
-        if (rc == ZKW_OK) {
-            std::vector<FsJob> fs(1, FsJob{d_zero, d_zero, 0u, 0u, w->challenges});
-            rc = dev_fs(ctx, fs, 4, 21);
-        }
+        ZKW_TRY(empty_queue_instance(ctx, inst, w->instances, w->challenges));
     } else {
         const zkw_log_query* d_q = nullptr;
-        rc = ctx->in("evt_q", q, n, &d_q);
-        if (rc == ZKW_OK) rc = events_run(ctx, w, d_q, rin);
+        ZKW_TRY(ctx->in("evt_q", q, n, &d_q));
+        ZKW_TRY(events_run(ctx, w.w, d_q, rin));
     }
-    if (rc == ZKW_OK) rc = closed_form_public_inputs<CfEventsSorter>(ctx, w->instances, w->n_instances, &w->cf_pi);
-    if (rc == ZKW_OK) rc = ctx->sync_if_host();
-    if (rc != ZKW_OK) {
-        w->release();
-        delete w;
-        return rc;
-    }
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(closed_form_public_inputs<CfEventsSorter>(ctx, w->instances, w->n_instances, &w->cf_pi));
+    ZKW_TRY(ctx->sync_if_host());
+    w.commit(out);
     return ZKW_OK;
 }
 
@@ -461,53 +437,38 @@ extern "C" int zkw_log_demux_build(zkw_ctx* ctx, const zkw_log_query* q, size_t 
     if (!ctx || !out || capacity == 0 || (n && !q)) return fail(ZKW_ERR_INVALID, "zkw_log_demux_build: bad argument");
     if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "too many log queries");
     HIP_TRY(hipSetDevice(ctx->device));
-    zkw_demux_witness* w = new zkw_demux_witness();
-    w->ctx = ctx;
+    Building<zkw_demux_witness> w(ctx);
     w->n = n;
     w->capacity = capacity;
     w->n_instances = n ? (n + capacity - 1) / capacity : 1;
     const size_t m = n ? n : 1;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->out_q, m * sizeof(zkw_log_query));
-    alloc((void**)&w->enc_all, 2 * m * 160);
-    alloc((void**)&w->tails_all, 4 * m * 32);
-    alloc((void**)&w->d_offsets, 8 * 8);
-    alloc((void**)&w->route_count, 6 * m * sizeof(u32));
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_log_demux_instance));
-    if (e != hipSuccess) {
-        w->release();
-        delete w;
-        return fail(ZKW_ERR_OOM, "zkw_log_demux_build: hipMalloc failed: %s", hipGetErrorString(e));
-    }
+    w.alloc(&w->out_q, m * sizeof(zkw_log_query));
+    w.alloc(&w->enc_all, 2 * m * 160);
+    w.alloc(&w->tails_all, 4 * m * 32);
+    w.alloc(&w->d_offsets, 8 * 8);
+    w.alloc(&w->route_count, 6 * m * sizeof(u32));
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_log_demux_instance));
+    ZKW_TRY(w.oom("zkw_log_demux_build"));
     zkw_demux_params p = ZKW_DEMUX_PARAMS_DEFAULT;
     if (params) p = *params;
     {
         const zkw_demux_params d = ZKW_DEMUX_PARAMS_DEFAULT;
         w->default_params = memcmp(&p, &d, sizeof d) == 0;
     }
-    int rc = ZKW_OK;
     if (n == 0) {  // log_demux.rs:51-107
         zkw_log_demux_instance inst;
         memset(&inst, 0, sizeof inst);
         inst.start_flag = inst.completion_flag = 1;
-        if (hipMemcpy(w->instances, &inst, sizeof inst, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(w->d_offsets, 0, 64) != hipSuccess)
-            rc = fail(ZKW_ERR_HIP, "copy failed");
+        HIP_TRY(hipMemcpy(w->instances, &inst, sizeof inst, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(w->d_offsets, 0, 64));
     } else {
         const zkw_log_query* d_q = nullptr;
-        rc = ctx->in("dmx_q", q, n, &d_q);
-        if (rc == ZKW_OK) rc = demux_run(ctx, w, d_q, p);
+        ZKW_TRY(ctx->in("dmx_q", q, n, &d_q));
+        ZKW_TRY(demux_run(ctx, w.w, d_q, p));
     }
-    if (rc == ZKW_OK) rc = closed_form_public_inputs<CfLogDemux>(ctx, w->instances, w->n_instances, &w->cf_pi);
-    if (rc == ZKW_OK) rc = ctx->sync_if_host();
-    if (rc != ZKW_OK) {
-        w->release();
-        delete w;
-        return rc;
-    }
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(closed_form_public_inputs<CfLogDemux>(ctx, w->instances, w->n_instances, &w->cf_pi));
+    ZKW_TRY(ctx->sync_if_host());
+    w.commit(out);
     return ZKW_OK;
 }
 
@@ -650,61 +611,38 @@ extern "C" int zkw_storage_sorter_build(zkw_ctx* ctx, const zkw_log_query* q, si
     if (!ctx || !out || capacity == 0 || (n && !q)) return fail(ZKW_ERR_INVALID, "zkw_storage_sorter_build: bad argument");
     if (n >= (1ull << 31)) return fail(ZKW_ERR_INVALID, "too many log queries");
     HIP_TRY(hipSetDevice(ctx->device));
-    zkw_storage_witness* w = new zkw_storage_witness();
-    w->ctx = ctx;
+    Building<zkw_storage_witness> w(ctx);
     w->n = n;
     w->capacity = capacity;
     w->n_instances = n ? (n + capacity - 1) / capacity : 1;
     const size_t m = n ? n : 1;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
-    alloc((void**)&w->sorted_q, m * sizeof(zkw_log_query));
-    alloc((void**)&w->result_q, m * sizeof(zkw_log_query));
-    alloc((void**)&w->sorted_ext, m * 4);
-    alloc((void**)&w->enc_all, 3 * m * 160);
-    alloc((void**)&w->lhs_enc, m * 160);
-    alloc((void**)&w->tails_all, 5 * m * 32);
-    alloc((void**)&w->challenges, 42 * 8);
-    alloc((void**)&w->lhs_z, m * 16);
-    alloc((void**)&w->rhs_z, m * 16);
-    alloc((void**)&w->scans, 4 * m * sizeof(u32));
-    alloc((void**)&w->instances, w->n_instances * sizeof(zkw_storage_sorter_instance));
-    if (e != hipSuccess) {
-        w->release();
-        delete w;
-        return fail(ZKW_ERR_OOM, "zkw_storage_sorter_build: hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    int rc = ZKW_OK;
+    w.alloc(&w->sorted_q, m * sizeof(zkw_log_query));
+    w.alloc(&w->result_q, m * sizeof(zkw_log_query));
+    w.alloc(&w->sorted_ext, m * 4);
+    w.alloc(&w->enc_all, 3 * m * 160);
+    w.alloc(&w->lhs_enc, m * 160);
+    w.alloc(&w->tails_all, 5 * m * 32);
+    w.alloc(&w->challenges, 42 * 8);
+    w.alloc(&w->lhs_z, m * 16);
+    w.alloc(&w->rhs_z, m * 16);
+    w.alloc(&w->scans, 4 * m * sizeof(u32));
+    w.alloc(&w->instances, w->n_instances * sizeof(zkw_storage_sorter_instance));
+    ZKW_TRY(w.oom("zkw_storage_sorter_build"));
     if (n == 0) {  // storage_sort_dedup.rs:23-70
         zkw_storage_sorter_instance inst;
         memset(&inst, 0, sizeof inst);
         inst.start_flag = inst.completion_flag = 1;
         for (int r = 0; r < 2; r++) inst.hidden_fsm_output.lhs_accumulator[r] = inst.hidden_fsm_output.rhs_accumulator[r] = 1;
         inst.hidden_fsm_output.cycle_idx = 4;
-        // the circuit derives its challenges whatever the queue holds (the trace's closed-form section does): those of two empty queues
-        u64* d_zero = nullptr;
-        rc = ctx->scratch_t<u64>("empty_queue_tail", 4, &d_zero);
-        if (rc == ZKW_OK && (hipMemcpy(w->instances, &inst, sizeof inst, hipMemcpyHostToDevice) != hipSuccess ||
-                             ctx->memset_async(d_zero, 0, 4 * sizeof(u64)) != hipSuccess))
-            rc = fail(ZKW_ERR_HIP, "copy failed");
-        if (rc == ZKW_OK) {
-            std::vector<FsJob> fs(1, FsJob{d_zero, d_zero, 0u, 0u, w->challenges});
-            rc = dev_fs(ctx, fs, 4, 21);
-        }
+        ZKW_TRY(empty_queue_instance(ctx, inst, w->instances, w->challenges));
     } else {
         const zkw_log_query* d_q = nullptr;
-        rc = ctx->in("sto_q", q, n, &d_q);
-        if (rc == ZKW_OK) rc = storage_run(ctx, w, d_q);
+        ZKW_TRY(ctx->in("sto_q", q, n, &d_q));
+        ZKW_TRY(storage_run(ctx, w.w, d_q));
     }
-    if (rc == ZKW_OK) rc = closed_form_public_inputs<CfStorageSorter>(ctx, w->instances, w->n_instances, &w->cf_pi);
-    if (rc == ZKW_OK) rc = ctx->sync_if_host();
-    if (rc != ZKW_OK) {
-        w->release();
-        delete w;
-        return rc;
-    }
-    ctx_retain(ctx);
-    *out = w;
+    ZKW_TRY(closed_form_public_inputs<CfStorageSorter>(ctx, w->instances, w->n_instances, &w->cf_pi));
+    ZKW_TRY(ctx->sync_if_host());
+    w.commit(out);
     return ZKW_OK;
 }
 

@@ -45,47 +45,31 @@ extern "C" int zkw_storage_tree_create(zkw_ctx* ctx, size_t capacity_leaves, zkw
     if (ctx->batch) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create: the context belongs to a batch of blocks");
     HIP_TRY(hipSetDevice(ctx->device));
     *out = nullptr;
-    zkw_storage_tree* t = new zkw_storage_tree();
-    t->ctx = ctx;
+    Building<zkw_storage_tree> t(ctx);
     t->cap = capacity_leaves;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = dev_malloc(p, bytes + 64); };
     for (int s = 0; s < 2; s++) {
-        alloc(&t->keys[s], t->cap * 32);
-        alloc(&t->index[s], t->cap * 8);
-        alloc(&t->values[s], t->cap * 32);
+        t.alloc(&t->keys[s], t->cap * 32);
+        t.alloc(&t->index[s], t->cap * 8);
+        t.alloc(&t->values[s], t->cap * 32);
     }
-    alloc(&t->nodes, t->cap * (size_t)ST_DEPTH * 32);
-    alloc(&t->empty, (ST_DEPTH + 1) * 32);
-    alloc(&t->d, t->cap * 4);
-    alloc(&t->nxt, t->cap * 4);
-    alloc(&t->root_dev, 32);
-    auto bail = [&](int rc) { t->release(); delete t; return rc; };
-    if (e != hipSuccess) {
+    t.alloc(&t->nodes, t->cap * (size_t)ST_DEPTH * 32);
+    t.alloc(&t->empty, (ST_DEPTH + 1) * 32);
+    t.alloc(&t->d, t->cap * 4);
+    t.alloc(&t->nxt, t->cap * 4);
+    t.alloc(&t->root_dev, 32);
+    if (t.err != hipSuccess) {
         (void)hipGetLastError();
-        return bail(fail(ZKW_ERR_OOM, "zkw_storage_tree_create: %zu leaves need %zu bytes of device memory: %s", capacity_leaves,
-                         capacity_leaves * ST_BYTES_PER_LEAF, hipGetErrorString(e)));
+        return fail(ZKW_ERR_OOM, "zkw_storage_tree_create: %zu leaves need %zu bytes of device memory: %s", capacity_leaves,
+                    capacity_leaves * ST_BYTES_PER_LEAF, hipGetErrorString(t.err));
     }
-    int rc = [&]() -> int {
-        ZKW_LAUNCH(ctx, k_st_empty, 1, 64, t->empty);
-        return ctx->read_small(t->empty_root, t->empty + 8 * ST_DEPTH, 32);
-    }();
-    if (rc != ZKW_OK) return bail(rc);
+    ZKW_LAUNCH(ctx, k_st_empty, 1, 64, t->empty);
+    ZKW_TRY(ctx->read_small(t->empty_root, t->empty + 8 * ST_DEPTH, 32));
     memcpy(t->root, t->empty_root, 32);
-    ctx_retain(ctx);
-    *out = t;
+    t.commit(out);
     return ZKW_OK;
 }
 
-extern "C" void zkw_storage_tree_free(zkw_storage_tree* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->ctx->device);
-    (void)t->ctx->sync_stream();
-    t->release();
-    zkw_ctx* owner = t->ctx;
-    delete t;
-    ctx_release(owner);
-}
+extern "C" void zkw_storage_tree_free(zkw_storage_tree* t) { witness_free(t); }
 
 extern "C" int zkw_storage_tree_root(const zkw_storage_tree* t, uint8_t out[32]) {
     if (!t || !out) return fail(ZKW_ERR_INVALID, "zkw_storage_tree_root: null argument");
@@ -283,30 +267,19 @@ extern "C" int zkw_storage_tree_apply_queries(zkw_storage_tree* t, const zkw_log
 }
 
 // ------------------------------------------------------------------------------------------------ witness trees
-// an empty table for up to `entries` entries on ctx (not yet retained: the caller does that once the table is complete)
-static int sw_alloc(zkw_ctx* ctx, size_t entries, const char* who, zkw_storage_tree** out) {
-    zkw_storage_tree* t = new zkw_storage_tree();
-    t->ctx = ctx;
+// `t` becomes an empty table for up to `entries` entries (the caller commits it once the table is complete)
+static int sw_alloc(Building<zkw_storage_tree>& t, size_t entries, const char* who) {
     t->witness = true;
     t->cap = entries;
-    hipError_t e = dev_malloc(&t->keys[0], entries * 32 + 64);
-    if (e == hipSuccess) e = dev_malloc(&t->index[0], entries * 8 + 64);
-    if (e == hipSuccess) e = dev_malloc(&t->values[0], entries * 32 + 64);
-    if (e == hipSuccess) e = dev_malloc(&t->paths, entries * (size_t)ST_DEPTH * 32 + 64);
-    if (e != hipSuccess) {
+    t.alloc(&t->keys[0], entries * 32);
+    t.alloc(&t->index[0], entries * 8);
+    t.alloc(&t->values[0], entries * 32);
+    t.alloc(&t->paths, entries * (size_t)ST_DEPTH * 32);
+    if (t.err != hipSuccess) {
         (void)hipGetLastError();
-        t->release();
-        delete t;
-        return fail(ZKW_ERR_OOM, "%s: %zu entries need %zu bytes of device memory: %s", who, entries, entries * (size_t)(ST_DEPTH * 32 + 72), hipGetErrorString(e));
+        return fail(ZKW_ERR_OOM, "%s: %zu entries need %zu bytes of device memory: %s", who, entries, entries * (size_t)(ST_DEPTH * 32 + 72), hipGetErrorString(t.err));
     }
-    *out = t;
     return ZKW_OK;
-}
-static int sw_drop(zkw_storage_tree* t, int rc) {
-    (void)t->ctx->sync_stream();  // nothing queued may still write the table
-    t->release();
-    delete t;
-    return rc;
 }
 
 static const char* sw_reason(u32 status) {
@@ -335,15 +308,14 @@ extern "C" int zkw_storage_tree_create_witness(zkw_ctx* ctx, const uint8_t* keys
     u32 *status = nullptr, *meta = nullptr;  // meta[0] = the first bad entry, meta[1] = entries with a nonzero index
     ZKW_TRY(ctx->scratch_t<u32>("sw_status", n + 1, &status));
     ZKW_TRY(ctx->scratch_t<u32>("sw_meta", 2, &meta));
-    zkw_storage_tree* t = nullptr;
-    ZKW_TRY(sw_alloc(ctx, n, "zkw_storage_tree_create_witness", &t));
+    Building<zkw_storage_tree> t(ctx);
+    ZKW_TRY(sw_alloc(t, n, "zkw_storage_tree_create_witness"));
     memcpy(t->root, root, 32);
     t->next_index = next_enumeration_index;
     u32 h_meta[2] = {~0u, 0};
-    int rc = [&]() -> int {
-        HIP_TRY(ctx->memset_async(meta, 0xFF, sizeof(u32)));
-        HIP_TRY(ctx->memset_async(meta + 1, 0, sizeof(u32)));
-        if (n == 0) return ZKW_OK;
+    HIP_TRY(ctx->memset_async(meta, 0xFF, sizeof(u32)));
+    HIP_TRY(ctx->memset_async(meta + 1, 0, sizeof(u32)));
+    if (n) {
         SwEntries e{reinterpret_cast<const u32*>(d_k), d_i, reinterpret_cast<const u32*>(d_v), reinterpret_cast<const u32*>(d_p), (u64)n, next_enumeration_index, {}};
         memcpy(e.root, root, 32);
         ZKW_LAUNCH(ctx, k_sw_verify, blocks_for(n, 64), 64, e, status, meta);
@@ -351,18 +323,15 @@ extern "C" int zkw_storage_tree_create_witness(zkw_ctx* ctx, const uint8_t* keys
         ZKW_TRY(st_sort_merged(ctx, st_keys_only(e.keys, n), n, &perm));
         ZKW_LAUNCH(ctx, k_sw_gather, n, ST_DEPTH, e, perm, SwTable{t->keys[0], t->index[0], t->values[0], t->paths}, status, meta);
         ZKW_LAUNCH(ctx, k_sw_count, blocks_for(n, 256), 256, (const u64*)t->index[0], (u64)n, meta + 1);
-        return ctx->read_small(h_meta, meta, sizeof h_meta);
-    }();
-    if (rc != ZKW_OK) return sw_drop(t, rc);
+        ZKW_TRY(ctx->read_small(h_meta, meta, sizeof h_meta));
+    }
     if (h_meta[0] != ~0u) {
         u32 st = 0;
-        rc = ctx->read_small(&st, status + h_meta[0], sizeof st);
-        if (rc != ZKW_OK) return sw_drop(t, rc);
-        return sw_drop(t, fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: entry %u is not a proof for this root: %s", h_meta[0], sw_reason(st)));
+        ZKW_TRY(ctx->read_small(&st, status + h_meta[0], sizeof st));
+        return fail(ZKW_ERR_INVALID, "zkw_storage_tree_create_witness: entry %u is not a proof for this root: %s", h_meta[0], sw_reason(st));
     }
     t->n = h_meta[1];
-    ctx_retain(ctx);
-    *out = t;
+    t.commit(out);
     return ZKW_OK;
 }
 
@@ -386,13 +355,12 @@ extern "C" int zkw_storage_tree_extract_witness(const zkw_storage_tree* tree, zk
         ZKW_TRY(flag_prefix(ctx, "k_st_heads", StHeadFlag{st_keys_only(d_keys, n), perm}, n, heads));
         ZKW_TRY(ctx->read_small(&unique, heads + n, sizeof unique));
     }
-    zkw_storage_tree* t = nullptr;
-    ZKW_TRY(sw_alloc(ctx, unique, "zkw_storage_tree_extract_witness", &t));
+    Building<zkw_storage_tree> t(ctx);
+    ZKW_TRY(sw_alloc(t, unique, "zkw_storage_tree_extract_witness"));
     memcpy(t->root, tree->root, 32);
     t->next_index = tree->next_index;
     u32 count = 0;
-    int rc = [&]() -> int {
-        if (unique == 0) return ZKW_OK;
+    if (unique) {
         u32* d_count = nullptr;
         ZKW_TRY(ctx->scratch_t<u32>("sw_meta", 2, &d_count));
         HIP_TRY(ctx->memset_async(d_count, 0, sizeof(u32)));
@@ -400,12 +368,10 @@ extern "C" int zkw_storage_tree_extract_witness(const zkw_storage_tree* tree, zk
         // the full tree's answers straight into the table
         ZKW_TRY(st_query(ctx, tree, StQuery{nullptr, t->keys[0], t->index[0], t->values[0], t->paths}, unique));
         ZKW_LAUNCH(ctx, k_sw_count, blocks_for(unique, 256), 256, (const u64*)t->index[0], (u64)unique, d_count);
-        return ctx->read_small(&count, d_count, sizeof count);
-    }();
-    if (rc != ZKW_OK) return sw_drop(t, rc);
+        ZKW_TRY(ctx->read_small(&count, d_count, sizeof count));
+    }
     t->n = count;
-    ctx_retain(ctx);
-    *out = t;
+    t.commit(out);
     return ZKW_OK;
 }
 
@@ -429,35 +395,31 @@ static int sw_advance(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx
     ZKW_TRY(ctx->scratch_t<u32>("swa_nxt", bound, &nxt));
     ZKW_TRY(ctx->scratch_t<u32>("swa_up", bound * (size_t)(ST_DEPTH + 1) * 8, &up));
     u32* last = meta + SWA_META_WORDS;
-    zkw_storage_tree* t = nullptr;
-    ZKW_TRY(sw_alloc(ctx, entries, who, &t));
+    Building<zkw_storage_tree> t(ctx);
+    ZKW_TRY(sw_alloc(t, entries, who));
     u32 h_meta[SWA_META_WORDS] = {};
-    int rc = [&]() -> int {
-        if (entries) HIP_TRY(ctx->memset_async(first, 0xFF, entries * sizeof(u32)));
-        HIP_TRY(ctx->memset_async(meta, 0, (SWA_META_WORDS + entries) * sizeof(u32)));
-        const SwView tv = src->table();
-        const SwaFold f{tv, wlist, up, d, nxt, meta, (u64)bound};
-        ZKW_LAUNCH(ctx, k_swa_locate, blocks_for(n, 64), 64, tv, wr, ent, first, last, meta);
-        ZKW_TRY(flag_prefix(ctx, "k_swa_new_rank", SwaNewFlag{ent, first, tv.index}, n, new_rank));
-        ZKW_TRY(flag_prefix(ctx, "k_swa_wrank", SwaWrittenFlag{first}, entries, wrank));
-        ZKW_LAUNCH(ctx, k_swa_compact, blocks_for(entries, 256), 256, (const u32*)first, (const u32*)wrank, (const u32*)new_rank, (u64)entries, (u64)n, wlist, meta);
-        ZKW_LAUNCH(ctx, k_swa_leaves, blocks_for(bound, 64), 64, f, wr, (const u32*)first, (const u32*)last, (const u32*)new_rank, src->next_index, widx, wval);
-        if (bound <= ST_PERSISTENT_MAX) {
-            ZKW_LAUNCH(ctx, k_swa_fold, bound ? 1 : 0, ST_PERSISTENT_THREADS, f);  // (no writes: nothing is launched, the span is still recorded)
-        } else {
-            for (int L = 0; L < ST_DEPTH; L++) ZKW_LAUNCH(ctx, k_swa_level, blocks_for(bound, 64), 64, f, L);
-        }
-        ZKW_LAUNCH(ctx, k_swa_paths, entries, ST_DEPTH, f, (const u32*)first, (const u32*)wrank, (const u64*)widx, (const u32*)wval, SwTable{t->keys[0], t->index[0], t->values[0], t->paths});
-        return ctx->read_small(h_meta, meta, sizeof h_meta);
-    }();
-    if (rc != ZKW_OK) return sw_drop(t, rc);
+    if (entries) HIP_TRY(ctx->memset_async(first, 0xFF, entries * sizeof(u32)));
+    HIP_TRY(ctx->memset_async(meta, 0, (SWA_META_WORDS + entries) * sizeof(u32)));
+    const SwView tv = src->table();
+    const SwaFold f{tv, wlist, up, d, nxt, meta, (u64)bound};
+    ZKW_LAUNCH(ctx, k_swa_locate, blocks_for(n, 64), 64, tv, wr, ent, first, last, meta);
+    ZKW_TRY(flag_prefix(ctx, "k_swa_new_rank", SwaNewFlag{ent, first, tv.index}, n, new_rank));
+    ZKW_TRY(flag_prefix(ctx, "k_swa_wrank", SwaWrittenFlag{first}, entries, wrank));
+    ZKW_LAUNCH(ctx, k_swa_compact, blocks_for(entries, 256), 256, (const u32*)first, (const u32*)wrank, (const u32*)new_rank, (u64)entries, (u64)n, wlist, meta);
+    ZKW_LAUNCH(ctx, k_swa_leaves, blocks_for(bound, 64), 64, f, wr, (const u32*)first, (const u32*)last, (const u32*)new_rank, src->next_index, widx, wval);
+    if (bound <= ST_PERSISTENT_MAX) {
+        ZKW_LAUNCH(ctx, k_swa_fold, bound ? 1 : 0, ST_PERSISTENT_THREADS, f);  // (no writes: nothing is launched, the span is still recorded)
+    } else {
+        for (int L = 0; L < ST_DEPTH; L++) ZKW_LAUNCH(ctx, k_swa_level, blocks_for(bound, 64), 64, f, L);
+    }
+    ZKW_LAUNCH(ctx, k_swa_paths, entries, ST_DEPTH, f, (const u32*)first, (const u32*)wrank, (const u64*)widx, (const u32*)wval, SwTable{t->keys[0], t->index[0], t->values[0], t->paths});
+    ZKW_TRY(ctx->read_small(h_meta, meta, sizeof h_meta));
     if (h_meta[SWA_META_MISSING])
-        return sw_drop(t, fail(ZKW_ERR_INVALID, "%s: the key written at position %zu is not in the witness tree", who, n - h_meta[SWA_META_MISSING]));
+        return fail(ZKW_ERR_INVALID, "%s: the key written at position %zu is not in the witness tree", who, n - h_meta[SWA_META_MISSING]);
     memcpy(t->root, h_meta[SWA_META_NW] ? reinterpret_cast<const uint8_t*>(h_meta + SWA_META_ROOT) : src->root, 32);
     t->n = src->n + h_meta[SWA_META_NEW];
     t->next_index = src->next_index + h_meta[SWA_META_NEW];
-    ctx_retain(ctx);
-    *out = t;
+    t.commit(out);
     return ZKW_OK;
 }
 
@@ -545,62 +507,44 @@ static int sw_chain(const char* who, const zkw_storage_tree* src, zkw_ctx* ctx, 
     }
     const u32 *h_tbase = h_hdr.data() + SWC_HDR_WORDS, *h_wbase = h_tbase + K + 1;
     // the K tables and the working copy
-    std::vector<zkw_storage_tree*> made;
-    auto drop_all = [&](int rc) {
-        (void)ctx->sync_stream();  // nothing queued may still write a table
-        for (zkw_storage_tree* t : made) { t->release(); delete t; }
-        return rc;
-    };
+    std::vector<Building<zkw_storage_tree>> made;
+    made.reserve(K + 1);
     for (size_t k = 0; k <= K; k++) {
-        zkw_storage_tree* t = nullptr;
-        const int rc = sw_alloc(ctx, k < K ? h_tbase[k + 1] - h_tbase[k] : E, who, &t);
-        if (rc != ZKW_OK) return drop_all(rc);
-        made.push_back(t);
+        made.emplace_back(ctx);
+        ZKW_TRY(sw_alloc(made[k], k < K ? h_tbase[k + 1] - h_tbase[k] : E, who));
     }
-    zkw_storage_tree* work = made[K];
+    Building<zkw_storage_tree>& work = made[K];
     std::vector<u32> h_fin(fin_words);
-    int rc = [&]() -> int {
-        std::vector<SwTable> tabs(K);
-        for (size_t k = 0; k < K; k++) tabs[k] = SwTable{made[k]->keys[0], made[k]->index[0], made[k]->values[0], made[k]->paths};
-        SwTable* d_tabs = nullptr;
-        ZKW_TRY(ctx->upload("swc_tables", tabs, &d_tabs));
-        c.outs = d_tabs;
-        c.work = SwTable{work->keys[0], work->index[0], work->values[0], work->paths};
-        if (E) {
-            HIP_TRY(ctx->copy_async(work->keys[0], tv.keys, E * 32, hipMemcpyDeviceToDevice));
-            Prof _p(ctx, "swc_copy_paths");
-            HIP_TRY(ctx->copy_async(work->paths, tv.paths, E * (size_t)ST_DEPTH * 32, hipMemcpyDeviceToDevice));
-        }
-        ZKW_LAUNCH(ctx, k_swc_walk, blocks_for(E, 64), 64, c, wr, tv.index, tv.values, (const u32*)last, (const u32*)cfirst, (const u32*)new_rank, src->next_index);
-        const unsigned fold_wgs = blocks_for(h_wbase[K], 256), all_wgs = fold_wgs + blocks_for(KE, 256);
-        if (h_tbase[K])  // (a chain without a query captures and folds nothing)
-            for (int s = 0; s < ST_DEPTH + (int)K - 1; s++) ZKW_LAUNCH(ctx, k_swc_step, all_wgs, 256, c, fold_wgs, s);
-        return ctx->read_small(h_fin.data(), fin, fin_words * sizeof(u32));
-    }();
-    if (rc != ZKW_OK) return drop_all(rc);
+    std::vector<SwTable> tabs(K);
+    for (size_t k = 0; k < K; k++) tabs[k] = SwTable{made[k]->keys[0], made[k]->index[0], made[k]->values[0], made[k]->paths};
+    SwTable* d_tabs = nullptr;
+    ZKW_TRY(ctx->upload("swc_tables", tabs, &d_tabs));
+    c.outs = d_tabs;
+    c.work = SwTable{work->keys[0], work->index[0], work->values[0], work->paths};
+    if (E) {
+        HIP_TRY(ctx->copy_async(work->keys[0], tv.keys, E * 32, hipMemcpyDeviceToDevice));
+        Prof _p(ctx, "swc_copy_paths");
+        HIP_TRY(ctx->copy_async(work->paths, tv.paths, E * (size_t)ST_DEPTH * 32, hipMemcpyDeviceToDevice));
+    }
+    ZKW_LAUNCH(ctx, k_swc_walk, blocks_for(E, 64), 64, c, wr, tv.index, tv.values, (const u32*)last, (const u32*)cfirst, (const u32*)new_rank, src->next_index);
+    const unsigned fold_wgs = blocks_for(h_wbase[K], 256), all_wgs = fold_wgs + blocks_for(KE, 256);
+    if (h_tbase[K])  // (a chain without a query captures and folds nothing)
+        for (int s = 0; s < ST_DEPTH + (int)K - 1; s++) ZKW_LAUNCH(ctx, k_swc_step, all_wgs, 256, c, fold_wgs, s);
+    ZKW_TRY(ctx->read_small(h_fin.data(), fin, fin_words * sizeof(u32)));
     // roots and indices are carried over the blocks: a block without writes leaves the state as it is
     uint8_t root[32];
     memcpy(root, src->root, 32);
     u64 next = src->next_index;
     for (size_t k = 0; k <= K; k++) {
-        zkw_storage_tree* t = made[k];
+        Building<zkw_storage_tree>& t = made[k];
         memcpy(t->root, root, 32);
         t->next_index = next;
         t->n = h_fin[9 * K + k];
         if (k < K && h_wbase[k + 1] != h_wbase[k]) memcpy(root, h_fin.data() + 8 * k, 32);
         if (k < K) next += h_fin[8 * K + k];
     }
-    if (final_state) {
-        *final_state = work;
-        ctx_retain(ctx);
-    } else {
-        work->release();  // (the readback has synchronised the stream)
-        delete work;
-    }
-    for (size_t k = 0; k < K; k++) {
-        out[k] = made[k];
-        ctx_retain(ctx);
-    }
+    if (final_state) work.commit(final_state);  // (else the working copy goes when `made` does)
+    for (size_t k = 0; k < K; k++) made[k].commit(&out[k]);
     return ZKW_OK;
 }
 
