@@ -250,13 +250,20 @@ static __device__ __forceinline__ void k_kzg_cell_toeplitz(const VB& vb, KzgSrc 
 // 32 i + w) sit in LDS; a lane walks them a word at a time for the next byte equal to d (the zero-byte test on the word xor d d d d: its
 // lowest flag is exact) and adds table[w][j][i] = 2^(8 w) X_i[j], so a wave pays for its busiest lane's entries (8 on average) and no fold
 // follows: the buckets go through LDS into k_kzg_finish's eight bit sums, sums[b] = the sum of the buckets whose digit has bit b set — a
-// wave per bit, two passes. c: k_kzg_cell_toeplitz's rows; table: [32][8192] affine; sums: [n_blobs][128][8]
-static __device__ __forceinline__ void k_kzg_cell_msm(const VB& vb, const uint8_t* __restrict__ c, const bls::G1Aff* __restrict__ table, bls::G1Jac* __restrict__ sums) {
+// wave per bit, two passes. c: k_kzg_cell_toeplitz's rows; table: [32][8192] affine; sums: [n_blobs][128][8].
+// The walk and the fold are written once, kzg_cell_msm_sum, for every table of byte windows: sum number `sum` over the 64 entries that
+// `at(w, i)` (w < 32, i < 64) places in `table` — here column j of the cell settings, in kzg_cell_verify_kernels.cuh the first 64 columns of
+// the settings themselves
+struct KzgCellColumns {
+    u32 j;
+    __device__ __forceinline__ size_t operator()(u32 w, u32 i) const { return (size_t)w * KZG_CELL_POINTS + j * 64u + i; }  // w < 32, j < 128, i < 64
+};
+template <class At>
+static __device__ __forceinline__ void kzg_cell_msm_sum(size_t sum, At at, const uint8_t* __restrict__ c, const bls::G1Aff* __restrict__ table, bls::G1Jac* __restrict__ sums) {
     __shared__ __attribute__((aligned(16))) u32 digits[512];
     __shared__ bls::G1Jac bucket[KZG_BUCKETS];
     __shared__ bls::G1Jac fold[KZG_CELL_MSM_THREADS / 2];
-    const u32 t = threadIdx.x, j = vb.x;
-    const size_t sum = (size_t)vb.y * KZG_CELLS + j;
+    const u32 t = threadIdx.x;
     if (t < 128) reinterpret_cast<uint4*>(digits)[t] = reinterpret_cast<const uint4*>(c + sum * 2048)[t];
     __syncthreads();
     bls::G1Jac acc = bls::jac_inf();
@@ -275,7 +282,7 @@ static __device__ __forceinline__ void k_kzg_cell_msm(const VB& vb, const uint8_
             q = (q & ~3u) + 4;
         }
         if (q >= 2048) break;
-        acc = bls::jmadd(acc, table[(size_t)(q & 31u) * KZG_CELL_POINTS + j * 64u + (q >> 5)]);  // w < 32, j < 128, i < 64
+        acc = bls::jmadd(acc, table[at(q & 31u, q >> 5)]);
         q++;
     }
     bucket[t] = acc;
@@ -293,6 +300,9 @@ static __device__ __forceinline__ void k_kzg_cell_msm(const VB& vb, const uint8_
         a = kzg_group_sum<64>(a, fold);
         if (l == 0) sums[sum * 8 + b] = a;
     }
+}
+static __device__ __forceinline__ void k_kzg_cell_msm(const VB& vb, const uint8_t* __restrict__ c, const bls::G1Aff* __restrict__ table, bls::G1Jac* __restrict__ sums) {
+    kzg_cell_msm_sum((size_t)vb.y * KZG_CELLS + vb.x, KzgCellColumns{vb.x}, c, table, sums);
 }
 
 // a lane per sum: H = sum_b 2^b sums[b] by seven doublings, kept Jacobian

@@ -20,8 +20,9 @@
 namespace zkw {
 
 enum : int { KZG_VFY_THREADS = 64, KZG_VFY_CLAIMS_PER_BLOCK = KZG_VFY_THREADS / bls::F12_LANES };
-// a verdict byte; the lowest applicable code above 1 wins
-enum : u32 { KZG_VERDICT_FAILS = 0, KZG_VERDICT_HOLDS = 1, KZG_VERDICT_BAD_COMMITMENT = 2, KZG_VERDICT_BAD_PROOF = 3, KZG_VERDICT_BAD_SCALAR = 4 };
+// a verdict byte; the lowest applicable code above 1 wins (5: zkw_kzg_verify_cells alone, a cell index that is not below 128)
+enum : u32 { KZG_VERDICT_FAILS = 0, KZG_VERDICT_HOLDS = 1, KZG_VERDICT_BAD_COMMITMENT = 2, KZG_VERDICT_BAD_PROOF = 3, KZG_VERDICT_BAD_SCALAR = 4,
+             KZG_VERDICT_BAD_INDEX = 5 };
 enum : int { KZG_G2_INFINITY = 6 };  // k_kzg_g2_prepare's status beside bls::G1_OK .. G1_NOT_IN_SUBGROUP
 
 // -G2 for the standard generator G2 (G2Affine::one() of the reference), compressed

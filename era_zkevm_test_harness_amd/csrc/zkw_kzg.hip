@@ -5,9 +5,10 @@
 // (verify_proof_poly), and the producers from a blob in evaluation form, zkw_kzg_blob_coefficients, zkw_kzg_commit_blobs,
 // zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them), and
 // the EIP-7594 cells and cell proofs, zkw_kzg_cell_settings with zkw_kzg_g1_fft, zkw_kzg_cells_blobs, zkw_kzg_cell_proofs_blobs and
-// zkw_eip4844_cell_proofs, and the way back from any half of the cells, zkw_kzg_recover_cells_blobs (the reference has no counterpart).
+// zkw_eip4844_cell_proofs, and the way back from any half of the cells, zkw_kzg_recover_cells_blobs, and the check of cell proofs,
+// zkw_kzg_verify_cells with zkw_kzg_commit_cells (the reference has no counterpart of the three).
 // Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh,
-// kzg_recover_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
+// kzg_recover_kernels.cuh, kzg_cell_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 // What the calls share is written once, ahead of them: the handles' owner logic (KzgHandle), the blob limit, the 128 KiB of dynamic LDS of
 // the five transform kernels, and the twiddles.
 #include "zkw_ctx.h"
@@ -17,6 +18,7 @@
 #include "kzg_verify_kernels.cuh"
 #include "kzg_cell_kernels.cuh"
 #include "kzg_recover_kernels.cuh"
+#include "kzg_cell_verify_kernels.cuh"
 
 #include <cstddef>
 
@@ -780,5 +782,92 @@ extern "C" int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings* cs, zkw_
         ZKW_TRY(kzg_cell_proofs_device(cs, ctx, src, (u32)KZG_EVAL_BYTES, d_tw, n, d_proofs));
         ZKW_TRY(ctx->finish_out(proofs, d_proofs, n * KZG_CELLS * 48));
     }
+    return ctx->sync_if_host();
+}
+
+// ---- EIP-7594 verification: a verdict per (commitment, cell index, cell, proof) (kzg_cell_verify_kernels.cuh) ------------------------------
+// [I_k(tau)] G1 of n >= 1 claims, Jacobian, at *d_h, and k_kzg_cell_interpolate's status words at *d_st: the twiddles, the interpolation,
+// the 64-term sums over columns 0..63 of the settings' table, their Horner step. Nothing is read back
+static int kzg_cell_commit_device(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* d_idx, const uint8_t* d_cells, size_t n, const bls::Fr** d_tw,
+                                  const bls::G1Jac** d_h, const u32** d_st) {
+    const bls::Fr* d_wpow = nullptr;
+    uint8_t* d_c = nullptr;
+    bls::G1Jac *d_sums = nullptr, *d_pts = nullptr;
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<uint8_t>("kzg_cell_scalars", n * KZG_CELL_BYTES, &d_c));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_sums", n * 8, &d_sums));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_cell_points", n, &d_pts));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_cell_status", n, &d_status));
+    ZKW_TRY(kzg_twiddles_device(ctx, d_tw, &d_wpow));
+    ZKW_LAUNCH(ctx, k_kzg_cell_interpolate, blocks_for(n, KZG_CELL_INTERP_CLAIMS), KZG_CELL_INTERP_THREADS, d_idx, d_cells, (u32)n, *d_tw, d_wpow, d_c, d_status);
+    ZKW_LAUNCH(ctx, k_kzg_cell_commit_msm, n, KZG_CELL_MSM_THREADS, (const uint8_t*)d_c, (const bls::G1Aff*)s->table, (u32)s->n, d_sums);
+    ZKW_LAUNCH(ctx, k_kzg_cell_horner, blocks_for(n, 64), 64, (const bls::G1Jac*)d_sums, (u32)n, d_pts);
+    *d_h = d_pts;
+    *d_st = d_status;
+    return ZKW_OK;
+}
+
+static int kzg_cell_claims_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
+    if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
+    if (s->n < KZG_CELL_ELEMENTS) return fail(ZKW_ERR_INVALID, "%s: a cell's interpolant has 64 coefficients, the settings hold %zu points", who, s->n);
+    if (n > (1u << 24)) return fail(ZKW_ERR_INVALID, "%s: at most %u claims per call, not %zu", who, 1u << 24, n);
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_commit_cells(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint64_t* cell_indices, const uint8_t* cells, size_t n, uint8_t* out) {
+    const char* who = "zkw_kzg_commit_cells";
+    if (!s || !ctx || (n && (!cell_indices || !cells || !out))) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    ZKW_TRY(kzg_cell_claims_check_call(who, s, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint64_t* d_idx = nullptr;
+    const uint8_t* d_cells = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_indices", cell_indices, n, &d_idx));
+    ZKW_TRY(ctx->in("kzg_in_cells", cells, n * KZG_CELL_BYTES, &d_cells));
+    const bls::Fr* d_tw = nullptr;
+    const bls::G1Jac* d_h = nullptr;
+    const u32* d_st = nullptr;
+    ZKW_TRY(kzg_cell_commit_device(s, ctx, reinterpret_cast<const uint8_t*>(d_idx), d_cells, n, &d_tw, &d_h, &d_st));
+    std::vector<u32> st(n);  // the call's ONE readback, ahead of anything that writes the caller's buffer
+    ZKW_TRY(ctx->read_small(st.data(), d_st, n * sizeof(u32)));
+    for (size_t i = 0; i < n; i++) {
+        if (st[i] == KZG_CELL_ST_BAD_INDEX) return fail(ZKW_ERR_INVALID, "%s: cell_indices[%zu] is not below 128", who, i);
+        if (st[i] != KZG_CELL_ST_OK) return fail(ZKW_ERR_INVALID, "%s: element %u of cells[%zu] is not below r", who, (unsigned)(st[i] - KZG_CELL_ST_BAD_ELEMENT), i);
+    }
+    uint8_t* d_out = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", out, n * 48, &d_out));
+    ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(n, 64), 64, d_h, (u32)n, 0u, d_out);
+    ZKW_TRY(ctx->finish_out(out, d_out, n * 48));
+    return ctx->sync_if_host();
+}
+
+extern "C" int zkw_kzg_verify_cells(const zkw_kzg_verifier* v64, const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* commitments, const uint64_t* cell_indices,
+                                    const uint8_t* cells, const uint8_t* proofs, size_t n, uint8_t* verdicts) {
+    const char* who = "zkw_kzg_verify_cells";
+    if (!v64 || !s || !ctx || (n && (!commitments || !cell_indices || !cells || !proofs || !verdicts))) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    ZKW_TRY(kzg_verify_check_call(who, v64, ctx, n));
+    ZKW_TRY(kzg_cell_claims_check_call(who, s, ctx, n));
+    if (n == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint64_t* d_idx64 = nullptr;
+    const uint8_t *d_cm = nullptr, *d_cells = nullptr, *d_pr = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_commitments", commitments, n * 48, &d_cm));
+    ZKW_TRY(ctx->in("kzg_in_indices", cell_indices, n, &d_idx64));
+    ZKW_TRY(ctx->in("kzg_in_cells", cells, n * KZG_CELL_BYTES, &d_cells));
+    ZKW_TRY(ctx->in("kzg_in_proofs", proofs, n * 48, &d_pr));
+    const uint8_t* d_idx = reinterpret_cast<const uint8_t*>(d_idx64);
+    uint8_t* d_verdicts = nullptr;
+    ZKW_TRY(ctx->out("kzg_verdicts", verdicts, n, &d_verdicts));
+    const bls::Fr* d_tw = nullptr;
+    const bls::G1Jac* d_h = nullptr;
+    const u32* d_ist = nullptr;
+    ZKW_TRY(kzg_cell_commit_device(s, ctx, d_idx, d_cells, n, &d_tw, &d_h, &d_ist));
+    bls::G1Aff* d_pts = nullptr;
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_verify_points", 2 * n, &d_pts));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_verify_status", n, &d_status));
+    ZKW_LAUNCH(ctx, k_kzg_verify_cell_points, blocks_for(n, 64), 64, d_cm, d_idx, d_pr, d_ist, d_h, d_tw, (u32)n, d_pts, d_status);
+    ZKW_LAUNCH_D(ctx, k_kzg_verify_pairing, "k_kzg_verify_pairing", dim3(blocks_for(n, KZG_VFY_CLAIMS_PER_BLOCK)), KZG_VFY_THREADS, bls::f12_lds_bytes(KZG_VFY_THREADS), (const bls::G1Aff*)d_pts, (const u32*)d_status, (const bls::G2Line*)v64->table, (u32)n, d_verdicts);
+    ZKW_TRY(ctx->finish_out(verdicts, d_verdicts, n));
     return ctx->sync_if_host();
 }

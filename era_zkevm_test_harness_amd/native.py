@@ -206,6 +206,8 @@ SYMBOLS = [
     ("zkw_kzg_cell_proofs_blobs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_eip4844_cell_proofs", _int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_kzg_recover_cells_blobs", _int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("zkw_kzg_verify_cells", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zkw_kzg_commit_cells", _int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zkw_block_apply_storage", _int, [_vp, _vp]),
     ("zkw_storage_application_synthesize", _int, [_vp, _vp, _sz, _sz, _vp, _sz]),
     ("zkw_storage_application_check_satisfied", _int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp]),
@@ -952,6 +954,30 @@ class KzgSettings:
         _check(load().zkw_eip4844_prove_blobs(self.handle, ctx.handle, eptr, cptr, n, pptr, optr))
         return (proofs, op) if openings else proofs
 
+    @staticmethod
+    def _cell_indices(ctx, cell_indices):
+        """(pointer, count, keep-alive) of cell indices as 64-bit words: a torch int64 / uint64 tensor in device pointer mode, anything
+        numpy makes unsigned 64-bit words of otherwise"""
+        if ctx.pointer_mode == PTR_DEVICE:
+            t = cell_indices.contiguous()
+            assert t.is_cuda and t.element_size() == 8
+            return C.c_void_p(t.data_ptr() if t.numel() else None), t.numel(), t
+        a = np.ascontiguousarray(cell_indices, dtype=np.uint64).reshape(-1)
+        return (_np_ptr(a) if a.size else None), a.size, a
+
+    def commit_cells(self, cell_indices, cells, ctx=None):
+        """zkw_kzg_commit_cells: `cell_indices` = [n] 64-bit words, `cells` = [n, 2048] bytes (a cell as `kzg_cells_blobs` writes it);
+        returns [n, 48]: compress([I_k(tau)] G1), I_k the polynomial of degree below 64 through the 64 values of the cell at the points
+        of cell k. Needs 64 points or more. An index of 128 or more, or an element that is not below r, raises ZkwError(ERR_INVALID)
+        naming the claim."""
+        ctx = ctx or self.ctx
+        iptr, n, _ki = self._cell_indices(ctx, cell_indices)
+        cptr, nc, _kc = self._bytes(ctx, cells, EIP7594_CELL_BYTES)
+        assert n == nc
+        out, optr = self._empty(ctx, _kc, (n, 48))
+        _check(load().zkw_kzg_commit_cells(self.handle, ctx.handle, iptr, cptr, n, optr))
+        return out
+
     def free(self):
         if self.handle:
             load().zkw_kzg_settings_free(self.handle)
@@ -1003,7 +1029,7 @@ class KzgCellSettings:
     of its device: the G1 transforms of the 64 vectors x_i[m] = S[4031 - i - 64 m] as a byte-window table in HBM (`nbytes`). Immutable
     afterwards and it keeps its context alive: the proof calls may run on any context of the same device (`ctx=`), several at once.
     Arrays as for `KzgSettings`. `recover_cells_and_proofs` (and `kzg_recover_cells`, which needs no settings) is the way back from any 64
-    of the 128 cells. Verification of cell proofs is not offered."""
+    of the 128 cells. The check of cell proofs is `KzgVerifier.verify_cells`."""
 
     def __init__(self, settings, ctx=None):
         self.ctx = ctx or settings.ctx
@@ -1100,6 +1126,7 @@ def kzg_g1_fft(ctx, points, n, inverse=False):
 
 
 KZG_VERDICT_FAILS, KZG_VERDICT_HOLDS, KZG_VERDICT_BAD_COMMITMENT, KZG_VERDICT_BAD_PROOF, KZG_VERDICT_BAD_SCALAR = range(5)
+KZG_VERDICT_BAD_INDEX = 5  # `KzgVerifier.verify_cells` alone: a cell index that is not below 128
 
 
 class KzgVerifier:
@@ -1188,6 +1215,22 @@ class KzgVerifier:
         _check(load().zkw_eip4844_verify_blobs(self.handle, ctx.handle, eptr, cptr, pptr, n, _np_ptr(out) if n else None,
                                                _np_ptr(op) if openings and n else None))
         return (out, op) if openings else out
+
+    def verify_cells(self, settings, commitments, cell_indices, cells, proofs, ctx=None):
+        """zkw_kzg_verify_cells (verify_cell_kzg_proof_batch of the consensus specs, a verdict per claim) on a verifier made from
+        [tau^64] G2 — with the one of [tau] G2 a true claim gets verdict 0 (unless its proof is the point at infinity). `settings` = a `KzgSettings` of 64 points or more;
+        `commitments` and `proofs` = [n, 48] bytes, `cell_indices` = [n] 64-bit words, `cells` = [n, 2048] bytes (a cell as
+        `kzg_cells_blobs` writes it). Returns [n] verdict bytes: the codes of `verify`, 4 for a cell element that is not below r,
+        KZG_VERDICT_BAD_INDEX for an index of 128 or more."""
+        ctx = ctx or self.ctx
+        cptr, n, _kc = KzgSettings._bytes(ctx, commitments, 48)
+        iptr, ni, _ki = KzgSettings._cell_indices(ctx, cell_indices)
+        eptr, ne, _ke = KzgSettings._bytes(ctx, cells, EIP7594_CELL_BYTES)
+        pptr, np_, _kp = KzgSettings._bytes(ctx, proofs, 48)
+        assert n == ni == ne == np_
+        out, optr = KzgSettings._empty(ctx, _kc, (n,))
+        _check(load().zkw_kzg_verify_cells(self.handle, settings.handle, ctx.handle, cptr, iptr, eptr, pptr, n, optr))
+        return out
 
     def free(self):
         if self.handle:

@@ -864,8 +864,8 @@ int zkw_eip4844_prove_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8
    two from 1 to 128, natural order in and out: out[u] = sum_j w_n^(u j) in[j], w_n = 7^((r-1)/n); inverse != 0: w_n^-1 and the
    factor 1/n.  The points are checked as zkw_kzg_settings_create checks them (the point at infinity is allowed); a bad one is
    ZKW_ERR_INVALID naming its position and its transform, the outputs untouched.  At most 65 535 transforms per call.
-   Not offered: verification of cell proofs (it needs [tau^64] G2), a Lagrange-basis setup.  Recovery from half the cells is
-   zkw_kzg_recover_cells_blobs below. */
+   Not offered: a Lagrange-basis setup.  Recovery from half the cells is zkw_kzg_recover_cells_blobs below, the check of cell
+   proofs zkw_kzg_verify_cells below that. */
 typedef struct zkw_kzg_cell_settings zkw_kzg_cell_settings;
 int zkw_kzg_cell_settings_create(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_cell_settings **out);
 void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings *cs);
@@ -891,11 +891,47 @@ int zkw_eip4844_cell_proofs(const zkw_kzg_cell_settings *cs, zkw_ctx *ctx, const
    of 128 or more or one that does not ascend (naming its position in the list); proofs without settings; settings and context
    on different devices; more than 32 767 blobs; a supplied element not below r (naming blob, position in the list and
    element); an inconsistent set.  One readback per call, ahead of every write to recovered or proofs (the results are staged
-   in context scratch and copied afterwards).  n = 0 is a no-op.  Not offered: a per-blob index list, verification of cell proofs. */
+   in context scratch and copied afterwards).  n = 0 is a no-op.  Not offered: a per-blob index list.  The supplied cells are
+   checked against each other, never against the blob's commitment: a consistent set of cells of another blob recovers without
+   complaint, and a caller that holds commitments and proofs composes this call with zkw_kzg_verify_cells. */
 int zkw_kzg_recover_cells_blobs(const zkw_kzg_cell_settings *cs /* may be NULL when proofs is NULL */, zkw_ctx *ctx,
                                 const uint8_t *cell_indices /*[n_cells], HOST memory in both pointer modes*/, size_t n_cells,
                                 const uint8_t *cells /*[n][n_cells][2048]*/, size_t n,
                                 uint8_t *recovered /*[n][128][2048]*/, uint8_t *proofs /*[n][128][48] or NULL*/);
+/* EIP-7594 verification (verify_cell_kzg_proof_batch of the consensus specs, with a verdict per claim): does proofs[i] prove
+   that cells[i] is cell cell_indices[i] of the blob committed to by commitments[i]?  One commitment per claim, repeated by the
+   caller for the cells of one blob.  With c_k = w128^brp7(k), h_k = W^brp7(k) and I_k the polynomial of degree below 64 through
+   the 64 values of cell k (at h_k w64^brp6(t), w64 = W^128), p = q_k (X^64 - c_k) + I_k, so the claim holds exactly when
+       e(C - [I_k(tau)] G1 + [c_k] proof, -G2) e(proof, [tau^64] G2) = 1
+   — zkw_kzg_verify's equation with [y] G1 replaced by the commitment of I_k, z by c_k and [tau] G2 by [tau^64] G2.
+   v64: a zkw_kzg_verifier created from [tau^64] G2 (the caller supplies it as it supplies [tau] G2; the mainnet ceremony's is the
+   65th point of its G2 list).  The handle cannot know which power of tau it holds: with the verifier of [tau] G2 every true
+   claim gets verdict 0 (but one whose proof is the point at infinity — a blob of degree below 64 — which holds under any).
+   s: any settings handle of at least 64 points on the context's device; only columns 0..63 of its table are read, so a node that
+   only verifies may build its settings from the first 64 points of the setup (about 200 KB of HBM instead of 12.6 MB).  Fewer
+   than 64 points: ZKW_ERR_INVALID.
+   cell_indices are 64-bit words (host or device memory as the context's pointer mode says, any address; both halves are read),
+   a cell is 64 x 32 big-endian bytes in the cell's own order, the form zkw_kzg_cells_blobs writes.
+   A verifier reports, it does not refuse: bad data is a verdict, never an error return.  verdicts[i]: the codes of
+   zkw_kzg_verify — 0 the equation fails, 1 it holds, 2 malformed commitment, 3 malformed proof, 4 a cell element is not below
+   r — and 5, cell_indices[i] >= 128; the lowest applicable code above 1 wins.  Nothing is read back: in device pointer mode the
+   call only enqueues.  n = 0 is a no-op; at most 2^24 claims per call; ZKW_ERR_INVALID, named in zkw_last_error, when the
+   verifier or the settings live on another device than the context.
+   zkw_kzg_commit_cells writes out[i] = compress([I_k(tau)] G1), the commitment of claim i's interpolant alone (the point at
+   infinity for an all-zero cell): the one intermediate that can be compared on a setup for which no [tau^64] G2 is at hand, and
+   what a batch verifier would sum.  It is a producer and refuses like one: ZKW_ERR_INVALID naming the claim (and the LOWEST
+   offending element) when an index is 128 or more or an element is not below r, out then untouched in both pointer modes; one
+   readback per call, ahead of every write to out.  The settings, n = 0 and the limit as above.
+   Not offered: the single-verdict random-linear-combination form of the specs (as for zkw_eip4844_verify: the call is bound by the
+   latency of one wave per 8 claims, and a verdict per claim tells a custodian WHICH column is bad); a [tau^64] G2 of the ceremony
+   among the fixtures; multi-scalar work in G2; the check of recovery's inputs inside zkw_kzg_recover_cells_blobs (callers
+   compose the two calls). */
+int zkw_kzg_verify_cells(const zkw_kzg_verifier *v64, const zkw_kzg_settings *s, zkw_ctx *ctx,
+                         const uint8_t *commitments /*[n][48]*/, const uint64_t *cell_indices /*[n]*/,
+                         const uint8_t *cells /*[n][2048]*/, const uint8_t *proofs /*[n][48]*/, size_t n,
+                         uint8_t *verdicts /*[n]*/);
+int zkw_kzg_commit_cells(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint64_t *cell_indices /*[n]*/,
+                         const uint8_t *cells /*[n][2048]*/, size_t n, uint8_t *out /*[n][48]*/);
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;
