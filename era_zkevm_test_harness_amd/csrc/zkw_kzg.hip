@@ -6,9 +6,10 @@
 // zkw_kzg_open_blobs and zkw_eip4844_prove_blobs (compute_commitment, compute_proof, compute_proof_poly as the reference calls them), and
 // the EIP-7594 cells and cell proofs, zkw_kzg_cell_settings with zkw_kzg_g1_fft, zkw_kzg_cells_blobs, zkw_kzg_cell_proofs_blobs and
 // zkw_eip4844_cell_proofs, and the way back from any half of the cells, zkw_kzg_recover_cells_blobs, and the check of cell proofs,
-// zkw_kzg_verify_cells with zkw_kzg_commit_cells (the reference has no counterpart of the three).
+// zkw_kzg_verify_cells with zkw_kzg_commit_cells (the reference has no counterpart of the three), and the setup in the Lagrange basis
+// (KzgSettings::new, kzg/src/lib.rs:36-156): zkw_kzg_g1_fft_wide, zkw_kzg_settings_to_lagrange, _to_monomial, _points and _basis.
 // Kernels and the decomposition: kzg_kernels.cuh, kzg_open_kernels.cuh, kzg_eval_kernels.cuh, kzg_verify_kernels.cuh, kzg_cell_kernels.cuh,
-// kzg_recover_kernels.cuh, kzg_cell_verify_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
+// kzg_recover_kernels.cuh, kzg_cell_verify_kernels.cuh, kzg_g1_fft_wide_kernels.cuh; field and group arithmetic: bls12_381.cuh, the tower and the pairing: bls12_381_pairing.cuh.
 // What the calls share is written once, ahead of them: the handles' owner logic (KzgHandle), the blob limit, the 128 KiB of dynamic LDS of
 // the five transform kernels, and the twiddles.
 #include "zkw_ctx.h"
@@ -19,6 +20,7 @@
 #include "kzg_cell_kernels.cuh"
 #include "kzg_recover_kernels.cuh"
 #include "kzg_cell_verify_kernels.cuh"
+#include "kzg_g1_fft_wide_kernels.cuh"
 
 #include <cstddef>
 
@@ -65,6 +67,7 @@ template <class H> static hipError_t kzg_handle_new(zkw_ctx* ctx, size_t bytes, 
 
 struct zkw_kzg_settings : KzgHandle<bls::G1Aff> {  // table: [32][n], table[w * n + k] = 2^(8 w) S[k]
     size_t n = 0;
+    int basis = 0;  // 1: zkw_kzg_settings_to_lagrange made it, S[k] = L[brp(k)]; 0: as created (taken as [tau^k] G1)
 };
 
 static const char* kzg_reason(u32 status) {
@@ -127,7 +130,15 @@ static int kzg_commit_device(const zkw_kzg_settings* s, zkw_ctx* ctx, KzgSrc src
     return ZKW_OK;
 }
 
-static int kzg_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
+// every call that reads S[k] as [tau^k] G1 refuses a handle in the Lagrange basis, ahead of its first launch
+static int kzg_monomial_only(const char* who, const zkw_kzg_settings* s) {
+    if (s->basis != 0) return fail(ZKW_ERR_INVALID, "%s: the settings are in the Lagrange basis (zkw_kzg_settings_to_lagrange made them), the call needs [tau^k] G1", who);
+    return ZKW_OK;
+}
+
+enum KzgBasis { KZG_MONOMIAL, KZG_ANY_BASIS };
+static int kzg_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n, KzgBasis basis = KZG_MONOMIAL) {
+    if (basis == KZG_MONOMIAL) ZKW_TRY(kzg_monomial_only(who, s));
     if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
     if (n > 65535) return fail(ZKW_ERR_INVALID, "%s: at most 65535 polynomials per call, not %zu", who, n);
     return ZKW_OK;
@@ -171,7 +182,7 @@ static int kzg_twiddles_device(const LaunchAt& at, const bls::Fr** d_tw, const b
 extern "C" int zkw_kzg_commit(const zkw_kzg_settings* s, zkw_ctx* ctx, const uint8_t* coeffs, size_t n_coeffs, size_t n_polys, uint8_t* out) {
     if (!s || !ctx || (n_polys && (!out || (n_coeffs && !coeffs)))) return fail(ZKW_ERR_INVALID, "zkw_kzg_commit: null argument");
     if (n_coeffs > s->n) return fail(ZKW_ERR_INVALID, "zkw_kzg_commit: %zu coefficients, the settings hold %zu points", n_coeffs, s->n);
-    ZKW_TRY(kzg_check_call("zkw_kzg_commit", s, ctx, n_polys));
+    ZKW_TRY(kzg_check_call("zkw_kzg_commit", s, ctx, n_polys, KZG_ANY_BASIS));  // a sum over the points, whatever they are
     if (n_polys == 0) return ZKW_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t total = n_coeffs * n_polys;
@@ -580,6 +591,7 @@ static int kzg_g1_fft_device(zkw_ctx* ctx, const bls::G1Jac* d_in, bls::G1Jac* d
 
 extern "C" int zkw_kzg_cell_settings_create(const zkw_kzg_settings* s, zkw_ctx* ctx, zkw_kzg_cell_settings** out) {
     if (!s || !ctx || !out) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: null argument");
+    ZKW_TRY(kzg_monomial_only("zkw_kzg_cell_settings_create", s));
     if (s->n != KZG_BLOB_ELEMENTS) return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: a blob has 4096 elements, the settings hold %zu points", s->n);
     if (ctx->device != s->ctx->device)
         return fail(ZKW_ERR_INVALID, "zkw_kzg_cell_settings_create: the settings live on device %d, the context on device %d", s->ctx->device, ctx->device);
@@ -637,6 +649,130 @@ extern "C" int zkw_kzg_g1_fft(zkw_ctx* ctx, const uint8_t* points, size_t n, siz
     ZKW_TRY(kzg_g1_fft_device(ctx, d_jac, d_jac, log_n, n_ffts, inverse != 0, inverse != 0, false));
     ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(total, 64), 64, (const bls::G1Jac*)d_jac, (u32)total, 0u, d_out);
     ZKW_TRY(ctx->finish_out(out, d_out, total * 48));
+    return ctx->sync_if_host();
+}
+
+// ---- the wide G1 transform and the setup's two bases (kzg_g1_fft_wide_kernels.cuh) -------------------------------------------------------
+static_assert(KZG_G1_FFT_WIDE_MAX == KZG_MAX_POINTS && KZG_G1_FFT_WIDE_POINTS % KZG_G1_FFT_MAX == 0, "a setup is one wide transform");
+
+// n_ffts transforms of 2^log_n <= 4 096 Jacobian points each (n_ffts 2^log_n <= 65 536), in place at d_x up to the order of the result:
+// *d_res is d_x when the result is there in natural order (n <= 128 without `brp`), else d_y (as many points, another buffer), in natural
+// order or with `brp` output u at brp(u). The inverse carries its 1 / n
+static int kzg_g1_fft_wide_device(zkw_ctx* ctx, bls::G1Jac* d_x, bls::G1Jac* d_y, u32 log_n, size_t n_ffts, bool inverse, bool brp, const bls::G1Jac** d_res) {
+    const size_t total = n_ffts << log_n;
+    const u32 inv = inverse ? 1u : 0u;
+    if (log_n <= 7) {
+        ZKW_TRY(kzg_g1_fft_device(ctx, d_x, d_x, log_n, n_ffts, inverse, inverse, false));
+        *d_res = d_x;
+        if (!brp) return ZKW_OK;
+    }
+    const unsigned order_blocks = blocks_for(total < KZG_G1_FFT_WIDE_POINTS / 2 ? total : KZG_G1_FFT_WIDE_POINTS / 2, KZG_G1_FFT_THREADS);
+    const size_t waves = log_n > 7 ? total / KZG_G1_FFT_MAX : 0;  // of a stage and of the tail; the order kernel has at most as many with a table
+    u32* d_tab = nullptr;                                          // the lanes' window tables (kzg_g1_fft_device asks for the same ones)
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_g1_fft_tables", (waves > order_blocks ? waves : order_blocks) * KZG_G1_TAB_WORDS, &d_tab));
+    if (log_n > 7) {
+        for (u32 s = 0; s + 7 < log_n; s++)
+            ZKW_LAUNCH(ctx, k_kzg_g1_fft_stage, waves, KZG_G1_FFT_THREADS, d_x, d_tab, log_n, s, inv, (u32)(total / 2));
+        ZKW_TRY(kzg_g1_fft_device(ctx, d_x, d_x, 7, waves, inverse, false, false));
+    }
+    const u32 scale_row = inverse && log_n > 7 ? KZG_G1_FFT_WIDE_HALF + log_n - 8 : 0u;
+    ZKW_LAUNCH(ctx, k_kzg_g1_fft_order, order_blocks, KZG_G1_FFT_THREADS, (const bls::G1Jac*)d_x, d_y, d_tab, log_n, (u32)total, order_blocks * (u32)KZG_G1_FFT_THREADS,
+               scale_row, brp ? 1u : 0u);
+    *d_res = d_y;
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_g1_fft_wide(zkw_ctx* ctx, const uint8_t* points, size_t n, size_t n_ffts, int inverse, uint8_t* out) {
+    const char* who = "zkw_kzg_g1_fft_wide";
+    if (!ctx || (n_ffts && (!points || !out))) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (n == 0 || n > KZG_G1_FFT_WIDE_MAX || (n & (n - 1))) return fail(ZKW_ERR_INVALID, "%s: a power of two from 1 to %u points, not %zu", who, (unsigned)KZG_G1_FFT_WIDE_MAX, n);
+    if (n_ffts > 65535) return fail(ZKW_ERR_INVALID, "%s: at most 65535 transforms per call, not %zu", who, n_ffts);
+    if (n * n_ffts > KZG_G1_FFT_WIDE_POINTS) return fail(ZKW_ERR_INVALID, "%s: at most %u points per call, not %zu transforms of %zu", who, (unsigned)KZG_G1_FFT_WIDE_POINTS, n_ffts, n);
+    if (n_ffts == 0) return ZKW_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = n * n_ffts;
+    u32 log_n = 0;
+    while ((size_t)1 << log_n < n) log_n++;
+    const uint8_t* d_in = nullptr;
+    ZKW_TRY(ctx->in("kzg_in_points", points, total * 48, &d_in));
+    bls::G1Aff* d_aff = nullptr;
+    bls::G1Jac *d_jac = nullptr, *d_ord = nullptr;
+    u32* d_status = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Aff>("kzg_g1_fft_affine", total, &d_aff));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_points", total, &d_jac));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_ordered", total, &d_ord));
+    ZKW_TRY(ctx->scratch_t<u32>("kzg_status", total, &d_status));
+    ZKW_LAUNCH(ctx, k_kzg_decompress, blocks_for(total, 64), 64, d_in, (u32)total, d_aff, d_status);
+    std::vector<u32> status(total);
+    ZKW_TRY(ctx->read_small(status.data(), d_status, total * sizeof(u32)));
+    for (size_t k = 0; k < total; k++)
+        if (status[k] != bls::G1_OK) return fail(ZKW_ERR_INVALID, "%s: point %zu of transform %zu is refused: %s", who, k % n, k / n, kzg_reason(status[k]));
+    uint8_t* d_out = nullptr;
+    ZKW_TRY(ctx->out("kzg_out", out, total * 48, &d_out));
+    ZKW_LAUNCH(ctx, k_kzg_g1_lift, blocks_for(total, 64), 64, (const bls::G1Aff*)d_aff, (u32)total, d_jac);
+    const bls::G1Jac* d_res = nullptr;
+    ZKW_TRY(kzg_g1_fft_wide_device(ctx, d_jac, d_ord, log_n, n_ffts, inverse != 0, false, &d_res));
+    ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(total, 64), 64, d_res, (u32)total, 0u, d_out);
+    ZKW_TRY(ctx->finish_out(out, d_out, total * 48));
+    return ctx->sync_if_host();
+}
+
+// a new handle from row 0 of s's table, device to device: to the Lagrange basis S'[i] = L[brp(i)], L the inverse transform of S, or back,
+// S = the forward transform of L[u] = S'[brp(u)]. Sums of checked points stay in the subgroup: nothing is decompressed or checked again
+static int kzg_settings_transform(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, bool to_lagrange, zkw_kzg_settings** out) {
+    if (!s || !ctx || !out) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (s->n & (s->n - 1)) return fail(ZKW_ERR_INVALID, "%s: a transform has a power of two of points, the settings hold %zu", who, s->n);
+    if (to_lagrange && s->basis != 0) return fail(ZKW_ERR_INVALID, "%s: the settings are in the Lagrange basis already", who);
+    if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
+    if (ctx->batch) return fail(ZKW_ERR_INVALID, "%s: the context belongs to a batch of blocks", who);
+    HIP_TRY(hipSetDevice(ctx->device));
+    *out = nullptr;
+    const size_t n = s->n;
+    u32 log_n = 0;
+    while ((size_t)1 << log_n < n) log_n++;
+    bls::G1Jac *d_x = nullptr, *d_y = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_points", n, &d_x));
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_ordered", n, &d_y));
+    zkw_kzg_settings* h = nullptr;
+    const hipError_t e = kzg_handle_new(ctx, s->bytes, 64, &h);
+    if (e != hipSuccess) return fail(ZKW_ERR_OOM, "%s: %zu points need %zu bytes of device memory: %s", who, n, s->bytes, hipGetErrorString(e));
+    h->n = n;
+    h->basis = to_lagrange ? 1 : 0;
+    const int rc = [&]() -> int {
+        ZKW_LAUNCH(ctx, k_kzg_g1_fft_load, blocks_for(n, 64), 64, (const bls::G1Aff*)s->table, log_n, to_lagrange ? 0u : 1u, d_x);
+        const bls::G1Jac* d_res = nullptr;
+        ZKW_TRY(kzg_g1_fft_wide_device(ctx, d_x, d_y, log_n, 1, to_lagrange, to_lagrange, &d_res));
+        ZKW_LAUNCH(ctx, k_kzg_g1_affine, blocks_for(n, 64), 64, d_res, (u32)n, h->table);
+        ZKW_LAUNCH_2D(ctx, k_kzg_table, blocks_for(n, 64), KZG_WINDOWS - 1, 64, h->table, (u32)n);
+        HIP_TRY(ctx->sync_stream());  // other contexts read the table without any ordering with this stream
+        return ZKW_OK;
+    }();
+    if (rc != ZKW_OK) return kzg_handle_drop(h, rc);
+    ctx_retain(ctx);
+    *out = h;
+    return ZKW_OK;
+}
+
+extern "C" int zkw_kzg_settings_to_lagrange(const zkw_kzg_settings* s, zkw_ctx* ctx, zkw_kzg_settings** out) {
+    return kzg_settings_transform("zkw_kzg_settings_to_lagrange", s, ctx, true, out);
+}
+extern "C" int zkw_kzg_settings_to_monomial(const zkw_kzg_settings* s, zkw_ctx* ctx, zkw_kzg_settings** out) {
+    return kzg_settings_transform("zkw_kzg_settings_to_monomial", s, ctx, false, out);
+}
+extern "C" int zkw_kzg_settings_basis(const zkw_kzg_settings* s) { return s ? s->basis : 0; }
+
+extern "C" int zkw_kzg_settings_points(const zkw_kzg_settings* s, zkw_ctx* ctx, uint8_t* out) {
+    const char* who = "zkw_kzg_settings_points";
+    if (!s || !ctx || !out) return fail(ZKW_ERR_INVALID, "%s: null argument", who);
+    if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
+    HIP_TRY(hipSetDevice(ctx->device));
+    bls::G1Jac* d_x = nullptr;
+    uint8_t* d_out = nullptr;
+    ZKW_TRY(ctx->scratch_t<bls::G1Jac>("kzg_g1_fft_points", s->n, &d_x));
+    ZKW_TRY(ctx->out("kzg_out", out, s->n * 48, &d_out));
+    ZKW_LAUNCH(ctx, k_kzg_g1_lift, blocks_for(s->n, 64), 64, (const bls::G1Aff*)s->table, (u32)s->n, d_x);
+    ZKW_LAUNCH(ctx, k_kzg_g1_compress, blocks_for(s->n, 64), 64, (const bls::G1Jac*)d_x, (u32)s->n, 0u, d_out);
+    ZKW_TRY(ctx->finish_out(out, d_out, s->n * 48));
     return ctx->sync_if_host();
 }
 
@@ -808,6 +944,7 @@ static int kzg_cell_commit_device(const zkw_kzg_settings* s, zkw_ctx* ctx, const
 }
 
 static int kzg_cell_claims_check_call(const char* who, const zkw_kzg_settings* s, zkw_ctx* ctx, size_t n) {
+    ZKW_TRY(kzg_monomial_only(who, s));
     if (ctx->device != s->ctx->device) return fail(ZKW_ERR_INVALID, "%s: the settings live on device %d, the context on device %d", who, s->ctx->device, ctx->device);
     if (s->n < KZG_CELL_ELEMENTS) return fail(ZKW_ERR_INVALID, "%s: a cell's interpolant has 64 coefficients, the settings hold %zu points", who, s->n);
     if (n > (1u << 24)) return fail(ZKW_ERR_INVALID, "%s: at most %u claims per call, not %zu", who, 1u << 24, n);

@@ -199,6 +199,11 @@ SYMBOLS = [
     ("zkw_kzg_open_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_eip4844_prove_blobs", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zkw_kzg_g1_fft", _int, [_vp, _vp, _sz, _sz, _int, _vp]),
+    ("zkw_kzg_g1_fft_wide", _int, [_vp, _vp, _sz, _sz, _int, _vp]),
+    ("zkw_kzg_settings_to_lagrange", _int, [_vp, _vp, C.POINTER(_vp)]),
+    ("zkw_kzg_settings_to_monomial", _int, [_vp, _vp, C.POINTER(_vp)]),
+    ("zkw_kzg_settings_points", _int, [_vp, _vp, _vp]),
+    ("zkw_kzg_settings_basis", _int, [_vp]),
     ("zkw_kzg_cell_settings_create", _int, [_vp, _vp, C.POINTER(_vp)]),
     ("zkw_kzg_cell_settings_free", None, [_vp]),
     ("zkw_kzg_cell_settings_bytes", _sz, [_vp]),
@@ -807,6 +812,52 @@ class KzgSettings:
         ptr, n, _keep = self._bytes(ctx, g1_monomial, 48)
         _check(load().zkw_kzg_settings_create(ctx.handle, ptr, n, C.byref(self.handle)))
 
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        """a handle the library returned (to_lagrange, to_monomial)"""
+        s = cls.__new__(cls)
+        s.ctx, s.handle = ctx, handle
+        return s
+
+    @property
+    def basis(self) -> int:
+        """zkw_kzg_settings_basis: 0 as created (taken as monomial), 1 the Lagrange basis `to_lagrange` makes"""
+        return load().zkw_kzg_settings_basis(self.handle)
+
+    def _transformed(self, entry, ctx):
+        ctx = ctx or self.ctx
+        handle = C.c_void_p(None)
+        _check(entry(self.handle, ctx.handle, C.byref(handle)))
+        return KzgSettings._adopt(ctx, handle)
+
+    def to_lagrange(self, ctx=None):
+        """zkw_kzg_settings_to_lagrange: a NEW KzgSettings of basis 1, made on the device from this one's points S (a power of two of
+        them): S'[i] = L[brp(i)], L = the inverse transform of S, L[u] = [l_u(tau)] G1 — the reference's `lagrange_setup_brp`. `commit` of
+        a blob's evaluations (little-endian) on it is the reference's `compute_commitment`; every call that needs [tau^k] G1 refuses it.
+        Independent of this handle, which may be freed first."""
+        return self._transformed(load().zkw_kzg_settings_to_lagrange, ctx)
+
+    def to_monomial(self, ctx=None):
+        """zkw_kzg_settings_to_monomial: the way back — un-bit-reverse, forward transform, a NEW KzgSettings of basis 0. Takes either
+        basis: settings created from the `g1_lagrange` list of a Lagrange-only setup file have basis 0, because the library cannot know."""
+        return self._transformed(load().zkw_kzg_settings_to_monomial, ctx)
+
+    def points(self, ctx=None):
+        """zkw_kzg_settings_points: [num_points, 48] bytes, the compressed points the handle holds, in its order (a tensor on the context's
+        device in device pointer mode)."""
+        ctx = ctx or self.ctx
+        n = self.num_points
+        if ctx.pointer_mode == PTR_DEVICE:
+            import torch
+
+            out = torch.empty((n, 48), dtype=torch.uint8, device="cuda:%d" % getattr(ctx, "device_id", 0))
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            out = np.zeros((n, 48), np.uint8)
+            optr = _np_ptr(out)
+        _check(load().zkw_kzg_settings_points(self.handle, ctx.handle, optr))
+        return out
+
     @staticmethod
     def _bytes(ctx, a, row):
         """(pointer, rows, keep-alive) of an array of rows of `row` bytes"""
@@ -1125,6 +1176,17 @@ def kzg_g1_fft(ctx, points, n, inverse=False):
     return out
 
 
+def kzg_g1_fft_wide(ctx, points, n, inverse=False):
+    """zkw_kzg_g1_fft_wide: `kzg_g1_fft` for n a power of two from 1 to 4 096 (at most 65 536 points a call): `points` = [n_ffts, n, 48]
+    bytes, the same shape back, natural order in and out. Up to 128 points the bytes are `kzg_g1_fft`'s."""
+    ptr, rows, _keep = KzgSettings._bytes(ctx, points, 48)
+    n_ffts = rows // n if n else 0
+    assert n_ffts * n == rows
+    out, optr = KzgSettings._empty(ctx, _keep, (n_ffts, n, 48))
+    _check(load().zkw_kzg_g1_fft_wide(ctx.handle, ptr, n, n_ffts, 1 if inverse else 0, optr))
+    return out
+
+
 KZG_VERDICT_FAILS, KZG_VERDICT_HOLDS, KZG_VERDICT_BAD_COMMITMENT, KZG_VERDICT_BAD_PROOF, KZG_VERDICT_BAD_SCALAR = range(5)
 KZG_VERDICT_BAD_INDEX = 5  # `KzgVerifier.verify_cells` alone: a cell index that is not below 128
 
@@ -1392,6 +1454,7 @@ class Context:
         self.handle = lib.zkw_create(device_id)
         if not self.handle:
             raise ZkwError(ERR_NO_DEVICE, lib.zkw_last_error().decode())
+        self.device_id = device_id
         self.pointer_mode = PTR_HOST
 
     def close(self):

@@ -864,8 +864,9 @@ int zkw_eip4844_prove_blobs(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint8
    two from 1 to 128, natural order in and out: out[u] = sum_j w_n^(u j) in[j], w_n = 7^((r-1)/n); inverse != 0: w_n^-1 and the
    factor 1/n.  The points are checked as zkw_kzg_settings_create checks them (the point at infinity is allowed); a bad one is
    ZKW_ERR_INVALID naming its position and its transform, the outputs untouched.  At most 65 535 transforms per call.
-   Not offered: a Lagrange-basis setup.  Recovery from half the cells is zkw_kzg_recover_cells_blobs below, the check of cell
-   proofs zkw_kzg_verify_cells below that. */
+   Transforms above 128 points, and the setup in the Lagrange basis, are zkw_kzg_g1_fft_wide and zkw_kzg_settings_to_lagrange
+   at the end of this section.  Recovery from half the cells is zkw_kzg_recover_cells_blobs below, the check of cell proofs
+   zkw_kzg_verify_cells below that. */
 typedef struct zkw_kzg_cell_settings zkw_kzg_cell_settings;
 int zkw_kzg_cell_settings_create(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_cell_settings **out);
 void zkw_kzg_cell_settings_free(zkw_kzg_cell_settings *cs);
@@ -932,6 +933,38 @@ int zkw_kzg_verify_cells(const zkw_kzg_verifier *v64, const zkw_kzg_settings *s,
                          uint8_t *verdicts /*[n]*/);
 int zkw_kzg_commit_cells(const zkw_kzg_settings *s, zkw_ctx *ctx, const uint64_t *cell_indices /*[n]*/,
                          const uint8_t *cells /*[n][2048]*/, size_t n, uint8_t *out /*[n][48]*/);
+/* The setup in the Lagrange basis (KzgSettings::new, kzg/src/lib.rs:36-156: an inverse transform over the setup's G1 points,
+   kept in bit-reversed order as lagrange_setup_brp; every commitment of the reference is sum_i blob[i] lagrange_setup_brp[i]).
+   zkw_kzg_g1_fft_wide is zkw_kzg_g1_fft's contract with n a power of two from 1 to 4 096: natural order in and out, out[u] =
+   sum_j w_n^(u j) in[j], w_n = 7^((r-1)/n); inverse != 0: w_n^-1 and the factor 1/n; the same point checks, a bad point is
+   ZKW_ERR_INVALID naming "point k of transform t" with out untouched in both pointer modes.  At most 65 535 transforms and at
+   most 65 536 points per call (the lanes' window tables are 71 MB of context scratch then); more is ZKW_ERR_INVALID.  Up to
+   128 points it runs zkw_kzg_g1_fft's path and gives its bytes; above, m - 7 stages over HBM, the 128-point kernel on the
+   blocks, and one reordering pass.  zkw_kzg_g1_fft itself still stops at 128.
+   zkw_kzg_settings_to_lagrange makes a NEW handle, device to device, from the points S of a handle: S'[i] = L[brp(i)] with L
+   the inverse transform of S, so for S[k] = [tau^k] G1, L[u] = [l_u(tau)] G1, l_u the Lagrange polynomial of w_n^u — the
+   reference's lagrange_setup_brp.  num_points must be a power of two (1 and 2 included), the source of basis 0; the new handle
+   has basis 1.  Nothing is decompressed or subgroup-checked again.  As for zkw_kzg_settings_create the context must be on the
+   handle's device and not of a batch, the stream is synchronised before the handle is returned, and the new handle retains its
+   context and is independent of its source, which may be freed first.  zkw_kzg_settings_to_monomial is the way back
+   (un-bit-reverse, forward transform, a new handle of basis 0) and takes a handle of either basis: a handle that
+   zkw_kzg_settings_create made from the g1_lagrange list of a Lagrange-only setup file has basis 0, because the library cannot
+   know.  zkw_kzg_settings_points writes the compressed points a handle holds, in the handle's order: with it either basis can
+   be handed out.  zkw_kzg_settings_basis: 0 as created / monomial, 1 Lagrange.
+   zkw_kzg_commit knows no basis: on a basis-1 handle, with a blob's evaluations as little-endian "coefficients", it is the
+   reference's compute_commitment.  Every call that reads S[k] as [tau^k] G1 — zkw_eip4844_witness, zkw_kzg_open,
+   zkw_eip4844_prove, zkw_kzg_commit_blobs, zkw_kzg_open_blobs, zkw_eip4844_prove_blobs, zkw_kzg_cell_settings_create,
+   zkw_kzg_commit_cells, zkw_kzg_verify_cells — refuses a basis-1 handle ahead of its first launch (ZKW_ERR_INVALID naming the
+   Lagrange basis, outputs untouched).
+   Not offered: zkw_kzg_commit_blobs without its inverse transform on a Lagrange handle (that transform is 0.12 ms of the
+   call's 5.9 ms); a second table per handle (a handle is one basis; make two handles); transforms above 4 096 points (no setup
+   is longer); anything in G2 (the verifier needs one G2 point, not a basis). */
+int zkw_kzg_g1_fft_wide(zkw_ctx *ctx, const uint8_t *points /*[n_ffts][n][48]*/, size_t n, size_t n_ffts, int inverse,
+                        uint8_t *out /*[n_ffts][n][48]*/);
+int zkw_kzg_settings_to_lagrange(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_settings **out);
+int zkw_kzg_settings_to_monomial(const zkw_kzg_settings *s, zkw_ctx *ctx, zkw_kzg_settings **out);
+int zkw_kzg_settings_points(const zkw_kzg_settings *s, zkw_ctx *ctx, uint8_t *out /*[num_points][48]*/);
+int zkw_kzg_settings_basis(const zkw_kzg_settings *s); /* 0: as created / monomial, 1: Lagrange */
 
 /* ---- keccak256 / sha256 / ecrecover round-function witness builders (a16) ---------------------------- */
 typedef struct zkw_precompile_witness zkw_precompile_witness;

@@ -1,6 +1,6 @@
 """Writes era_zkevm_test_harness_amd/csrc/kzg_cell_tables.cuh: the constants of the EIP-7594 cell kernels (kzg_cell_kernels.cuh) that are
 not worth computing on the device — the GLV split of the 128 twiddles of the G1 transform, the endomorphism's beta, the 8 192nd root of
-unity W of the extended blob. `python tools/gen_kzg_cell_tables.py` rewrites the file, `--check` compares it with what is committed
+unity W of the extended blob, and for the wide G1 transform (kzg_g1_fft_wide_kernels.cuh) the split of the lower half of the 4 096th roots. `python tools/gen_kzg_cell_tables.py` rewrites the file, `--check` compares it with what is committed
 (tests/test_kzg_cells_model.py does the same and checks the statements the numbers rest on).
 
 BLS12-381 has the endomorphism phi(x, y) = (beta x, y) on G1, beta a primitive cube root of unity of Fq, and phi(P) = [lambda] P with
@@ -17,6 +17,7 @@ LAMBDA = Z * Z - 1
 BETA = 0x1A0111EA397FE699EC02408663D4DE85AA0D857D89759AD4897D29650FB85F9B409427EB4F49FFFD8BFD00000000AAAC
 W128 = pow(7, (R - 1) // 128, R)
 W8192 = pow(7, (R - 1) // 8192, R)
+W4096 = W8192 * W8192 % R
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "era_zkevm_test_harness_amd", "csrc", "kzg_cell_tables.cuh")
 
 
@@ -34,6 +35,11 @@ def words(v, n):
 def twiddle_rows():
     """row e: the split of W128^e (e < 128), then row 128 + b: the split of 2^-b mod r (b <= 7: the inverse transform's 1 / n)"""
     return [split(pow(W128, e, R)) for e in range(128)] + [split(pow(pow(2, b, R), -1, R)) for b in range(8)]
+
+
+def wide_twiddle_rows():
+    """row e: the split of W4096^e (e < 2048; the upper half is its negative), then row 2048 + b - 8: the split of 2^-b mod r (b = 8 .. 12)"""
+    return [split(pow(W4096, e, R)) for e in range(2048)] + [split(pow(pow(2, b, R), -1, R)) for b in range(8, 13)]
 
 
 def render():
@@ -58,6 +64,13 @@ def render():
               "static __device__ __forceinline__ bls::Fr kzg_cell_w() {",
               "    return bls::Fr{{%s}};" % words(W8192 * (1 << 256) % R, 8),
               "}",
+              "// rows 0..2047: w4096^e = k1 + k2 lambda for w4096 = 7^((r - 1) / 4096), the words as above (w4096^(2048 + e) = -w4096^e: the",
+              "// kernel negates the point); rows 2048..2052: the split of 2^-b mod r, b = 8 .. 12. 64 KiB: in global memory, not in a constant bank",
+              "static __device__ const bls::u32 d_kzg_g1_twiddle_wide[2053][8] = {"]
+    assert pow(W4096, 2048, R) == R - 1 and pow(W4096, 32, R) == W128
+    for k1, k2 in wide_twiddle_rows():
+        lines.append("    {%s, %s}," % (words(k1, 4), words(k2, 4)))
+    lines += ["};",
               "}  // namespace zkw",
               ""]
     return "\n".join(lines)
